@@ -12,7 +12,7 @@ then - N > 1 - the gather of the decoded images on rank 0).  ``--config`` picks 
 
 ``value`` is timed in the ACCURACY mode of the UNet (``residual_fp32``: the mode that meets north_star's
 "<= 1e-3 max latent-eps deviation vs reference"; round 6 - VERDICT r5 next #1); the all-fp16 mode (the reference's own
-GPU configuration, app.py:34) is timed beside it on three batches and reported as ``config.fast_fp16_value``
+GPU configuration, app.py:34) is timed beside it on three batches under ``--full`` and reported as ``config.fast_fp16_value``
 (``--fast-fp16`` swaps the two).  Everything a reader needs to judge the line is a FLAT scalar: ``config.mode``,
 ``config.eps_max`` / ``eps_bound`` / ``eps_rel`` / ``eps_max_unit_var``, ``config.fast_fp16_value``, the box calibration
 ``config.box_mfma_tflops`` / ``box_sclk_mhz`` / ``box_power_w`` / ``box_power_cap_w`` and ``roofline.*_frac``.
@@ -25,10 +25,16 @@ once, every rank samples its own images (weak scaling, no per-step collective).
     python bench.py --gpus 8                       (launches itself under torch.distributed.run, one rank per GPU)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 ... bench.py --gpus 8
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with `roofline` (dominant contraction kernel,
-HIP-event timed in an extra instrumented pass; `rocprof` = the committed rocprofv3 average of the same
-kernel on the same command, when profiles/ holds one) and `cpu_baseline` (the CPU oracle timed on this box's
-host cores on a bounded sample; baseline only).
+Prints ONE JSON line on rank 0 (contract in the task statement).  A plain run does only what that line's headline needs: set-up,
+--warmup batches, --steps timed batches (`value`, `ms_per_step`), the --dump-outputs files when asked for, the line.  Everything
+else runs with ``--full`` only: the box calibration (`config.box_*`), `roofline` (dominant contraction kernel, HIP-event timed in
+an extra instrumented pass; `rocprof` = the committed rocprofv3 average of the same kernel on the same command, when profiles/
+holds one), the second timed region in the other mode (`config.fast_fp16_value`), `cpu_baseline` (the CPU oracle timed on this
+box's host cores on a bounded sample; baseline only) and the eps / end-to-end checks against the fp32 oracle.  Under --full the
+--no-* switches below still drop single parts.
+
+    python bench.py --gpus 1 --steps 5 --warmup 1 --dump-outputs DIR     (DIR/images.npy, DIR/latents.npy: float32)
+    python bench.py --full                                                 (the whole line, as the recorded BENCH_*.json show it)
 """
 import argparse
 import csv
@@ -117,7 +123,21 @@ def parse():
     ap.add_argument("--shape-report", default=None, help="write a per-shape table of the GEMM / conv / attention launches of one batch")
     ap.add_argument("--first-sample", type=int, default=0, help="global index of rank 0's first sample (seeds depend on the global index only)")
     ap.add_argument("--dump-images", default=None, help="rank 0 saves the gathered result of the LAST timed batch (torch.save)")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="rank 0 writes what the LAST timed batch returned as DIR/<name>.npy in float32: images (the gathered uint8 images; "
+                         "--gather latents: the gathered latents) and latents (rank 0's final latents).  Over 60 MiB in all, a fixed "
+                         "seeded sample of the samples is kept and DIR/<name>_rows.npy lists their indices")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beyond the headline: box calibration, instrumented roofline pass, second timed region in "
+                         "the other mode, CPU baseline and the checks against the fp32 oracle (each still off with its --no-* switch)")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.shape_report and not args.full:
+        ap.error("--shape-report needs --full (the table comes from the instrumented roofline pass)")
+    if not args.full:
+        args.no_box_probe = args.no_roofline = args.no_second_mode = args.no_cpu_baseline = True
+    return args
 
 
 ATTN_NAMES = {16: "1, 1, 2", 32: "1, 2, 2", 40: "2, 3, 2", 64: "2, 4, 2", 80: "3, 5, 2", 160: "5, 10, 1"}
@@ -698,6 +718,29 @@ def plumbing_check(args, world, rank):
     dist.destroy_process_group()
 
 
+DUMP_BUDGET = 60 << 20      # --dump-outputs: bytes of .npy payload in all
+
+
+def dump_outputs(path, arrays, budget=DUMP_BUDGET, seed=0):
+    """Every array as <path>/<name>.npy in float32 (the uint8 images widen exactly).  When they hold more than `budget` bytes in all,
+    each keeps the same fraction of its leading (sample) dimension, drawn once from a fixed seed, in ascending order; then
+    <path>/<name>_rows.npy (float64) holds the indices kept."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    arrs = {k: v.detach().to("cpu", torch.float32) for k, v in arrays.items()}
+    frac = min(1.0, budget / sum(a.numel() * 4 for a in arrs.values()))
+    for name, a in arrs.items():
+        rows_file = os.path.join(path, f"{name}_rows.npy")
+        if os.path.exists(rows_file):
+            os.remove(rows_file)
+        if frac < 1.0:
+            keep = max(1, int(a.shape[0] * frac))
+            rows = torch.randperm(a.shape[0], generator=torch.Generator().manual_seed(seed))[:keep].sort().values
+            a = a[rows]
+            np.save(rows_file, rows.numpy().astype(np.float64))
+        np.save(os.path.join(path, f"{name}.npy"), a.contiguous().numpy())
+
+
 def _timed(one_batch, steps, warmup, barrier, dist, dev):
     out = None
     for _ in range(warmup):
@@ -787,6 +830,8 @@ def main():
     decode_s = sum(a.elapsed_time(b) for a, b in wl["decode_events"]) * 1e-3
     if rank == 0 and args.dump_images:
         torch.save(dict(images=out.cpu(), latents=lat_final.cpu()), args.dump_images)
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, dict(images=out, latents=lat_final) if args.gather == "images" else dict(latents=out))
 
     roof, cpu = None, None
     if rank == 0 and not args.no_roofline:

@@ -575,7 +575,7 @@ def test_bench_prints_one_contract_line():
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "1", "--warmup", "0", "--ddim-steps", "4",
-                        "--samples-per-gpu", "1", "--no-cpu-baseline"], capture_output=True, text=True, timeout=600)
+                        "--samples-per-gpu", "1", "--no-cpu-baseline", "--full"], capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1

@@ -889,7 +889,7 @@ def test_rccl_path_executes_on_one_gpu(tmp_path):
 @pytest.mark.parametrize("config", [4, 5])
 def test_bench_contract_line_configs_4_and_5(config):
     d = _bench(["--config", str(config), "--steps", "1", "--warmup", "0", "--ddim-steps", "2", "--samples-per-gpu", "1",
-                "--no-cpu-baseline"])
+                "--no-cpu-baseline", "--full"])
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
               "vs_baseline", "dtype", "data", "config", "roofline", "cpu_baseline"):
         assert k in d, k

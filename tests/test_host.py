@@ -265,6 +265,54 @@ def test_bench_workload_strings_survive_a_120_character_cut():
     assert abs(b.f_img_tflop(2, 50) - 107.65) < 0.01 and b.EPS_BOUND == 1e-3
 
 
+def test_bench_plain_run_is_lean_and_full_keeps_the_rest(monkeypatch):
+    """A plain `bench.py` turns off everything beyond the headline (box probe, roofline pass, second mode, CPU baseline); --full
+    brings it back, each part still off with its own --no-* switch; --shape-report needs the instrumented pass of --full."""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(ROOT, "bench.py"))
+    b = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(b)
+    extras = ("no_box_probe", "no_roofline", "no_second_mode", "no_cpu_baseline")
+
+    def parse(*argv):
+        monkeypatch.setattr(sys, "argv", ["bench.py", *argv])
+        return b.parse()
+    a = parse("--gpus", "1", "--steps", "7", "--warmup", "2")
+    assert a.steps == 7 and a.warmup == 2 and not a.full and a.dump_outputs is None and all(getattr(a, k) for k in extras)
+    a = parse("--full")
+    assert a.full and not any(getattr(a, k) for k in extras)
+    a = parse("--full", "--no-cpu-baseline")
+    assert a.no_cpu_baseline and not a.no_roofline
+    for bad in (["--shape-report", "x.txt"], ["--steps", "0"]):
+        with pytest.raises(SystemExit):
+            parse(*bad)
+
+
+def test_bench_dump_outputs_float32_within_budget(tmp_path):
+    """--dump-outputs: float32 .npy files, exact for uint8 images; over the budget a fixed seeded subset of samples is kept."""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(ROOT, "bench.py"))
+    b = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(b)
+    g = torch.Generator().manual_seed(3)
+    img = torch.randint(0, 256, (8, 16, 16, 3), generator=g, dtype=torch.uint8)
+    lat = torch.randn(8, 4, 2, 2, generator=g)
+    b.dump_outputs(str(tmp_path / "all"), dict(images=img, latents=lat))
+    got = np.load(tmp_path / "all" / "images.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, img.numpy().astype(np.float32))
+    assert np.array_equal(np.load(tmp_path / "all" / "latents.npy"), lat.numpy())
+    assert not (tmp_path / "all" / "images_rows.npy").exists()
+    budget = (img.numel() + lat.numel()) * 4 // 2
+    for d in ("s1", "s2"):
+        b.dump_outputs(str(tmp_path / d), dict(images=img, latents=lat), budget=budget)
+    rows = np.load(tmp_path / "s1" / "images_rows.npy")
+    assert rows.dtype == np.float64 and len(rows) == 4 and np.all(np.diff(rows) > 0)
+    assert np.array_equal(np.load(tmp_path / "s1" / "images.npy"), img.numpy()[rows.astype(np.int64)].astype(np.float32))
+    assert sum(os.path.getsize(tmp_path / "s1" / f"{n}.npy") for n in ("images", "latents")) <= budget + 256
+    for n in ("images", "images_rows", "latents", "latents_rows"):
+        assert np.array_equal(np.load(tmp_path / "s1" / f"{n}.npy"), np.load(tmp_path / "s2" / f"{n}.npy"))
+
+
 def test_shard_range_covers_everything():
     from sketch2img_amd.dist import shard_range
     for total in (1, 7, 8, 64, 65):
