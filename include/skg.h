@@ -365,7 +365,7 @@ int skg_geglu_bwd(const void* H, int ldh, const void* dY, int lddy, void* dH, in
  * [h*dh, (h+1)*dh).  Vt is V transposed: Vt[h*dh + d][b*kv_stride + j] (ldvt).  Only the first
  * Nkv of each batch row's kv_stride key slots are valid.  O [batch*Nq][..] (ldo).
  * lse (float [batch][heads][Nq], natural-log-sum-exp of the scaled scores) may be NULL.
- * dh in {16, 32, 40, 64, 80, 160}; kv_stride % 8 == 0.
+ * dh in {16, 32, 40, 64, 80, 160}; kv_stride % 8 == 0 (the V^T operand; the row-major-V forms below take any kv_stride).
  * Replaces: xformers memory_efficient_attention (enabled at app.py:43) / diffusers
  * CrossAttention baddbmm+softmax+bmm for attn1, attn2 and the injected sketch_attn
  * (modules/clip_guided_attn.py:114, modules/sketch_guided_attn.py:127). */
@@ -461,6 +461,14 @@ int skg_lgp_layer0_gather(const SkgLgpTap* taps, int ntaps, const void* Wextra, 
 /* adjoint of the bilinear part for ONE tap: dP [rows*s*s][H0] fp16 from dZ [rows*h*h][H0] fp16. */
 int skg_lgp_layer0_scatter(const void* dZ, int lddz, void* dP, int rows, int h, int s, int H0,
                            void* stream);
+/* Rectangular forms of the layer-0 pieces on an h x w grid (h, w multiples of 8; pixel order (y, x), pixel = y*w + x).
+ * A tap of height s has width s*w/h (the same power-of-two scale on both axes): P [rows*s*(s*w/h)][H0], noise / target
+ * float NCHW [samples][4][h][w].  With w == h they compute what the square entry points compute, bit for bit. */
+int skg_lgp_layer0_gather_hw(const SkgLgpTap* taps, int ntaps, const void* Wextra, int ldw,
+                             const void* bias0, const float* noise, float sigma, int samples,
+                             void* Z, int rows, int h, int w, int H0, void* stream);
+int skg_lgp_layer0_scatter_hw(const void* dZ, int lddz, void* dP, int rows, int h, int w, int s, int H0,
+                              void* stream);
 /* train-mode BatchNorm1d whose "batch" is ONE sample's LGP rows (the reference only runs B = 1:
  * SURVEY Q1/Q3).  Row layout of X: row = (j*samples + s)*seg_rows + i, j = 0..segs-1 (segs = 2 CFG
  * halves, seg_rows = h*h).  X is the post-ReLU activation fp16 [samples*segs*seg_rows][C].
@@ -490,6 +498,9 @@ int skg_bn_relu_bwd(const void* X, int ldx, const void* dY, int lddy, void* dX, 
  * columns >= 4 zeroed up to ldd.  Mirrors modules/pipeline.py:155-157. */
 int skg_lgp_mse_seed(const void* out, int ldo, const float* target, void* dOut, int ldd,
                      float* loss, int samples, int h, float loss_scale, void* stream);
+/* the same on an h x w grid (n = 4*h*w; h, w multiples of 8) */
+int skg_lgp_mse_seed_hw(const void* out, int ldo, const float* target, void* dOut, int ldd,
+                        float* loss, int samples, int h, int w, float loss_scale, void* stream);
 
 /* ---- LGP training (trainer.py:208-252: forward taps -> LGP -> MSE -> backward with weight gradients -> optimizer) --
  * The reference trains with accelerate fp16 autocast + bitsandbytes AdamW8bit; here: fp16 compute with a static loss
@@ -506,6 +517,9 @@ int skg_bn_param_grads(const void* X, int ldx, const void* dY, int lddy, int row
  * fp16, E [rows*h*h][ld] with columns >= 40 zeroed: the operand of the layer-0 weight gradient for those columns. */
 int skg_lgp_extra_features(const float* noise, float sigma, int samples, int rows, int h, void* E, int ld,
                            void* stream);
+/* the same on an h x w grid (E [rows*h*w][ld]; h, w multiples of 8) */
+int skg_lgp_extra_features_hw(const float* noise, float sigma, int samples, int rows, int h, int w, void* E, int ld,
+                              void* stream);
 /* Training loss (trainer.py:240): mean((out - target)^2) over samples*4*h*h; dOut = loss_scale * d loss / d out
  * (fp16 [samples*h*h][ldd], columns >= 4 zero); loss_parts[s] = this sample's share of the mean (sum them). */
 int skg_lgp_mse_train(const void* out, int ldo, const float* target, void* dOut, int ldd, float* loss_parts,

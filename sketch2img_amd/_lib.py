@@ -94,6 +94,8 @@ SIGNATURES = {
     "skg_nhwc_f16_to_nchw_f32": ("i", "pipiiip"),
     "skg_lgp_layer0_gather": ("i", "pipippfipiiip"),
     "skg_lgp_layer0_scatter": ("i", "pipiiiip"),
+    "skg_lgp_layer0_gather_hw": ("i", "pipippfipiiiip"),
+    "skg_lgp_layer0_scatter_hw": ("i", "pipiiiiip"),
     "skg_bn_scratch_floats": ("z", "ii"),
     "skg_bn_stats": ("i", "piiiiifppppp"),
     "skg_bn_stats_from_running": ("i", "ppiifpp"),
@@ -103,9 +105,11 @@ SIGNATURES = {
     "skg_colsum_f16": ("i", "piiifppp"),
     "skg_bn_param_grads": ("i", "pipiiipfpppp"),
     "skg_lgp_extra_features": ("i", "pfiiipip"),
+    "skg_lgp_extra_features_hw": ("i", "pfiiiipip"),
     "skg_lgp_mse_train": ("i", "pippipiifp"),
     "skg_adamw_step": ("i", "pppppzfffffifp"),
     "skg_lgp_mse_seed": ("i", "pippipiifp"),
+    "skg_lgp_mse_seed_hw": ("i", "pippipiiifp"),
     "skg_cfg_ddim_step": ("i", "ppiipppiifffffip"),
     "skg_softmax_rows_f16": ("i", "pipiiip"),
     "skg_image_postprocess": ("i", "pipziffp"),

@@ -1459,8 +1459,12 @@ inline int attn_var() {
   return v;
 }
 
-inline bool common_ok(int batch, int heads, int Nq, int Nkv, int kv_stride, int dh) {
-  return batch > 0 && heads > 0 && Nq > 0 && Nkv > 0 && kv_stride >= Nkv && kv_stride % 8 == 0 && dh % 8 == 0;
+// kv8: kv_stride % 8 == 0 - only the transposed V^T operand needs it (16-byte loads along the key axis start at b * kv_stride).
+// Row-major K / V rows are addressed row by row (buffer descriptors sized to this batch row's keys, or explicit key < Nkv
+// tests), so the forms that read V row-major take any kv_stride: the self-attention of a non-square map has HW keys per
+// image, e.g. 5 x 9 = 45 at the deepest level of 320 x 576 px.
+inline bool common_ok(int batch, int heads, int Nq, int Nkv, int kv_stride, int dh, bool kv8 = true) {
+  return batch > 0 && heads > 0 && Nq > 0 && Nkv > 0 && kv_stride >= Nkv && (!kv8 || kv_stride % 8 == 0) && dh % 8 == 0;
 }
 
 }  // namespace
@@ -1468,7 +1472,7 @@ inline bool common_ok(int batch, int heads, int Nq, int Nkv, int kv_stride, int 
 static int attn_fwd_impl(const void* Q, int ldq, const void* K, int ldk, const void* Vt, int ldvt, void* O,
                          int ldo, float* lse, int batch, int heads, int Nq, int Nkv, int kv_stride, int dh,
                          float scale, bool causal, void* stream, bool vrow = false) {
-  SKG_REQUIRE(Q && K && Vt && O && common_ok(batch, heads, Nq, Nkv, kv_stride, dh));
+  SKG_REQUIRE(Q && K && Vt && O && common_ok(batch, heads, Nq, Nkv, kv_stride, dh, !vrow));
   SKG_REQUIRE(ldq % 8 == 0 && ldk % 8 == 0 && ldvt % 8 == 0 && ldo % 4 == 0);
   SKG_REQUIRE(skg_aligned(Q, 16) && skg_aligned(K, 16) && skg_aligned(Vt, 16) && skg_aligned(O, 8));
   AttnParams p{};
@@ -1579,7 +1583,7 @@ extern "C" int skg_attn_bwd_delta(const void* O, int ldo, const void* dO, int ld
 static int attn_bwd_dq_impl(const void* Q, int ldq, const void* K, int ldk, const void* V, int ldv, const void* dO, int lddo,
                             const float* lse, const float* delta, void* dQ, int lddq, int batch, int heads, int Nq, int Nkv,
                             int kv_stride, int dh, float scale, void* stream, const void* O, int ldo, float* delta_out) {
-  SKG_REQUIRE(Q && K && V && dO && lse && (delta || (O && delta_out)) && dQ && common_ok(batch, heads, Nq, Nkv, kv_stride, dh));
+  SKG_REQUIRE(Q && K && V && dO && lse && (delta || (O && delta_out)) && dQ && common_ok(batch, heads, Nq, Nkv, kv_stride, dh, false));
   SKG_REQUIRE(!O || (ldo % 8 == 0 && skg_aligned(O, 16)));
   SKG_REQUIRE(ldq % 8 == 0 && ldk % 8 == 0 && ldv % 8 == 0 && lddo % 8 == 0 && lddq % 4 == 0);
   SKG_REQUIRE(skg_aligned(Q, 16) && skg_aligned(K, 16) && skg_aligned(V, 16) && skg_aligned(dO, 16) && skg_aligned(dQ, 8));
@@ -1628,7 +1632,7 @@ extern "C" int skg_attn_bwd_dkv(const void* Q, int ldq, const void* K, int ldk,
                                 const void* V, int ldv, const void* dO, int lddo,
                                 const float* lse, const float* delta, void* dK, int lddk, void* dV, int lddv,
                                 int batch, int heads, int Nq, int Nkv, int dh, float scale, void* stream) {
-  SKG_REQUIRE(Q && K && V && dO && lse && delta && dK && dV && common_ok(batch, heads, Nq, Nkv, Nkv, dh));
+  SKG_REQUIRE(Q && K && V && dO && lse && delta && dK && dV && common_ok(batch, heads, Nq, Nkv, Nkv, dh, false));
   SKG_REQUIRE(ldq % 8 == 0 && ldk % 8 == 0 && ldv % 8 == 0 && lddo % 8 == 0 && lddk % 4 == 0 && lddv % 4 == 0);
   SKG_REQUIRE(skg_aligned(Q, 16) && skg_aligned(K, 16) && skg_aligned(V, 16) &&
               skg_aligned(dO, 16) && skg_aligned(dK, 8) && skg_aligned(dV, 8));

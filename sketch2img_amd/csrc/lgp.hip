@@ -3,7 +3,8 @@
 // BatchNorm1d (stats / apply / backward through the preceding ReLU) and the MSE seed gradient.
 //
 // Row layout of every LGP activation: row = (j * S + s) * hw + pixel with j = CFG half (0 = uncond,
-// 1 = cond), s = sample, pixel = y * h + x.  One BatchNorm "batch" is one sample's two CFG rows
+// 1 = cond), s = sample, pixel = y * w + x on the h x w grid.  A tap of height s has width s * w / h (every tap sits at
+// the same power-of-two scale on both axes).  One BatchNorm "batch" is one sample's two CFG rows
 // (2*hw LGP rows): the reference only runs B = 1, so statistics are per sample.
 #include "common.h"
 
@@ -33,16 +34,16 @@ __device__ __forceinline__ void bil_coord(int d, int s, int h, int& i0, int& i1,
 __global__ __launch_bounds__(256) void lgp_gather_kernel(const TapArgs taps, const half_t* __restrict__ Wx, int ldw,
                                                          const half_t* __restrict__ bias0,
                                                          const float* __restrict__ noise, float sigma, int S,
-                                                         half_t* __restrict__ Z, int rows, int h, int H0) {
+                                                         half_t* __restrict__ Z, int rows, int h, int w, int H0) {
   __shared__ float e_s[2][NEXTRA];
-  const int hw = h * h;
+  const int hw = h * w;
   const int half_id = threadIdx.x >> 7;
   const int tl = threadIdx.x & 127;
   const size_t pix = (size_t)blockIdx.x * 2 + half_id;   // over rows*hw
   const bool ok = pix < (size_t)rows * hw;
   const int row = ok ? (int)(pix / hw) : 0;
   const int pp = ok ? (int)(pix - (size_t)row * hw) : 0;
-  const int y = pp / h, x = pp - y * h;
+  const int y = pp / w, x = pp - y * w;
   const int smp = row % S;
   if (tl < NEXTRA) {
     const int c = tl < 4 ? tl : (tl - 4) & 3;
@@ -59,29 +60,29 @@ __global__ __launch_bounds__(256) void lgp_gather_kernel(const TapArgs taps, con
   for (int c0 = tl * 4; c0 < H0; c0 += 512) {
     float4_t acc = {0.f, 0.f, 0.f, 0.f};
     for (int i = 0; i < taps.n; ++i) {
-      const int s = taps.s[i];
-      const float* P = taps.P[i] + (size_t)row * s * s * H0 + c0;
+      const int s = taps.s[i], sw = s * w / h;
+      const float* P = taps.P[i] + (size_t)row * s * sw * H0 + c0;
       if (s == h) {
         acc += *reinterpret_cast<const float4_t*>(P + (size_t)pp * H0);
       } else {
         int y0, y1, x0, x1;
         float wy, wx;
         bil_coord(y, s, h, y0, y1, wy);
-        bil_coord(x, s, h, x0, x1, wx);
-        const float4_t v00 = *reinterpret_cast<const float4_t*>(P + (size_t)(y0 * s + x0) * H0);
-        const float4_t v01 = *reinterpret_cast<const float4_t*>(P + (size_t)(y0 * s + x1) * H0);
-        const float4_t v10 = *reinterpret_cast<const float4_t*>(P + (size_t)(y1 * s + x0) * H0);
-        const float4_t v11 = *reinterpret_cast<const float4_t*>(P + (size_t)(y1 * s + x1) * H0);
+        bil_coord(x, sw, w, x0, x1, wx);
+        const float4_t v00 = *reinterpret_cast<const float4_t*>(P + (size_t)(y0 * sw + x0) * H0);
+        const float4_t v01 = *reinterpret_cast<const float4_t*>(P + (size_t)(y0 * sw + x1) * H0);
+        const float4_t v10 = *reinterpret_cast<const float4_t*>(P + (size_t)(y1 * sw + x0) * H0);
+        const float4_t v11 = *reinterpret_cast<const float4_t*>(P + (size_t)(y1 * sw + x1) * H0);
         acc += (1.f - wy) * ((1.f - wx) * v00 + wx * v01) + wy * ((1.f - wx) * v10 + wx * v11);
       }
     }
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
-      const half_t* w = Wx + (size_t)(c0 + j) * ldw;
+      const half_t* wr = Wx + (size_t)(c0 + j) * ldw;
       float d = 0.f;
 #pragma unroll
       for (int k = 0; k < NEXTRA; k += 8) {
-        const half8_t wv = ld_half8(w + k);
+        const half8_t wv = ld_half8(wr + k);
 #pragma unroll
         for (int q = 0; q < 8; ++q) d += (float)wv[q] * e_s[half_id][k + q];
       }
@@ -103,11 +104,11 @@ constexpr int GT = 8, GC = 128, GPITCH = GC + 4;
 __global__ __launch_bounds__(256) void lgp_gather_tiled_kernel(const TapArgs taps, const half_t* __restrict__ Wx, int ldw,
                                                                const half_t* __restrict__ bias0,
                                                                const float* __restrict__ noise, float sigma, int S,
-                                                               half_t* __restrict__ Z, int rows, int h, int H0) {
+                                                               half_t* __restrict__ Z, int rows, int h, int w, int H0) {
   __shared__ __attribute__((aligned(16))) float patch[GT * GT * GPITCH];
   __shared__ float e_s[GT * GT][NEXTRA];
-  const int hw = h * h;
-  const int tiles = h / GT;
+  const int hw = h * w;
+  const int tiles = w / GT;
   const int ty = blockIdx.x / tiles, tx = blockIdx.x - ty * tiles;
   const int row = blockIdx.y, cbase = blockIdx.z * GC;
   const int tid = threadIdx.x;
@@ -117,7 +118,7 @@ __global__ __launch_bounds__(256) void lgp_gather_tiled_kernel(const TapArgs tap
   const int smp = row % S;
   for (int i = tid; Wx != nullptr && i < GT * GT * NEXTRA; i += 256) {
     const int p = i / NEXTRA, tl = i - p * NEXTRA;
-    const int pp = (ty * GT + (p >> 3)) * h + tx * GT + (p & 7);
+    const int pp = (ty * GT + (p >> 3)) * w + tx * GT + (p & 7);
     const int c = tl < 4 ? tl : (tl - 4) & 3;
     const float nl = sigma * noise[((size_t)smp * 4 + c) * hw + pp];
     float v = nl;
@@ -128,27 +129,27 @@ __global__ __launch_bounds__(256) void lgp_gather_tiled_kernel(const TapArgs tap
 #pragma unroll
   for (int q = 0; q < 8; ++q) acc[q] = float4_t{0.f, 0.f, 0.f, 0.f};
   for (int i = 0; i < taps.n; ++i) {
-    const int s = taps.s[i];
+    const int s = taps.s[i], sw = s * w / h;
     int sy0, sx0, nrow, ncol;
     if (s == h) {
       sy0 = ty * GT; sx0 = tx * GT; nrow = ncol = GT;
     } else {
       int a0, a1, b0, b1;
-      float w;
-      bil_coord(ty * GT, s, h, a0, a1, w);
-      bil_coord(ty * GT + GT - 1, s, h, b0, b1, w);
+      float wt;
+      bil_coord(ty * GT, s, h, a0, a1, wt);
+      bil_coord(ty * GT + GT - 1, s, h, b0, b1, wt);
       sy0 = a0; nrow = b1 - a0 + 1;
-      bil_coord(tx * GT, s, h, a0, a1, w);
-      bil_coord(tx * GT + GT - 1, s, h, b0, b1, w);
+      bil_coord(tx * GT, sw, w, a0, a1, wt);
+      bil_coord(tx * GT + GT - 1, sw, w, b0, b1, wt);
       sx0 = a0; ncol = b1 - a0 + 1;
     }
     __syncthreads();                                   // the previous tap's window has been consumed
-    const float* P = taps.P[i] + (size_t)row * s * s * H0 + cbase;
+    const float* P = taps.P[i] + (size_t)row * s * sw * H0 + cbase;
     for (int idx = tid; idx < nrow * ncol * (GC / 4); idx += 256) {
       const int sp = idx / (GC / 4), q = idx - sp * (GC / 4);
       const int sy = sp / ncol, sx = sp - sy * ncol;
       *reinterpret_cast<float4_t*>(&patch[sp * GPITCH + q * 4]) =
-          *reinterpret_cast<const float4_t*>(P + (size_t)((sy0 + sy) * s + sx0 + sx) * H0 + q * 4);
+          *reinterpret_cast<const float4_t*>(P + (size_t)((sy0 + sy) * sw + sx0 + sx) * H0 + q * 4);
     }
     __syncthreads();
     const float* pc = patch + cg * 32;
@@ -160,7 +161,7 @@ __global__ __launch_bounds__(256) void lgp_gather_tiled_kernel(const TapArgs tap
       int y0, y1, x0, x1;
       float wy, wx;
       bil_coord(oy, s, h, y0, y1, wy);
-      bil_coord(ox, s, h, x0, x1, wx);
+      bil_coord(ox, sw, w, x0, x1, wx);
       const float* p00 = pc + ((y0 - sy0) * ncol + (x0 - sx0)) * GPITCH;
       const float* p01 = pc + ((y0 - sy0) * ncol + (x1 - sx0)) * GPITCH;
       const float* p10 = pc + ((y1 - sy0) * ncol + (x0 - sx0)) * GPITCH;
@@ -175,7 +176,7 @@ __global__ __launch_bounds__(256) void lgp_gather_tiled_kernel(const TapArgs tap
       }
     }
   }
-  const size_t orow = (size_t)row * hw + (size_t)oy * h + ox;
+  const size_t orow = (size_t)row * hw + (size_t)oy * w + ox;
   half_t* zo = Z + orow * H0 + cbase + cg * 32;
 #pragma unroll
   for (int q = 0; q < 8; ++q) {
@@ -185,10 +186,10 @@ __global__ __launch_bounds__(256) void lgp_gather_tiled_kernel(const TapArgs tap
       const int c = cbase + cg * 32 + q * 4 + j;
       float d = 0.f;
       if (Wx != nullptr) {       // (callers normally pass the 40 extra channels as one more s == h tap instead)
-        const half_t* w = Wx + (size_t)c * ldw;
+        const half_t* wr = Wx + (size_t)c * ldw;
 #pragma unroll
         for (int k = 0; k < NEXTRA; k += 8) {
-          const half8_t wv = ld_half8(w + k);
+          const half8_t wv = ld_half8(wr + k);
 #pragma unroll
           for (int u = 0; u < 8; ++u) d += (float)wv[u] * e_s[pix][k + u];
         }
@@ -206,27 +207,29 @@ __global__ __launch_bounds__(256) void lgp_gather_tiled_kernel(const TapArgs tap
 // so the inner loop is a multiply, a test and a load + 8 FMAs (the first version redid both coordinate computations and
 // an integer division for every window pixel: ~40 VALU per 16-byte load, and two thirds of the window has zero weight).
 __global__ __launch_bounds__(256) void lgp_scatter_kernel(const half_t* __restrict__ dZ, int lddz,
-                                                          half_t* __restrict__ dP, int rows, int h, int s, int H0) {
+                                                          half_t* __restrict__ dP, int rows, int h, int w, int s,
+                                                          int H0) {
   __shared__ float red[256][9];
   __shared__ float cys[256], cxs[256];
-  const int ss = s * s;
+  const int sw = s * w / h;
+  const int ss = s * sw;
   const int row = blockIdx.x / ss;
   const int np = blockIdx.x - row * ss;
-  const int py = np / s, px = np - py * s;
+  const int py = np / sw, px = np - py * sw;
   const int f = h / s;
   const int ylo = max(0, f * py - f), yhi = min(h - 1, f * py + 2 * f - 1);
-  const int xlo = max(0, f * px - f), xhi = min(h - 1, f * px + 2 * f - 1);
+  const int xlo = max(0, f * px - f), xhi = min(w - 1, f * px + 2 * f - 1);
   const int wy_n = yhi - ylo + 1, wx_n = xhi - xlo + 1;
   const bool tab = wy_n <= 256 && wx_n <= 256;            // (always, for the resolutions of the pipeline)
-  auto coef = [&](int v, int p) {
+  auto coef = [&](int v, int p, int n, int d) {          // weight of native index p (of n) at output index v (of d)
     int v0, v1;
-    float w;
-    bil_coord(v, s, h, v0, v1, w);
-    return (v0 == p ? 1.f - w : 0.f) + (v1 == p ? w : 0.f);
+    float wt;
+    bil_coord(v, n, d, v0, v1, wt);
+    return (v0 == p ? 1.f - wt : 0.f) + (v1 == p ? wt : 0.f);
   };
   if (tab) {
-    for (int i = threadIdx.x; i < wy_n; i += 256) cys[i] = coef(ylo + i, py);
-    for (int i = threadIdx.x; i < wx_n; i += 256) cxs[i] = coef(xlo + i, px);
+    for (int i = threadIdx.x; i < wy_n; i += 256) cys[i] = coef(ylo + i, py, s, h);
+    for (int i = threadIdx.x; i < wx_n; i += 256) cxs[i] = coef(xlo + i, px, sw, w);
     __syncthreads();
   }
   const int C8 = H0 >> 3;
@@ -238,15 +241,15 @@ __global__ __launch_bounds__(256) void lgp_scatter_kernel(const half_t* __restri
     float a[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
     if (wl < WL) {
       for (int yy = wl; yy < wy_n; yy += WL) {
-        const float cy = tab ? cys[yy] : coef(ylo + yy, py);
+        const float cy = tab ? cys[yy] : coef(ylo + yy, py, s, h);
         if (cy == 0.f) continue;
-        const half_t* src = dZ + ((size_t)row * h * h + (size_t)(ylo + yy) * h + xlo) * lddz + c0;
+        const half_t* src = dZ + ((size_t)row * h * w + (size_t)(ylo + yy) * w + xlo) * lddz + c0;
         for (int xx = 0; xx < wx_n; ++xx) {
-          const float w = cy * (tab ? cxs[xx] : coef(xlo + xx, px));
-          if (w == 0.f) continue;
+          const float wt = cy * (tab ? cxs[xx] : coef(xlo + xx, px, sw, w));
+          if (wt == 0.f) continue;
           const half8_t v = ld_half8(src + (size_t)xx * lddz);
 #pragma unroll
-          for (int j = 0; j < 8; ++j) a[j] += w * (float)v[j];
+          for (int j = 0; j < 8; ++j) a[j] += wt * (float)v[j];
         }
       }
     }
@@ -481,11 +484,10 @@ __global__ __launch_bounds__(256) void bn_apply_kernel(const half_t* __restrict_
 // one pixel (8 bytes) per thread and iteration.
 __global__ __launch_bounds__(256) void mse_seed_kernel(const half_t* __restrict__ out, int ldo,
                                                        const float* __restrict__ target, half_t* __restrict__ dOut,
-                                                       int ldd, float* __restrict__ loss, int S, int h,
+                                                       int ldd, float* __restrict__ loss, int S, int hw,
                                                        float loss_scale) {
   __shared__ float red[8];
   const int s = blockIdx.x;
-  const int hw = h * h;
   const float k = loss_scale * 2.f / (4.f * hw);
   float acc = 0.f;
   for (int p = threadIdx.x; p < hw; p += 256) {
@@ -553,8 +555,7 @@ __global__ void bn_param_grads_kernel(const float* __restrict__ partial, int C, 
 // the 40 extra input channels of layer 0 (noise level + 36 sinusoids), fp16-rounded like the reference's cast:
 // E [rows*hw][ld] with columns >= 40 zero.  Same arithmetic as lgp_gather_kernel.
 __global__ __launch_bounds__(256) void lgp_extra_kernel(const float* __restrict__ noise, float sigma, int S, int rows,
-                                                        int h, half_t* __restrict__ E, int ld) {
-  const int hw = h * h;
+                                                        int hw, half_t* __restrict__ E, int ld) {
   const size_t total = (size_t)rows * hw * ld;
   for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
     const size_t pix = i / ld;
@@ -626,41 +627,91 @@ inline int ew_grid(size_t total_items) {
 
 }  // namespace
 
-extern "C" int skg_lgp_layer0_gather(const SkgLgpTap* taps, int ntaps, const void* Wextra, int ldw,
-                                     const void* bias0, const float* noise, float sigma, int samples, void* Z,
-                                     int rows, int h, int H0, void* stream) {
-  SKG_REQUIRE(taps && ntaps > 0 && ntaps <= MAX_TAPS && bias0 && noise && Z && rows > 0 && h > 0);
+// a tap of height s on the h x w grid: s divides h and the tap's width s * w / h divides w (the same scale on both axes)
+static inline bool tap_fits(int s, int h, int w) {
+  return s > 0 && h % s == 0 && ((long long)s * w) % h == 0 && w % (int)((long long)s * w / h) == 0;
+}
+
+// the square entry points pass w = h (same kernels, same arithmetic); the _hw ones add the 8-multiple sides
+static int lgp_gather(const SkgLgpTap* taps, int ntaps, const void* Wextra, int ldw, const void* bias0, const float* noise,
+               float sigma, int samples, void* Z, int rows, int h, int w, int H0, void* stream) {
+  SKG_REQUIRE(taps && ntaps > 0 && ntaps <= MAX_TAPS && bias0 && noise && Z && rows > 0 && h > 0 && w > 0);
   SKG_REQUIRE(H0 % 4 == 0 && skg_aligned(Z, 8) && samples > 0 && rows % samples == 0);
-  SKG_REQUIRE(Wextra ? (ldw % 8 == 0 && skg_aligned(Wextra, 16)) : (h % GT == 0 && H0 % GC == 0));
+  SKG_REQUIRE(Wextra ? (ldw % 8 == 0 && skg_aligned(Wextra, 16)) : (h % GT == 0 && w % GT == 0 && H0 % GC == 0));
   TapArgs a{};
   a.n = ntaps;
   for (int i = 0; i < ntaps; ++i) {
-    SKG_REQUIRE(taps[i].P && taps[i].s > 0 && h % taps[i].s == 0 && skg_aligned(taps[i].P, 16));
+    SKG_REQUIRE(taps[i].P && tap_fits(taps[i].s, h, w) && skg_aligned(taps[i].P, 16));
     a.P[i] = taps[i].P;
     a.s[i] = taps[i].s;
   }
-  if (h % GT == 0 && H0 % GC == 0) {
-    hipLaunchKernelGGL(lgp_gather_tiled_kernel, dim3((h / GT) * (h / GT), rows, H0 / GC), dim3(256), 0,
+  if (h % GT == 0 && w % GT == 0 && H0 % GC == 0) {
+    hipLaunchKernelGGL(lgp_gather_tiled_kernel, dim3((h / GT) * (w / GT), rows, H0 / GC), dim3(256), 0,
                        (hipStream_t)stream, a, (const half_t*)Wextra, ldw, (const half_t*)bias0, noise, sigma, samples,
-                       (half_t*)Z, rows, h, H0);
+                       (half_t*)Z, rows, h, w, H0);
     SKG_CHECK_LAUNCH("skg_lgp_layer0_gather");
     return SKG_OK;
   }
-  const size_t pixels = (size_t)rows * h * h;
+  const size_t pixels = (size_t)rows * h * w;
   hipLaunchKernelGGL(lgp_gather_kernel, dim3((unsigned)((pixels + 1) / 2)), dim3(256), 0, (hipStream_t)stream, a,
-                     (const half_t*)Wextra, ldw, (const half_t*)bias0, noise, sigma, samples, (half_t*)Z, rows, h, H0);
+                     (const half_t*)Wextra, ldw, (const half_t*)bias0, noise, sigma, samples, (half_t*)Z, rows, h, w, H0);
   SKG_CHECK_LAUNCH("skg_lgp_layer0_gather");
   return SKG_OK;
 }
 
-extern "C" int skg_lgp_layer0_scatter(const void* dZ, int lddz, void* dP, int rows, int h, int s, int H0,
-                                      void* stream) {
-  SKG_REQUIRE(dZ && dP && rows > 0 && h > 0 && s > 0 && h % s == 0 && H0 % 8 == 0 && lddz % 8 == 0 &&
+static int lgp_scatter(const void* dZ, int lddz, void* dP, int rows, int h, int w, int s, int H0, void* stream) {
+  SKG_REQUIRE(dZ && dP && rows > 0 && h > 0 && w > 0 && tap_fits(s, h, w) && H0 % 8 == 0 && lddz % 8 == 0 &&
               skg_aligned(dZ, 16) && skg_aligned(dP, 16));
-  hipLaunchKernelGGL(lgp_scatter_kernel, dim3(rows * s * s), dim3(256), 0, (hipStream_t)stream, (const half_t*)dZ,
-                     lddz, (half_t*)dP, rows, h, s, H0);
+  hipLaunchKernelGGL(lgp_scatter_kernel, dim3(rows * s * (s * w / h)), dim3(256), 0, (hipStream_t)stream,
+                     (const half_t*)dZ, lddz, (half_t*)dP, rows, h, w, s, H0);
   SKG_CHECK_LAUNCH("skg_lgp_layer0_scatter");
   return SKG_OK;
+}
+
+static int lgp_mse_seed(const void* out, int ldo, const float* target, void* dOut, int ldd, float* loss, int samples, int h,
+                 int w, float loss_scale, void* stream) {
+  SKG_REQUIRE(out && target && dOut && samples > 0 && h > 0 && w > 0 && ldo >= 4 && ldd >= 4 && ldo % 4 == 0 &&
+              ldd % 4 == 0);
+  SKG_REQUIRE(skg_aligned(out, 8) && skg_aligned(dOut, 8));
+  if (hipMemsetAsync(dOut, 0, (size_t)2 * samples * h * w * ldd * sizeof(half_t), (hipStream_t)stream) != hipSuccess)
+    return SKG_E_LAUNCH;
+  hipLaunchKernelGGL(mse_seed_kernel, dim3(samples), dim3(256), 0, (hipStream_t)stream, (const half_t*)out, ldo,
+                     target, (half_t*)dOut, ldd, loss, samples, h * w, loss_scale);
+  SKG_CHECK_LAUNCH("skg_lgp_mse_seed");
+  return SKG_OK;
+}
+
+static int lgp_extra_features(const float* noise, float sigma, int samples, int rows, int h, int w, void* E, int ld,
+                       void* stream) {
+  SKG_REQUIRE(noise && E && samples > 0 && rows > 0 && rows % samples == 0 && h > 0 && w > 0 && ld >= NEXTRA);
+  hipLaunchKernelGGL(lgp_extra_kernel, dim3(ew_grid((size_t)rows * h * w * ld)), dim3(256), 0, (hipStream_t)stream,
+                     noise, sigma, samples, rows, h * w, (half_t*)E, ld);
+  SKG_CHECK_LAUNCH("skg_lgp_extra_features");
+  return SKG_OK;
+}
+
+extern "C" int skg_lgp_layer0_gather(const SkgLgpTap* taps, int ntaps, const void* Wextra, int ldw,
+                                     const void* bias0, const float* noise, float sigma, int samples, void* Z,
+                                     int rows, int h, int H0, void* stream) {
+  return lgp_gather(taps, ntaps, Wextra, ldw, bias0, noise, sigma, samples, Z, rows, h, h, H0, stream);
+}
+
+extern "C" int skg_lgp_layer0_gather_hw(const SkgLgpTap* taps, int ntaps, const void* Wextra, int ldw,
+                                        const void* bias0, const float* noise, float sigma, int samples, void* Z,
+                                        int rows, int h, int w, int H0, void* stream) {
+  SKG_REQUIRE(h > 0 && w > 0 && h % GT == 0 && w % GT == 0);
+  return lgp_gather(taps, ntaps, Wextra, ldw, bias0, noise, sigma, samples, Z, rows, h, w, H0, stream);
+}
+
+extern "C" int skg_lgp_layer0_scatter(const void* dZ, int lddz, void* dP, int rows, int h, int s, int H0,
+                                      void* stream) {
+  return lgp_scatter(dZ, lddz, dP, rows, h, h, s, H0, stream);
+}
+
+extern "C" int skg_lgp_layer0_scatter_hw(const void* dZ, int lddz, void* dP, int rows, int h, int w, int s, int H0,
+                                         void* stream) {
+  SKG_REQUIRE(h > 0 && w > 0 && h % GT == 0 && w % GT == 0);
+  return lgp_scatter(dZ, lddz, dP, rows, h, w, s, H0, stream);
 }
 
 extern "C" size_t skg_bn_scratch_floats(int samples, int C) {
@@ -729,14 +780,13 @@ extern "C" int skg_bn_relu_bwd(const void* X, int ldx, const void* dY, int lddy,
 
 extern "C" int skg_lgp_mse_seed(const void* out, int ldo, const float* target, void* dOut, int ldd, float* loss,
                                 int samples, int h, float loss_scale, void* stream) {
-  SKG_REQUIRE(out && target && dOut && samples > 0 && h > 0 && ldo >= 4 && ldd >= 4 && ldo % 4 == 0 && ldd % 4 == 0);
-  SKG_REQUIRE(skg_aligned(out, 8) && skg_aligned(dOut, 8));
-  if (hipMemsetAsync(dOut, 0, (size_t)2 * samples * h * h * ldd * sizeof(half_t), (hipStream_t)stream) != hipSuccess)
-    return SKG_E_LAUNCH;
-  hipLaunchKernelGGL(mse_seed_kernel, dim3(samples), dim3(256), 0, (hipStream_t)stream, (const half_t*)out, ldo,
-                     target, (half_t*)dOut, ldd, loss, samples, h, loss_scale);
-  SKG_CHECK_LAUNCH("skg_lgp_mse_seed");
-  return SKG_OK;
+  return lgp_mse_seed(out, ldo, target, dOut, ldd, loss, samples, h, h, loss_scale, stream);
+}
+
+extern "C" int skg_lgp_mse_seed_hw(const void* out, int ldo, const float* target, void* dOut, int ldd, float* loss,
+                                   int samples, int h, int w, float loss_scale, void* stream) {
+  SKG_REQUIRE(h > 0 && w > 0 && h % GT == 0 && w % GT == 0);
+  return lgp_mse_seed(out, ldo, target, dOut, ldd, loss, samples, h, w, loss_scale, stream);
 }
 
 // ---- training entry points ----------------------------------------------------------------------------------------
@@ -768,11 +818,13 @@ extern "C" int skg_bn_param_grads(const void* X, int ldx, const void* dY, int ld
 
 extern "C" int skg_lgp_extra_features(const float* noise, float sigma, int samples, int rows, int h, void* E, int ld,
                                       void* stream) {
-  SKG_REQUIRE(noise && E && samples > 0 && rows > 0 && rows % samples == 0 && h > 0 && ld >= NEXTRA);
-  hipLaunchKernelGGL(lgp_extra_kernel, dim3(ew_grid((size_t)rows * h * h * ld)), dim3(256), 0, (hipStream_t)stream,
-                     noise, sigma, samples, rows, h, (half_t*)E, ld);
-  SKG_CHECK_LAUNCH("skg_lgp_extra_features");
-  return SKG_OK;
+  return lgp_extra_features(noise, sigma, samples, rows, h, h, E, ld, stream);
+}
+
+extern "C" int skg_lgp_extra_features_hw(const float* noise, float sigma, int samples, int rows, int h, int w, void* E,
+                                         int ld, void* stream) {
+  SKG_REQUIRE(h > 0 && w > 0 && h % GT == 0 && w % GT == 0);
+  return lgp_extra_features(noise, sigma, samples, rows, h, w, E, ld, stream);
 }
 
 extern "C" int skg_lgp_mse_train(const void* out, int ldo, const float* target, void* dOut, int ldd,

@@ -65,22 +65,26 @@ class HipLGP:
 
     # ---------------------------------------------------------------------------------------------
     def forward(self, taps: Sequence[Tuple[torch.Tensor, int]], noise: torch.Tensor, sigma: float, S: int,
-                h: int, keep: Optional[dict] = None) -> torch.Tensor:
-        """taps: 9 x (fp16 [2S*s*s, C_i], s).  noise fp32 [S,4,h,h].  Returns fp16 [2S*h*h, 8] (first
-        ``out_dim`` columns valid), rows = [uncond block; cond block], pixels in (y, x) order."""
-        hw = h * h
+                h: int, keep: Optional[dict] = None, w: Optional[int] = None) -> torch.Tensor:
+        """taps: 9 x (fp16 [2S*s*s, C_i], s) - or (tensor, (s, sw)) on a non-square grid.  noise fp32 [S,4,h,w].
+        Returns fp16 [2S*h*w, 8] (first ``out_dim`` columns valid), rows = [uncond block; cond block], pixels in
+        (y, x) order.  w: the grid's width (default h); every tap has the grid's aspect ratio (s * w // h wide)."""
+        w = h if w is None else w
+        wk = None if w == h else w                                  # (square grids take the square entry points)
+        hw = h * w
         P, sizes, off = [], [], 0
         for (F, s), C in zip(taps, self.tap_channels):
-            assert F.shape == (2 * S * s * s, C)
+            s = s if isinstance(s, int) else s[0]
+            assert F.shape == (2 * S * s * (s * w // h), C)
             P.append(ops.gemm(F, self.W0[:, off:off + C], out_f32=True))
             sizes.append(s)
             off += C
-        if h % 8 == 0 and self.H0 % 128 == 0:
-            Ex = ops.lgp_extra_features(noise, sigma, S, 2 * S, h, 64)
+        if h % 8 == 0 and w % 8 == 0 and self.H0 % 128 == 0:
+            Ex = ops.lgp_extra_features(noise, sigma, S, 2 * S, h, 64, w=wk)
             Z = ops.lgp_layer0_gather(P + [ops.gemm(Ex, self.W0x, out_f32=True)], sizes + [h], None, self.b[0], noise,
-                                      sigma, S, h, self.H0)
+                                      sigma, S, h, self.H0, w=wk)
         else:
-            Z = ops.lgp_layer0_gather(P, sizes, self.W0[:, self.E:], self.b[0], noise, sigma, S, h, self.H0)
+            Z = ops.lgp_layer0_gather(P, sizes, self.W0[:, self.E:], self.b[0], noise, sigma, S, h, self.H0, w=wk)
         zs, stats = [], []
         for l in range(4):
             if self.training:
@@ -93,15 +97,17 @@ class HipLGP:
             stats.append(st)
             Z = ops.gemm(A, self.W[l + 1], bias=self.b[l + 1], relu=(l < 3))
         if keep is not None:
-            keep.update(zs=zs, stats=stats, sizes=sizes, S=S, h=h)
+            keep.update(zs=zs, stats=stats, sizes=sizes, S=S, h=h, w=w)
         return Z
 
     def backward(self, out: torch.Tensor, target: torch.Tensor, keep: dict):
         """MSE(target, out_cond) -> gradients w.r.t. the nine taps (cond rows only), scaled by LOSS_SCALE.
         Returns (tap_grads, loss[S])."""
         S, h, zs, stats, sizes = keep["S"], keep["h"], keep["zs"], keep["stats"], keep["sizes"]
-        hw = h * h
-        dOut, loss = ops.lgp_mse_seed(out, target, S, h, SEED_LD, LOSS_SCALE)
+        w = keep.get("w", h)
+        wk = None if w == h else w
+        hw = h * w
+        dOut, loss = ops.lgp_mse_seed(out, target, S, h, SEED_LD, LOSS_SCALE, w=wk)
         dA = ops.gemm(dOut, self.WT[4])
         dZ = None
         for l in (3, 2, 1, 0):
@@ -111,7 +117,7 @@ class HipLGP:
         dZc = dZ[S * hw:]
         grads, off = [], 0
         for s, C in zip(sizes, self.tap_channels):
-            dP = ops.lgp_layer0_scatter(dZc, S, h, s, self.H0)
+            dP = ops.lgp_layer0_scatter(dZc, S, h, s, self.H0, w=wk)
             grads.append(ops.gemm(dP, self.W0T[off:off + C]))
             off += C
         return grads, loss

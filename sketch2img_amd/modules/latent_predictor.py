@@ -67,7 +67,6 @@ class LatentEdgePredictor(nn.Module):
         from .. import ops
         assert x.is_cuda, "sketch2img_amd has no CPU path: move the inputs to the GPU"
         B, C, h, w = x.shape
-        assert h == w, "square inputs only (SURVEY Q8)"
         in_dim = self.layers[0].in_features
         assert C + 4 + 4 * self.num_layers == in_dim and self.num_layers == 9
         if B % 2 == 1:
@@ -77,7 +76,7 @@ class LatentEdgePredictor(nn.Module):
         assert torch.equal(t[:S], t[S:]), "t must be cat([noise_level] * 2)"
         eng = self._engine([C], x.device)
         feats = x.float().permute(0, 2, 3, 1).reshape(-1, C).half().contiguous()
-        out = eng.forward([(feats, h)], t[:S].float().contiguous(), 1.0, S, h)
+        out = eng.forward([(feats, h)], t[:S].float().contiguous(), 1.0, S, h, w=w)
         self._sync_running_stats()
         o = out[:, : self.layers[12].out_features].reshape(2 * S, h, w, -1).permute(0, 2, 1, 3)   # (b y x) -> (b w h)
         o = o.reshape(2 * S * w * h, -1)
@@ -90,14 +89,15 @@ class FeatureTap:
 
     def __init__(self, name: str):
         self.name = name
-        self._nhwc = None        # (fp16 [rows*s*s, C], rows, s)
+        self._nhwc = None        # (fp16 [rows*s*s, C], rows, s) - on a non-square map s = (height, width)
 
     @property
     def output(self):
         if self._nhwc is None:
             raise AttributeError("output")          # the reference deletes it after use (pipeline.py:149)
         t, rows, s = self._nhwc
-        return t.float().reshape(rows, s, s, -1).permute(0, 3, 1, 2).contiguous()
+        sh, sw = (s, s) if isinstance(s, int) else s
+        return t.float().reshape(rows, sh, sw, -1).permute(0, 3, 1, 2).contiguous()
 
     @output.deleter
     def output(self):

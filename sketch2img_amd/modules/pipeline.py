@@ -36,6 +36,19 @@ from .latent_predictor import LatentEdgePredictor, hook_unet
 logger = logging.getLogger(__name__)      # (the reference: diffusers.utils.logging.get_logger(__name__), modules/pipeline.py:11)
 
 
+def check_image_size(height: int, width: int, multiple: int = 64) -> None:
+    """The image sizes __call__ samples.  A side that is not a multiple of 8 px is a ValueError (check_inputs, as in
+    diffusers).  Square images keep that rule alone.  Non-square ones need both sides a multiple of `multiple` px, from 64
+    to 1024: the VAE factor times HipUNet.size_multiple() - 8 * 8 = 64 for SD's four levels - so every down level halves
+    the latent exactly and every nearest-2x upsample lands on its skip's size (other sizes need diffusers' upsample_size
+    branch and stride-2 convolutions of odd maps)."""
+    if height % 8 != 0 or width % 8 != 0:
+        raise ValueError(f"`height` and `width` have to be divisible by 8 but are {height} and {width}.")
+    if height != width and not all(v % multiple == 0 and 64 <= v <= 1024 for v in (height, width)):
+        raise NotImplementedError(f"non-square images need height and width multiples of {multiple} px from 64 to 1024, "
+                                  f"got {height} x {width}")
+
+
 class UNetFacade:
     """Stands where ``pipe.unet`` is: the attributes app.py / the reference pipeline touch, plus the engine."""
 
@@ -82,13 +95,12 @@ class UNetFacade:
         from .. import ops
         from ..unet import CIN_PAD
         rows, _, h, w = sample.shape
-        assert h == w
         net = self.hip
         if net.ctx is None or net.ctx.get("src") is not encoder_hidden_states:
             net.prepare_context(encoder_hidden_states)
             net.ctx["src"] = encoder_hidden_states
         x32 = ops.nchw_to_nhwc(sample.to(self._device, torch.float32).contiguous(), CIN_PAD)
-        eps, taps = net.forward(x32, int(timestep), rows, h)
+        eps, taps = net.forward(x32, int(timestep), rows, h, W=w)
         if self._feature_taps is not None:
             for tp, (t, s) in zip(self._feature_taps, taps):
                 tp._nhwc = (t, rows, s)
@@ -335,8 +347,7 @@ class AntiGradientPipeline:
         height = height or self.unet.config.sample_size * self.vae_scale_factor
         width = width or self.unet.config.sample_size * self.vae_scale_factor
         self.check_inputs(prompt, height, width, callback_steps)
-        if height != width:
-            raise RuntimeError("sketch guidance resizes with size=latents.shape[2] only: square images (SURVEY Q8)")
+        check_image_size(height, width, self.vae_scale_factor * 2 ** (len(self.unet.cfg.block_out_channels) - 1))
         if eta != 0.0:
             raise NotImplementedError("only eta = 0 (deterministic sampling) is implemented")
         batch_size = 1 if isinstance(prompt, str) else len(prompt)

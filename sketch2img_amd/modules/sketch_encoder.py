@@ -20,14 +20,14 @@ class SketchEncoder(UNetFacade):
         from .. import ops
         from ..unet import CIN_PAD
         rows, _, h, w = sample.shape
-        assert h == w
         net = self.hip
         if net.ctx is None or net.ctx.get("src") is not encoder_hidden_states:
             net.prepare_context(encoder_hidden_states)
             net.ctx["src"] = encoder_hidden_states
         x32 = ops.nchw_to_nhwc(sample.to(self._device, torch.float32).contiguous(), CIN_PAD)
-        blocks = net.forward(x32, int(timestep), rows, h, down_only=True)
-        res = [tuple(t.reshape(rows, s, s, -1).permute(0, 3, 1, 2) for t, s in blk) for blk in blocks]
+        blocks = net.forward(x32, int(timestep), rows, h, down_only=True, W=w)
+        hw = lambda s: (s, s) if isinstance(s, int) else s         # (a non-square map's residual samples carry (sh, sw))
+        res = [tuple(t.reshape(rows, *hw(s), -1).permute(0, 3, 1, 2) for t, s in blk) for blk in blocks]
         return SimpleNamespace(sample=res)
 
     forward = __call__

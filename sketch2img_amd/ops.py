@@ -835,28 +835,37 @@ def attn_bwd_dkv(Q, K, V, dO, lse, delta, batch, heads, Nq, Nkv, dh, scale, dK=N
 
 # ---- LGP --------------------------------------------------------------------------------------------
 def lgp_layer0_gather(P: Sequence[torch.Tensor], sizes: Sequence[int], Wextra, bias0, noise, sigma: float,
-                      samples: int, h: int, H0: int, out=None, rows: Optional[int] = None):
-    """rows defaults to 2*samples ([uncond ; cond] blocks of the sampler); the trainer passes rows = samples."""
+                      samples: int, h: int, H0: int, out=None, rows: Optional[int] = None, w: Optional[int] = None):
+    """rows defaults to 2*samples ([uncond ; cond] blocks of the sampler); the trainer passes rows = samples.
+    w: the grid's width when it is not square (skg_lgp_layer0_gather_hw; sizes are the taps' heights, a tap of height s is
+    s * w // h wide)."""
     rows = 2 * samples if rows is None else rows
+    wd = h if w is None else w
     arr = (SkgTap * len(P))()
     for i, (t, s) in enumerate(zip(P, sizes)):
-        assert t.dtype == torch.float32 and t.is_contiguous() and t.shape == (rows * s * s, H0)
+        assert t.dtype == torch.float32 and t.is_contiguous() and t.shape == (rows * s * (s * wd // h), H0)
         arr[i].P, arr[i].s = t.data_ptr(), s
     if out is None:
-        out = torch.empty(rows * h * h, H0, device=noise.device, dtype=torch.float16)
-    check(lib.skg_lgp_layer0_gather(ctypes.addressof(arr), len(P), _p(Wextra), _ld(Wextra) if Wextra is not None else 0, _p(bias0),
-                                    _p(noise), sigma, samples, _p(out), rows, h, H0, _stream()),
-          "skg_lgp_layer0_gather")
+        out = torch.empty(rows * h * wd, H0, device=noise.device, dtype=torch.float16)
+    wx = (_p(Wextra), _ld(Wextra) if Wextra is not None else 0, _p(bias0), _p(noise), sigma, samples, _p(out), rows, h)
+    if w is None:
+        check(lib.skg_lgp_layer0_gather(ctypes.addressof(arr), len(P), *wx, H0, _stream()), "skg_lgp_layer0_gather")
+    else:
+        check(lib.skg_lgp_layer0_gather_hw(ctypes.addressof(arr), len(P), *wx, w, H0, _stream()), "skg_lgp_layer0_gather_hw")
     return out
 
 
-def lgp_layer0_scatter(dZ, rows, h, s, H0):
+def lgp_layer0_scatter(dZ, rows, h, s, H0, w: Optional[int] = None):
+    """-> dP [rows * s * sw, H0] of the tap of height s (sw = s * w // h, w defaults to h)."""
     _f16(dZ)
     if s == h and dZ.stride(0) == H0:          # the adjoint of an identity resize: no copy
         return dZ
-    out = torch.empty(rows * s * s, H0, device=dZ.device, dtype=torch.float16)
-    check(lib.skg_lgp_layer0_scatter(_p(dZ), _ld(dZ), _p(out), rows, h, s, H0, _stream()),
-          "skg_lgp_layer0_scatter")
+    wd = h if w is None else w
+    out = torch.empty(rows * s * (s * wd // h), H0, device=dZ.device, dtype=torch.float16)
+    if w is None:
+        check(lib.skg_lgp_layer0_scatter(_p(dZ), _ld(dZ), _p(out), rows, h, s, H0, _stream()), "skg_lgp_layer0_scatter")
+    else:
+        check(lib.skg_lgp_layer0_scatter_hw(_p(dZ), _ld(dZ), _p(out), rows, h, w, s, H0, _stream()), "skg_lgp_layer0_scatter_hw")
     return out
 
 
@@ -904,12 +913,16 @@ def bn_relu_bwd(X, dY, samples, segs, seg_rows, stats, gamma, train: bool, out=N
     return out
 
 
-def lgp_mse_seed(out16, target, samples, h, ldd, loss_scale):
+def lgp_mse_seed(out16, target, samples, h, ldd, loss_scale, w: Optional[int] = None):
     _f16(out16)
-    dOut = torch.empty(2 * samples * h * h, ldd, device=out16.device, dtype=torch.float16)
+    dOut = torch.empty(2 * samples * h * (h if w is None else w), ldd, device=out16.device, dtype=torch.float16)
     loss = torch.empty(samples, device=out16.device, dtype=torch.float32)
-    check(lib.skg_lgp_mse_seed(_p(out16), _ld(out16), _p(target), _p(dOut), ldd, _p(loss), samples, h,
-                               loss_scale, _stream()), "skg_lgp_mse_seed")
+    if w is None:
+        check(lib.skg_lgp_mse_seed(_p(out16), _ld(out16), _p(target), _p(dOut), ldd, _p(loss), samples, h,
+                                   loss_scale, _stream()), "skg_lgp_mse_seed")
+    else:
+        check(lib.skg_lgp_mse_seed_hw(_p(out16), _ld(out16), _p(target), _p(dOut), ldd, _p(loss), samples, h, w,
+                                      loss_scale, _stream()), "skg_lgp_mse_seed_hw")
     return dOut, loss
 
 
@@ -934,10 +947,14 @@ def bn_param_grads(X, dY, stats, scale: float = 1.0):
     return dg, db
 
 
-def lgp_extra_features(noise, sigma: float, samples: int, rows: int, h: int, ld: int = 64):
-    out = torch.empty(rows * h * h, ld, device=noise.device, dtype=torch.float16)
-    check(lib.skg_lgp_extra_features(_p(noise), sigma, samples, rows, h, _p(out), ld, _stream()),
-          "skg_lgp_extra_features")
+def lgp_extra_features(noise, sigma: float, samples: int, rows: int, h: int, ld: int = 64, w: Optional[int] = None):
+    out = torch.empty(rows * h * (h if w is None else w), ld, device=noise.device, dtype=torch.float16)
+    if w is None:
+        check(lib.skg_lgp_extra_features(_p(noise), sigma, samples, rows, h, _p(out), ld, _stream()),
+              "skg_lgp_extra_features")
+    else:
+        check(lib.skg_lgp_extra_features_hw(_p(noise), sigma, samples, rows, h, w, _p(out), ld, _stream()),
+              "skg_lgp_extra_features_hw")
     return out
 
 

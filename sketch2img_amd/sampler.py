@@ -137,9 +137,9 @@ class HipSampler:
     @torch.no_grad()
     def step(self, x: torch.Tensor, noise: torch.Tensor, target: Optional[torch.Tensor], tab,
              i: int, guidance_scale: float, beta: float, want_eps: bool = False):
-        """One iteration of the loop for S samples.  x fp32 [S,4,h,h] on the device -> x_{t-1}."""
-        S, _, h, _ = x.shape
-        hw = h * h
+        """One iteration of the loop for S samples.  x fp32 [S,4,h,w] on the device -> x_{t-1}."""
+        S, _, h, w = x.shape
+        hw = h * w
         T = len(tab.timesteps)
         t = int(tab.timesteps[i])
         guided = guided_step(i, T) and target is not None and self.lgp is not None
@@ -151,7 +151,7 @@ class HipSampler:
 
         def guidance_branch(taps):
             keep = {}
-            out = self.lgp.forward(taps, noise, tab.sigma(t), S, h, keep)
+            out = self.lgp.forward(taps, noise, tab.sigma(t), S, h, keep, w=w)
             tap_grads, loss = self.lgp.backward(out, target, keep)
             return self.unet.backward(stash, tap_grads), loss
 
@@ -172,7 +172,7 @@ class HipSampler:
                 branch["done"].record(self._side)
 
         eps, taps = self.unet.forward(x32, t, 2 * S, h, stash, want_taps=guided, shared_input=self.share_cfg_prefix,
-                                      on_taps=on_taps if fork else None)
+                                      on_taps=on_taps if fork else None, W=w)
         fork = fork and "done" in branch          # (a forward that never reached the hook runs the branch in line)
         eu, ec, lo_off = ops.eps_halves(eps, S, hw)      # (accuracy mode: eps is a (hi, lo) pair, combined in fp32 by the step kernel)
         if isinstance(tab, DPMTables):
@@ -206,6 +206,8 @@ class HipSampler:
         tab = tables or DDIMTables.make(num_inference_steps)
         x = latents0.to(dev, torch.float32).contiguous()
         noise = x.clone()                                     # modules/pipeline.py:75
+        if target is not None and tuple(target.shape[-2:]) != tuple(x.shape[-2:]):
+            raise ValueError(f"target spatial shape {tuple(target.shape[-2:])} differs from the latents' {tuple(x.shape[-2:])}")
         tgt = None if target is None else target.to(dev, torch.float32).expand_as(x).contiguous()
         self.unet.prepare_timesteps(tab.timesteps.tolist())
         self.last_aux = []

@@ -59,6 +59,22 @@ COUT_PAD = 8      # conv_out / conv_in-dgrad output channels padded to the 8-cha
 CTX_PAD = 8       # text tokens padded to a multiple of 8 (77 -> 80)
 
 
+# spatial sizes inside the UNet are (height, width) pairs; every level keeps the latent's aspect ratio (both sides are
+# multiples of 2^(levels - 1), so each stride-2 level halves both exactly and each nearest-2x upsample lands on the skip's size)
+def _half(sz: Tuple[int, int]) -> Tuple[int, int]:
+    return (sz[0] // 2, sz[1] // 2)
+
+
+def _dbl(sz: Tuple[int, int]) -> Tuple[int, int]:
+    return (2 * sz[0], 2 * sz[1])
+
+
+def _side(sz: Tuple[int, int]):
+    """What a tap / residual sample carries as its size: the side s of a square map (the form of square evaluations),
+    else (height, width)."""
+    return sz[0] if sz[0] == sz[1] else sz
+
+
 def _h(t: torch.Tensor, dev) -> torch.Tensor:
     return t.detach().to(device=dev, dtype=torch.float16).contiguous()
 
@@ -601,83 +617,83 @@ class HipUNet:
         a 10-40 MB tensor - disappears.  Smaller maps keep the one-launch GroupNorm that holds a slice in registers."""
         return _GN_FROM_PRODUCER and HW >= 1024 and ops.gn_fusable(rows * HW, C, HW, self.cfg.norm_groups)
 
-    def _wino_ok(self, key: str, rows: int, H: int) -> bool:
-        return key in self.W and rows * H * H // 4 >= _WINO_MIN_TILES and not (H & 1)
+    def _wino_ok(self, key: str, rows: int, sz: Tuple[int, int]) -> bool:
+        return key in self.W and rows * sz[0] * sz[1] // 4 >= _WINO_MIN_TILES and not (sz[0] & 1) and not (sz[1] & 1)
 
-    def _conv_wino(self, key: str, x, rows: int, H: int, **kw):
+    def _conv_wino(self, key: str, x, rows: int, sz: Tuple[int, int], **kw):
         """The 3x3 convolution `key` (a weight name + ':wino' / ':winoT') by Winograd F(2x2, 3x3) when the pack exists and the launch is
         large enough; None when the path does not take it (the caller runs the implicit GEMM)."""
-        if not self._wino_ok(key, rows, H):
+        if not self._wino_ok(key, rows, sz):
             return None
         try:
-            return ops.conv3x3_wino(x, self.W[key], rows, H, H, **kw)
+            return ops.conv3x3_wino(x, self.W[key], rows, *sz, **kw)
         except ops.SkgError as e:      # declined (no room for the slabs in the stream's workspace)
             if e.rc != -2:
                 raise
             return None
 
-    def _gn_conv_wino(self, nkey: str, wkey: str, x, rows: int, H: int, eps: float, **kw):
+    def _gn_conv_wino(self, nkey: str, wkey: str, x, rows: int, sz: Tuple[int, int], eps: float, **kw):
         """GroupNorm + SiLU `nkey` and the Winograd convolution `wkey` behind it with the norm writing the convolution's input transform
         (ops.groupnorm_wino: no normalised tensor in memory).  -> (conv output, statistics), or None when either step declines (nothing
         was consumed: the caller runs groupnorm and the convolution as before)."""
-        if not _WINO_GN or not self._wino_ok(wkey, rows, H):
+        if not _WINO_GN or not self._wino_ok(wkey, rows, sz):
             return None
         W = self.W
         try:
-            V, st = ops.groupnorm_wino(x, rows, H, H, self.cfg.norm_groups, eps, W[nkey + ".weight"], W[nkey + ".bias"], True)
-            return ops.conv3x3_wino(None, W[wkey], rows, H, H, V=V, **kw), st
+            V, st = ops.groupnorm_wino(x, rows, *sz, self.cfg.norm_groups, eps, W[nkey + ".weight"], W[nkey + ".bias"], True)
+            return ops.conv3x3_wino(None, W[wkey], rows, *sz, V=V, **kw), st
         except ops.SkgError as e:
             if e.rc != -2:
                 raise
             return None
 
-    def _res_fwd(self, p, x, rows, H, tb, stash: Optional[Stash], out=None, xpart=None, want_part=False, half=False):
+    def _res_fwd(self, p, x, rows, sz, tb, stash: Optional[Stash], out=None, xpart=None, want_part=False, half=False):
         """xpart: GroupNorm partial sums of x from its producer (or None).  Returns (out, partial sums of out or None):
         they are produced when want_part is set and the level takes its statistics from the producers.
         half: `rows` are the COND rows only (the shared CFG prefix, see forward): the stash says so."""
         cfg, W = self.cfg, self.W
-        G, HW = cfg.norm_groups, H * H
+        G, HW = cfg.norm_groups, sz[0] * sz[1]
         Cout = W[p + ".conv1.weight"].shape[0]
         fuse = self._gn_from_producer(rows, HW, Cout)
         # small maps: conv1 / conv2 by Winograd F(2x2, 3x3), the GroupNorm in front writing the input transform where its slice fits a workgroup
         h1 = st1 = None
         if not fuse and xpart is None:
-            got = self._gn_conv_wino(p + ".norm1", p + ".conv1.weight:wino", x, rows, H, 1e-5, bias=tb[p])
+            got = self._gn_conv_wino(p + ".norm1", p + ".conv1.weight:wino", x, rows, sz, 1e-5, bias=tb[p])
             if got is not None:
                 h1, st1 = got
         if h1 is None:
             n1, st1 = ops.groupnorm(x, rows, HW, G, 1e-5, W[p + ".norm1.weight"], W[p + ".norm1.bias"], True, partial=xpart)
-            h1 = None if fuse else self._conv_wino(p + ".conv1.weight:wino", n1, rows, H, bias=tb[p])
+            h1 = None if fuse else self._conv_wino(p + ".conv1.weight:wino", n1, rows, sz, bias=tb[p])
         if h1 is not None:
             part1 = None
         elif fuse:
-            h1, part1 = ops.conv3x3(n1, W[p + ".conv1.weight"], rows, H, H, bias=tb[p], gn_groups=G)
+            h1, part1 = ops.conv3x3(n1, W[p + ".conv1.weight"], rows, *sz, bias=tb[p], gn_groups=G)
         else:
-            h1, part1 = ops.conv3x3(n1, W[p + ".conv1.weight"], rows, H, H, bias=tb[p]), None
+            h1, part1 = ops.conv3x3(n1, W[p + ".conv1.weight"], rows, *sz, bias=tb[p]), None
         opart = None
         done = False
         has_sc = (p + ".conv_shortcut.weight") in W
-        wino2 = (self._wino_ok(p + ".conv2.weight:wino", rows, H) and not (want_part and fuse) and (not has_sc or _WINO >= 2))
+        wino2 = (self._wino_ok(p + ".conv2.weight:wino", rows, sz) and not (want_part and fuse) and (not has_sc or _WINO >= 2))
         n2 = st2 = None
         if wino2:
             # Winograd conv2 with the block input - or the shortcut GEMM's output - as its residual
             sc = ops.gemm(x, W[p + ".conv_shortcut.weight"], bias=W[p + ".conv_shortcut.bias"]) if has_sc else x
-            got = self._gn_conv_wino(p + ".norm2", p + ".conv2.weight:wino", h1, rows, H, 1e-5, out=out, bias=W[p + ".conv2.bias"], residual=sc)
+            got = self._gn_conv_wino(p + ".norm2", p + ".conv2.weight:wino", h1, rows, sz, 1e-5, out=out, bias=W[p + ".conv2.bias"], residual=sc)
             if got is not None:
                 (out, st2), done = got, True
         if not done:
             n2, st2 = ops.groupnorm(h1, rows, HW, G, 1e-5, W[p + ".norm2.weight"], W[p + ".norm2.bias"], True, partial=part1)
         if wino2 and not done:
-            o = self._conv_wino(p + ".conv2.weight:wino", n2, rows, H, out=out, bias=W[p + ".conv2.bias"], residual=sc)
+            o = self._conv_wino(p + ".conv2.weight:wino", n2, rows, sz, out=out, bias=W[p + ".conv2.bias"], residual=sc)
             if o is not None:
                 out, done = o, True
         if not done and (p + ".conv2.weight:sc") in W:
             # the 1x1 shortcut as K tiles behind conv2's 3x3 walk: one launch, no [M, Cout] round trip of the shortcut output
             try:
                 if want_part and fuse:
-                    out, opart = ops.conv3x3_sc(n2, x, W[p + ".conv2.weight:sc"], rows, H, H, out=out, bias=W[p + ".conv2.bias:sc"], gn_groups=G)
+                    out, opart = ops.conv3x3_sc(n2, x, W[p + ".conv2.weight:sc"], rows, *sz, out=out, bias=W[p + ".conv2.bias:sc"], gn_groups=G)
                 else:
-                    out = ops.conv3x3_sc(n2, x, W[p + ".conv2.weight:sc"], rows, H, H, out=out, bias=W[p + ".conv2.bias:sc"])
+                    out = ops.conv3x3_sc(n2, x, W[p + ".conv2.weight:sc"], rows, *sz, out=out, bias=W[p + ".conv2.bias:sc"])
                 done = True
             except ops.SkgError as e:      # declined (an operand >= 2 GiB): the two launches
                 if e.rc != -2:
@@ -688,22 +704,22 @@ class HipUNet:
             else:
                 sc = x
             if want_part and fuse:
-                out, opart = ops.conv3x3(n2, W[p + ".conv2.weight"], rows, H, H, out=out, bias=W[p + ".conv2.bias"],
+                out, opart = ops.conv3x3(n2, W[p + ".conv2.weight"], rows, *sz, out=out, bias=W[p + ".conv2.bias"],
                                          residual=sc, gn_groups=G)
             else:
-                out = ops.conv3x3(n2, W[p + ".conv2.weight"], rows, H, H, out=out, bias=W[p + ".conv2.bias"], residual=sc)
+                out = ops.conv3x3(n2, W[p + ".conv2.weight"], rows, *sz, out=out, bias=W[p + ".conv2.bias"], residual=sc)
         if stash is not None:
-            stash.res[p] = dict(x=x, st1=st1, h1=h1, st2=st2, H=H, half=half)
+            stash.res[p] = dict(x=x, st1=st1, h1=h1, st2=st2, sz=sz, half=half)
         return out, opart
 
-    def _tr_fwd(self, p, x, rows, H, heads, stash: Optional[Stash], out=None, xpart=None, want_part=False, shared=False,
+    def _tr_fwd(self, p, x, rows, sz, heads, stash: Optional[Stash], out=None, xpart=None, want_part=False, shared=False,
                 x_full=None):
         """shared: x holds the COND rows only (rows // 2 of them) of a CFG-doubled batch whose two halves are identical up
         to here (see forward): everything in front of the first text-dependent operation - GroupNorm, proj_in, the whole
         self-attention, LayerNorm 2, to_q - runs once; p1 and q2 are written into the cond half of full-size buffers and
         copied to the uncond half (x_full: the same for x, filled by the caller)."""
         cfg, W = self.cfg, self.W
-        HW = H * H
+        HW = sz[0] * sz[1]
         C = x.shape[1]
         dh = C // heads
         scale = dh ** -0.5
@@ -844,7 +860,7 @@ class HipUNet:
             if r1 != rows and "x" not in half:      # the front diverged before p1 (an injector with differing halves): x is full size
                 ent["x"] = x
             half = tuple(k for k in half if k not in xk_half) + xk_half      # (the stashing cross-attention launch: cond rows only)
-            stash.tr[p] = dict(ent, o2=o2, lse2=lse2, p2=p2, st3=st3, f=f, H=H, heads=heads, half=half + st3h)
+            stash.tr[p] = dict(ent, o2=o2, lse2=lse2, p2=p2, st3=st3, f=f, sz=sz, heads=heads, half=half + st3h)
         return out, opart
 
     @staticmethod
@@ -866,12 +882,22 @@ class HipUNet:
         both.buf = torch.cat([part.buf, part.buf])
         return both
 
+    def size_multiple(self) -> int:
+        """What both latent sides of a non-square map must be multiples of: every stride-2 level halves them exactly and every
+        nearest-2x upsample lands on its skip's size (odd sides need diffusers' upsample_size branch)."""
+        return 2 ** (len(self.cfg.block_out_channels) - 1)
+
+    def _check_rect(self, sz: Tuple[int, int]):
+        f = self.size_multiple()
+        if sz[0] % f or sz[1] % f:
+            raise NotImplementedError(f"non-square latents {sz}: both sides must be multiples of {f}")
+
     # ------------------------------------------------------------------ forward
     def forward(self, x32: torch.Tensor, t: int, rows: int, H: int, stash: Optional[Stash] = None,
                 want_taps: bool = True, want_eps: bool = True, down_only: bool = False, shared_input: bool = False,
-                on_taps: Optional[Callable] = None):
-        """x32: fp16 [rows*H*H, 32] (latent channels zero-padded).  Returns (eps [rows*H*H, 8] or None,
-        taps: list of 9 (tensor [rows*s*s, C], s)).
+                on_taps: Optional[Callable] = None, W: Optional[int] = None):
+        """x32: fp16 [rows*H*W, 32] (latent channels zero-padded; W defaults to H).  Returns (eps [rows*H*W, 8] or None,
+        taps: list of 9 (tensor [rows*s*s, C], s)) - on a non-square map (tensor [rows*sh*sw, C], (sh, sw)).
 
         shared_input: the caller guarantees that the two halves of x32 are IDENTICAL - the CFG-doubled batch of
         modules/pipeline.py:85, `torch.cat([latents] * 2)`.  The two halves of the evaluation then only differ from the
@@ -885,14 +911,17 @@ class HipUNet:
         on_taps(taps): called as soon as the ninth tap exists (after the third up block), before the last up block and
         conv_out are launched - the guidance branch (LGP + backward-to-input) depends on nothing later, so the sampler can put
         it on a second stream while this one finishes eps (sampler.HipSampler.fork_guidance)."""
+        sz = (H, H if W is None else W)
         cfg, W = self.cfg, self.W
         assert self.ctx is not None and self.ctx["rows"] == rows, "call prepare_context first"
+        if sz[0] != sz[1]:
+            self._check_rect(sz)
         self.prepare_timesteps([t])
         if self.residual_fp32:
             assert not down_only, "accuracy mode: the whole UNet (with or without a stash, with or without an injector)"
-            return self._forward_hp(x32, t, rows, H, want_taps, want_eps, stash, on_taps, shared_input)
+            return self._forward_hp(x32, t, rows, H, want_taps, want_eps, stash, on_taps, shared_input, W=sz[1])
         if stash is not None:
-            stash.misc.update(rows=rows, H=H)
+            stash.misc.update(rows=rows, H=H, W=sz[1])
         tb = self.tbias[int(t)]
         boc = cfg.block_out_channels
         nb = len(boc)
@@ -910,7 +939,7 @@ class HipUNet:
             u = n_skips - 1 - len(skips)
             if down_only:
                 return None
-            cats[u] = torch.empty(rows * size * size, ch_h[u] + ch_s, device=self.dev, dtype=torch.float16)
+            cats[u] = torch.empty(rows * size[0] * size[1], ch_h[u] + ch_s, device=self.dev, dtype=torch.float16)
             return cats[u][:, ch_h[u]:]
 
         skips: List[torch.Tensor] = []
@@ -919,18 +948,19 @@ class HipUNet:
         # hp: GroupNorm partial sums of h left behind by the kernel that produced it, whenever the next consumer of h is a
         # GroupNorm of the 64 x 64 / 32 x 32 levels (None otherwise: concatenated inputs, small maps)
         shared = shared_input and rows % 2 == 0 and rows >= 2 and not down_only and nb > 1 and cfg.layers_per_block >= 1
-        cur = H
+        cur = sz
+        HW = sz[0] * sz[1]
         if shared:
-            S1, M1 = rows // 2, (rows // 2) * H * H
-            slot = skip_slot(boc[0], H)                           # the skip of conv_in, all rows
-            if self._gn_from_producer(S1, H * H, boc[0]):
-                h1, hp1 = ops.conv3x3(x32[M1:], W["conv_in.weight"], S1, H, H, out=slot[M1:], bias=W["conv_in.bias"], gn_groups=G)
+            S1, M1 = rows // 2, (rows // 2) * HW
+            slot = skip_slot(boc[0], sz)                          # the skip of conv_in, all rows
+            if self._gn_from_producer(S1, HW, boc[0]):
+                h1, hp1 = ops.conv3x3(x32[M1:], W["conv_in.weight"], S1, *sz, out=slot[M1:], bias=W["conv_in.bias"], gn_groups=G)
             else:
-                h1, hp1 = ops.conv3x3(x32[M1:], W["conv_in.weight"], S1, H, H, out=slot[M1:], bias=W["conv_in.bias"]), None
+                h1, hp1 = ops.conv3x3(x32[M1:], W["conv_in.weight"], S1, *sz, out=slot[M1:], bias=W["conv_in.bias"]), None
             ops.batch_copy(h1, M1, slot, M1, 1, M1)
             skips.append(slot)
             skip_parts.append(self._dup_partial(hp1))
-            x_full = torch.empty(rows * H * H, boc[0], device=self.dev, dtype=torch.float16)
+            x_full = torch.empty(rows * HW, boc[0], device=self.dev, dtype=torch.float16)
             h1, hp1 = self._res_fwd("down_blocks.0.resnets.0", h1, S1, cur, tb, stash, out=x_full[M1:], xpart=hp1,
                                     want_part=True, half=True)
             ops.batch_copy(h1, M1, x_full, M1, 1, M1)
@@ -939,11 +969,11 @@ class HipUNet:
                                  shared=True, x_full=x_full)
             skips.append(h)
             skip_parts.append(hp)
-        elif self._gn_from_producer(rows, H * H, boc[0]):
-            h, hp = ops.conv3x3(x32, W["conv_in.weight"], rows, H, H, out=skip_slot(boc[0], H), bias=W["conv_in.bias"],
+        elif self._gn_from_producer(rows, HW, boc[0]):
+            h, hp = ops.conv3x3(x32, W["conv_in.weight"], rows, *sz, out=skip_slot(boc[0], sz), bias=W["conv_in.bias"],
                                 gn_groups=G)
         else:
-            h, hp = ops.conv3x3(x32, W["conv_in.weight"], rows, H, H, out=skip_slot(boc[0], H), bias=W["conv_in.bias"]), None
+            h, hp = ops.conv3x3(x32, W["conv_in.weight"], rows, *sz, out=skip_slot(boc[0], sz), bias=W["conv_in.bias"]), None
         if not shared:
             skips.append(h)
             skip_parts.append(hp)
@@ -964,34 +994,36 @@ class HipUNet:
                 skip_parts.append(hp)
             if i < nb - 1:
                 p = f"down_blocks.{i}.downsamplers.0.conv"
-                half = cur // 2
-                if self._gn_from_producer(rows, half * half, boc[i]):
-                    h, hp = ops.conv3x3(h, W[p + ".weight"], rows, cur, cur, ops.CONV_S2, out=skip_slot(boc[i], half),
+                half = _half(cur)
+                if self._gn_from_producer(rows, half[0] * half[1], boc[i]):
+                    h, hp = ops.conv3x3(h, W[p + ".weight"], rows, *cur, ops.CONV_S2, out=skip_slot(boc[i], half),
                                         bias=W[p + ".bias"], gn_groups=G)
                 else:
-                    h, hp = ops.conv3x3(h, W[p + ".weight"], rows, cur, cur, ops.CONV_S2, out=skip_slot(boc[i], half),
+                    h, hp = ops.conv3x3(h, W[p + ".weight"], rows, *cur, ops.CONV_S2, out=skip_slot(boc[i], half),
                                         bias=W[p + ".bias"]), None
-                cur //= 2
+                cur = half
                 skips.append(h)
                 skip_parts.append(hp)
             if i < 3:
-                taps_down.append((h, cur))
+                taps_down.append((h, _side(cur)))
         if down_only:
             # modules/sketch_encoder.py:39-98: the forward stops after the down path and returns the per-block
             # tuples of residual samples ((tensor [rows*s*s, C], s), ...) - what SatMixin.set_res_samples consumes
+            # (on a non-square map: (tensor [rows*sh*sw, C], (sh, sw)))
             out, k = [], 1
             for i in range(nb):
                 n = cfg.layers_per_block + (1 if i < nb - 1 else 0)
-                sizes = [H >> i] * cfg.layers_per_block + ([H >> (i + 1)] if i < nb - 1 else [])
+                lv = lambda i: _side((sz[0] >> i, sz[1] >> i))
+                sizes = [lv(i)] * cfg.layers_per_block + ([lv(i + 1)] if i < nb - 1 else [])
                 out.append(tuple((skips[k + j], sizes[j]) for j in range(n)))
                 k += n
             return out
         h, hp = self._res_fwd("mid_block.resnets.0", h, rows, cur, tb, stash, xpart=hp, want_part=True)
-        tap_r0 = (h, cur)
+        tap_r0 = (h, _side(cur))
         h, hp = self._tr_fwd("mid_block.attentions.0", h, rows, cur, cfg.num_heads[-1], stash, xpart=hp, want_part=True)
-        tap_at = (h, cur)
+        tap_at = (h, _side(cur))
         h, _ = self._res_fwd("mid_block.resnets.1", h, rows, cur, tb, stash, out=cats[0][:, :ch_h[0]], xpart=hp)
-        tap_r1 = (h, cur)
+        tap_r1 = (h, _side(cur))
         hp = None
         taps_up = []
         rev_heads = tuple(reversed(cfg.num_heads))
@@ -1025,25 +1057,25 @@ class HipUNet:
                 p = f"up_blocks.{i}.upsamplers.0.conv"
                 u = (i + 1) * lpb1
                 # polyphase: 16 instead of 36 tap-products per low-res pixel (four launches; one grid on the small maps)
-                if (p + ".weight:pp") in W and (UP2_SMALL_MAPS or (rows * cur * cur // 128) * (h.shape[1] // 160) >= 200):
-                    h = ops.conv_up2(h, W[p + ".weight:pp"], rows, cur, cur, out=cats[u][:, :ch_h[u]], bias=W[p + ".bias"], W9=W[p + ".weight"])
+                if (p + ".weight:pp") in W and (UP2_SMALL_MAPS or (rows * cur[0] * cur[1] // 128) * (h.shape[1] // 160) >= 200):
+                    h = ops.conv_up2(h, W[p + ".weight:pp"], rows, *cur, out=cats[u][:, :ch_h[u]], bias=W[p + ".bias"], W9=W[p + ".weight"])
                 else:
-                    h = ops.conv3x3(h, W[p + ".weight"], rows, cur, cur, ops.CONV_UP2, out=cats[u][:, :ch_h[u]],
+                    h = ops.conv3x3(h, W[p + ".weight"], rows, *cur, ops.CONV_UP2, out=cats[u][:, :ch_h[u]],
                                     bias=W[p + ".bias"])
                 hp = None              # (the next concatenation's widths do not line up with 32 groups per half)
-                cur *= 2
+                cur = _dbl(cur)
             if i < 3:
-                taps_up.append((h, cur))
+                taps_up.append((h, _side(cur)))
                 if i == 2 and on_taps is not None:
                     on_taps(taps_down + [tap_at, tap_r0, tap_r1] + taps_up)
         eps = None
         if want_eps:
-            n, _ = ops.groupnorm(h, rows, cur * cur, cfg.norm_groups, 1e-5, W["conv_norm_out.weight"],
+            n, _ = ops.groupnorm(h, rows, cur[0] * cur[1], cfg.norm_groups, 1e-5, W["conv_norm_out.weight"],
                                  W["conv_norm_out.bias"], True, partial=hp)
-            eps = ops.conv3x3(n, W["conv_out.weight"], rows, cur, cur, bias=W["conv_out.bias"])
+            eps = ops.conv3x3(n, W["conv_out.weight"], rows, *cur, bias=W["conv_out.bias"])
         taps = taps_down + [tap_at, tap_r0, tap_r1] + taps_up
         if stash is not None:
-            stash.misc.update(rows=rows, H=H)
+            stash.misc.update(rows=rows, H=H, W=sz[1])
         return eps, (taps if want_taps else None)
 
 
@@ -1064,11 +1096,11 @@ class HipUNet:
         return ops.groupnorm_hilo(x.hi, x.lo, rows, HW, self.cfg.norm_groups, eps, self.W[name + ".weight"],
                                   self.W[name + ".bias"], silu, want_stats=True, partial=partial)
 
-    def _res_fwd_hp(self, p, x, rows, H, tb, out=None, full_of=None, stash=None, xpart=None, want_part=False, half=False):
+    def _res_fwd_hp(self, p, x, rows, sz, tb, out=None, full_of=None, stash=None, xpart=None, want_part=False, half=False):
         """As _res_fwd on pairs.  Returns (out pair, GroupNorm partial sums of out or None)."""
         W = self.W
         G = self.cfg.norm_groups
-        HW, M = H * H, rows * H * H
+        HW, M = sz[0] * sz[1], rows * sz[0] * sz[1]
         Cout = W[p + ".conv1.weight"].shape[0]
         n1, st1 = self._gn_hp(x, rows, HW, 1e-5, p + ".norm1", True, partial=xpart)
         h1 = self._pair(M, Cout)                                    # conv1 output feeds norm2: kept as a pair ("lin_n")
@@ -1076,22 +1108,22 @@ class HipUNet:
         part1 = None
         a1, w1 = (n1.full, W[p + ".conv1.weight:n2"]) if isinstance(n1, ops.Pair) else (n1, W[p + ".conv1.weight"])
         wino = _HP_WINO and not fuse      # (small maps only: the levels whose GroupNorm statistics do not come from the producers)
-        if wino and not isinstance(n1, ops.Pair) and self._conv_wino(p + ".conv1.weight:wino", n1, rows, H, out=h1.hi, out_lo=h1.lo, bias=tb[p]) is not None:
+        if wino and not isinstance(n1, ops.Pair) and self._conv_wino(p + ".conv1.weight:wino", n1, rows, sz, out=h1.hi, out_lo=h1.lo, bias=tb[p]) is not None:
             pass
         elif fuse:
-            _, part1 = ops.conv3x3(a1, w1, rows, H, H, out=h1.hi, out_lo=h1.lo, bias=tb[p], gn_groups=G)
+            _, part1 = ops.conv3x3(a1, w1, rows, *sz, out=h1.hi, out_lo=h1.lo, bias=tb[p], gn_groups=G)
         else:
-            ops.conv3x3(a1, w1, rows, H, H, out=h1.hi, out_lo=h1.lo, bias=tb[p])
+            ops.conv3x3(a1, w1, rows, *sz, out=h1.hi, out_lo=h1.lo, bias=tb[p])
         n2, st2 = self._gn_hp(h1, rows, HW, 1e-5, p + ".norm2", True, partial=part1)
         n2_pair = isinstance(n2, ops.Pair)
         w2n = W[p + ".conv2.weight:n2"] if n2_pair else None
         if n2_pair:
             n2 = n2.full
         if stash is not None:      # the backward differentiates the fp16 (hi) values, as in the default mode
-            stash.res[p] = dict(x=x.hi, st1=st1, h1=h1.hi, st2=st2, H=H, half=half)
+            stash.res[p] = dict(x=x.hi, st1=st1, h1=h1.hi, st2=st2, sz=sz, half=half)
         out = out or self._pair(M, Cout)
         opart = None
-        if wino and not n2_pair and self._wino_ok(p + ".conv2.weight:wino", rows, H):
+        if wino and not n2_pair and self._wino_ok(p + ".conv2.weight:wino", rows, sz):
             # Winograd conv2, pair output; its residual is the block input pair or the K-doubled shortcut GEMM's pair output
             if (p + ".conv_shortcut.weight") in W:
                 sc = self._pair(M, Cout)
@@ -1099,7 +1131,7 @@ class HipUNet:
                 ops.gemm(xf, W[p + ".conv_shortcut.weight:2"], out=sc.hi, out_lo=sc.lo, bias=W[p + ".conv_shortcut.bias"])
             else:
                 sc = x
-            if self._conv_wino(p + ".conv2.weight:wino", n2, rows, H, out=out.hi, out_lo=out.lo, bias=W[p + ".conv2.bias"],
+            if self._conv_wino(p + ".conv2.weight:wino", n2, rows, sz, out=out.hi, out_lo=out.lo, bias=W[p + ".conv2.bias"],
                                residual=sc.hi, residual_lo=sc.lo) is not None:
                 return out, None
         if (p + ".conv2.weight:sc2") in W:
@@ -1108,10 +1140,10 @@ class HipUNet:
             wsc2 = w2n if n2_pair else W[p + ".conv2.weight:sc2"]
             try:
                 if want_part and fuse:
-                    _, opart = ops.conv3x3_sc(n2, xf, wsc2, rows, H, H, out=out.hi, out_lo=out.lo,
+                    _, opart = ops.conv3x3_sc(n2, xf, wsc2, rows, *sz, out=out.hi, out_lo=out.lo,
                                               bias=W[p + ".conv2.bias:sc"], gn_groups=G)
                 else:
-                    ops.conv3x3_sc(n2, xf, wsc2, rows, H, H, out=out.hi, out_lo=out.lo, bias=W[p + ".conv2.bias:sc"])
+                    ops.conv3x3_sc(n2, xf, wsc2, rows, *sz, out=out.hi, out_lo=out.lo, bias=W[p + ".conv2.bias:sc"])
                 return out, opart
             except ops.SkgError as e:
                 if e.rc != -2:
@@ -1128,17 +1160,17 @@ class HipUNet:
         if not w2.is_contiguous():              # (a column slice of the folded pack: the kernel wants the 9-tap pack contiguous)
             w2 = w2.contiguous()
         if want_part and fuse:
-            _, opart = ops.conv3x3(n2, w2, rows, H, H, out=out.hi, out_lo=out.lo, bias=W[p + ".conv2.bias"],
+            _, opart = ops.conv3x3(n2, w2, rows, *sz, out=out.hi, out_lo=out.lo, bias=W[p + ".conv2.bias"],
                                    residual=sc.hi, residual_lo=sc.lo, gn_groups=G)
         else:
-            ops.conv3x3(n2, w2, rows, H, H, out=out.hi, out_lo=out.lo, bias=W[p + ".conv2.bias"],
+            ops.conv3x3(n2, w2, rows, *sz, out=out.hi, out_lo=out.lo, bias=W[p + ".conv2.bias"],
                         residual=sc.hi, residual_lo=sc.lo)
         return out, opart
 
-    def _tr_fwd_hp(self, p, x, rows, H, heads, out=None, stash=None, xpart=None, want_part=False, shared=False, x_full=None):
+    def _tr_fwd_hp(self, p, x, rows, sz, heads, out=None, stash=None, xpart=None, want_part=False, shared=False, x_full=None):
         """As _tr_fwd on pairs (shared / x_full: the shared CFG front, see _tr_fwd: x holds the cond rows only)."""
         W = self.W
-        HW, M = H * H, rows * H * H
+        HW, M = sz[0] * sz[1], rows * sz[0] * sz[1]
         C = x.hi.shape[1]
         dh = C // heads
         scale = dh ** -0.5
@@ -1222,7 +1254,7 @@ class HipUNet:
                            st2=st2, q2=q2_c if own else q2)
                 half = self._stash_half(ent, r1, rows, HW)
                 half = tuple(k for k in half if k not in xk_half) + xk_half
-                stash.tr[p] = dict(ent, o2=o2, lse2=lse2, p2=p2.hi, st3=st3, f=f, H=H, heads=heads, half=half)
+                stash.tr[p] = dict(ent, o2=o2, lse2=lse2, p2=p2.hi, st3=st3, f=f, sz=sz, heads=heads, half=half)
             return out, opart
         if ffb:
             # C = 320: norm3 -> FF1 -> gate -> FF2 + residual in ONE row-local launch on the pair (guided steps: the same launch
@@ -1256,7 +1288,7 @@ class HipUNet:
                        st2=st2, q2=q2_c if own else q2)
             half = self._stash_half(ent, r1, rows, HW)
             half = tuple(k for k in half if k not in xk_half) + xk_half
-            stash.tr[p] = dict(ent, o2=o2, lse2=lse2, p2=p2.hi, st3=st3, f=f, H=H, heads=heads, half=half)
+            stash.tr[p] = dict(ent, o2=o2, lse2=lse2, p2=p2.hi, st3=st3, f=f, sz=sz, heads=heads, half=half)
         if not ffb:
             p3 = self._pair(M, C)
             ops.gemm(gg, W[t + ".ff.net.2.weight"], out=p3.hi, out_lo=p3.lo, bias=W[t + ".ff.net.2.bias"],
@@ -1271,7 +1303,7 @@ class HipUNet:
                      residual=x.hi, residual_lo=x.lo)
         return out, opart
 
-    def _forward_hp(self, x32, t, rows, H, want_taps, want_eps, stash=None, on_taps=None, shared_input=False):
+    def _forward_hp(self, x32, t, rows, H, want_taps, want_eps, stash=None, on_taps=None, shared_input=False, W=None):
         """The forward of forward() with the residual stream as (hi, lo) pairs; the same graph, the same kernels for every
         contraction, pair-aware epilogues / norms (skg_*_hilo), the same GroupNorm statistics from the producers' epilogues and
         the same shared CFG front.  Concatenations [h | skip] are pair buffers [h_hi | skip_hi | h_lo | skip_lo], filled in
@@ -1279,9 +1311,10 @@ class HipUNet:
         on plain fp16 tensors (their pairs buy ~4 % of what the mode's pairs buy, tools/eps_decompose_stream.py): the stride-2
         convolution that enters the zone reads the pair and writes fp16, the upsampler that leaves it reads fp16 and writes a pair;
         skips produced inside the zone are consumed inside it (the U-Net's skips connect equal resolutions)."""
+        sz = (H, H if W is None else W)
         cfg, W = self.cfg, self.W
         if stash is not None:
-            stash.misc.update(rows=rows, H=H)
+            stash.misc.update(rows=rows, H=H, W=sz[1])
         tb = self.tbias[int(t)]
         boc = cfg.block_out_channels
         nb = len(boc)
@@ -1305,9 +1338,9 @@ class HipUNet:
             n_made[0] += 1
             ct = ch_h[u] + ch_s
             if plain_up(u // lpb1):
-                cats[u] = torch.empty(rows * size * size, ct, device=self.dev, dtype=torch.float16)
+                cats[u] = torch.empty(rows * size[0] * size[1], ct, device=self.dev, dtype=torch.float16)
                 return cats[u][:, ch_h[u]:]
-            cats[u] = torch.empty(rows * size * size, 2 * ct, device=self.dev, dtype=torch.float16)
+            cats[u] = torch.empty(rows * size[0] * size[1], 2 * ct, device=self.dev, dtype=torch.float16)
             return P(cats[u][:, ch_h[u]:ct], cats[u][:, ct + ch_h[u]:], None)
 
         def full_of(pv, C):
@@ -1324,33 +1357,33 @@ class HipUNet:
 
         def conv_pair(x, wkey, bkey, size, mode, o, r=rows, want=False):
             """conv with a pair output (+ the GroupNorm sums of its hi part where the level takes them from the producers)"""
-            osz = size // 2 if mode == ops.CONV_S2 else size
-            if want and self._gn_from_producer(r, osz * osz, o.hi.shape[1]):
-                return ops.conv3x3(x, W[wkey], r, size, size, mode, out=o.hi, out_lo=o.lo, bias=W[bkey], gn_groups=G)[1]
-            ops.conv3x3(x, W[wkey], r, size, size, mode, out=o.hi, out_lo=o.lo, bias=W[bkey])
+            osz = _half(size) if mode == ops.CONV_S2 else size
+            if want and self._gn_from_producer(r, osz[0] * osz[1], o.hi.shape[1]):
+                return ops.conv3x3(x, W[wkey], r, *size, mode, out=o.hi, out_lo=o.lo, bias=W[bkey], gn_groups=G)[1]
+            ops.conv3x3(x, W[wkey], r, *size, mode, out=o.hi, out_lo=o.lo, bias=W[bkey])
             return None
 
         def conv_plain(x, wkey, bkey, size, mode, o):
             """conv with an fp16 output (the plain zone; forward()'s form)"""
-            osz = size // 2 if mode == ops.CONV_S2 else size
-            if self._gn_from_producer(rows, osz * osz, o.shape[1]):
-                return ops.conv3x3(x, W[wkey], rows, size, size, mode, out=o, bias=W[bkey], gn_groups=G)[1]
-            ops.conv3x3(x, W[wkey], rows, size, size, mode, out=o, bias=W[bkey])
+            osz = _half(size) if mode == ops.CONV_S2 else size
+            if self._gn_from_producer(rows, osz[0] * osz[1], o.shape[1]):
+                return ops.conv3x3(x, W[wkey], rows, *size, mode, out=o, bias=W[bkey], gn_groups=G)[1]
+            ops.conv3x3(x, W[wkey], rows, *size, mode, out=o, bias=W[bkey])
             return None
 
         hi_of = lambda v: v.hi if isinstance(v, ops.Pair) else v
         shared = shared_input and rows % 2 == 0 and rows >= 2 and nb > 1 and cfg.layers_per_block >= 1
-        cur = H
+        cur = sz
         taps_down = []
-        h = skip_slot(boc[0], H)
+        h = skip_slot(boc[0], sz)
         if shared:
-            S1, M1 = rows // 2, (rows // 2) * H * H
+            S1, M1 = rows // 2, (rows // 2) * sz[0] * sz[1]
             hc = rows_of(h, M1, 2 * M1)
-            hp1 = conv_pair(x32[M1:], "conv_in.weight", "conv_in.bias", H, ops.CONV_S1, hc, r=S1, want=True)
+            hp1 = conv_pair(x32[M1:], "conv_in.weight", "conv_in.bias", sz, ops.CONV_S1, hc, r=S1, want=True)
             ops.batch_copy(hc.hi, M1, h.hi, M1, 1, M1)
             ops.batch_copy(hc.lo, M1, h.lo, M1, 1, M1)
             skip_parts.append(self._dup_partial(hp1))
-            x_full = self._pair(rows * H * H, boc[0])
+            x_full = self._pair(rows * sz[0] * sz[1], boc[0])
             h1, hp1 = self._res_fwd_hp("down_blocks.0.resnets.0", hc, S1, cur, tb, out=rows_of(x_full, M1, 2 * M1), full_of=full_of,
                                        stash=stash, xpart=hp1, want_part=True, half=True)
             ops.batch_copy(h1.full, M1, x_full.full, M1, 1, M1)
@@ -1358,7 +1391,7 @@ class HipUNet:
                                     stash=stash, xpart=hp1, want_part=0 < cfg.layers_per_block - 1, shared=True, x_full=x_full)
             skip_parts.append(hp)
         else:
-            hp = conv_pair(x32, "conv_in.weight", "conv_in.bias", H, ops.CONV_S1, h, want=True)
+            hp = conv_pair(x32, "conv_in.weight", "conv_in.bias", sz, ops.CONV_S1, h, want=True)
             skip_parts.append(hp)
         for i in range(nb):
             for j in range(cfg.layers_per_block):
@@ -1382,7 +1415,7 @@ class HipUNet:
                 skip_parts.append(hp)
             if i < nb - 1:
                 p = f"down_blocks.{i}.downsamplers.0.conv"
-                o = skip_slot(boc[i], cur // 2)               # (a pair, or fp16 when the consumer - the same level of the up path - is plain)
+                o = skip_slot(boc[i], _half(cur))               # (a pair, or fp16 when the consumer - the same level of the up path - is plain)
                 if plain_down(i):
                     hp = conv_plain(h, p + ".weight", p + ".bias", cur, ops.CONV_S2, o)
                 elif isinstance(o, ops.Pair):
@@ -1390,26 +1423,26 @@ class HipUNet:
                 else:                                         # entering the plain zone: the pair as K-doubled operand, fp16 out
                     hp = conv_plain(full_of(h, boc[i]), p + ".weight:2", p + ".bias", cur, ops.CONV_S2, o)
                 h = o
-                cur //= 2
+                cur = _half(cur)
                 skip_parts.append(hp)
             if i < 3:
-                taps_down.append((hi_of(h), cur))
+                taps_down.append((hi_of(h), _side(cur)))
         if pl > 0:
             h, hp = self._res_fwd("mid_block.resnets.0", h, rows, cur, tb, stash, xpart=hp, want_part=True)
-            tap_r0 = (h, cur)
+            tap_r0 = (h, _side(cur))
             h, hp = self._tr_fwd("mid_block.attentions.0", h, rows, cur, cfg.num_heads[-1], stash, xpart=hp, want_part=True)
-            tap_at = (h, cur)
+            tap_at = (h, _side(cur))
             h, _ = self._res_fwd("mid_block.resnets.1", h, rows, cur, tb, stash, out=cats[0][:, :ch_h[0]], xpart=hp)
-            tap_r1 = (h, cur)
+            tap_r1 = (h, _side(cur))
         else:
             h, hp = self._res_fwd_hp("mid_block.resnets.0", h, rows, cur, tb, full_of=full_of, stash=stash, xpart=hp, want_part=True)
-            tap_r0 = (h.hi, cur)
+            tap_r0 = (h.hi, _side(cur))
             h, hp = self._tr_fwd_hp("mid_block.attentions.0", h, rows, cur, cfg.num_heads[-1], stash=stash, xpart=hp, want_part=True)
-            tap_at = (h.hi, cur)
+            tap_at = (h.hi, _side(cur))
             ct0 = cats[0].shape[1] // 2
             h, _ = self._res_fwd_hp("mid_block.resnets.1", h, rows, cur, tb, out=P(cats[0][:, :ch_h[0]], cats[0][:, ct0:ct0 + ch_h[0]]),
                                     stash=stash, xpart=hp)
-            tap_r1 = (h.hi, cur)
+            tap_r1 = (h.hi, _side(cur))
         hp = None
         taps_up = []
         rev_heads = tuple(reversed(cfg.num_heads))
@@ -1453,34 +1486,34 @@ class HipUNet:
                 u = (i + 1) * lpb1
                 if plain_up(i + 1):    # inside the plain zone: forward()'s form
                     o = cats[u][:, :ch_h[u]]
-                    if (p + ".weight:pp") in W and (UP2_SMALL_MAPS or (rows * cur * cur // 128) * (h.shape[1] // 160) >= 200):
-                        ops.conv_up2(h, W[p + ".weight:pp"], rows, cur, cur, out=o, bias=W[p + ".bias"], W9=W[p + ".weight"])
+                    if (p + ".weight:pp") in W and (UP2_SMALL_MAPS or (rows * cur[0] * cur[1] // 128) * (h.shape[1] // 160) >= 200):
+                        ops.conv_up2(h, W[p + ".weight:pp"], rows, *cur, out=o, bias=W[p + ".bias"], W9=W[p + ".weight"])
                     else:
-                        ops.conv3x3(h, W[p + ".weight"], rows, cur, cur, ops.CONV_UP2, out=o, bias=W[p + ".bias"])
+                        ops.conv3x3(h, W[p + ".weight"], rows, *cur, ops.CONV_UP2, out=o, bias=W[p + ".bias"])
                 else:
                     ctn = cats[u].shape[1] // 2
                     o = P(cats[u][:, :ch_h[u]], cats[u][:, ctn:ctn + ch_h[u]])
                     hin = hi_of(h)                            # (leaving the plain zone: h is fp16 and the hi-only launch is the natural one)
                     if (plain_up(i) or not HP_UP_TRIPLE) and (p + ".weight:pp") in W and (p + ".weight:pp3") not in W:
                         try:
-                            ops.conv_up2_pairout(hin, W[p + ".weight:pp"], rows, cur, cur, o, bias=W[p + ".bias"])
+                            ops.conv_up2_pairout(hin, W[p + ".weight:pp"], rows, *cur, o, bias=W[p + ".bias"])
                         except ops.SkgError as e:      # declined (an operand >= 2 GiB): the 9-tap gather form on the SAME hi-only operand
                             if e.rc != -2:               # (both routes of the mode must see the same operand; pair output either way)
                                 raise
-                            ops.conv3x3(hin, W[p + ".weight"], rows, cur, cur, ops.CONV_UP2, out=o.hi, out_lo=o.lo, bias=W[p + ".bias"])
+                            ops.conv3x3(hin, W[p + ".weight"], rows, *cur, ops.CONV_UP2, out=o.hi, out_lo=o.lo, bias=W[p + ".bias"])
                     elif plain_up(i):
-                        ops.conv3x3(hin, W[p + ".weight"], rows, cur, cur, ops.CONV_UP2, out=o.hi, out_lo=o.lo, bias=W[p + ".bias"])
+                        ops.conv3x3(hin, W[p + ".weight"], rows, *cur, ops.CONV_UP2, out=o.hi, out_lo=o.lo, bias=W[p + ".bias"])
                     elif (p + ".weight:pp3") in W:      # polyphase, K axis [x_hi | x_lo | x_hi] . [W_hi | W_hi | W_lo]: 12 instead of 18 tap-products
-                        ops.conv_up2_hilo(full_of(h, h.hi.shape[1]), W[p + ".weight:pp3"], rows, cur, cur, o, bias=W[p + ".bias"],
+                        ops.conv_up2_hilo(full_of(h, h.hi.shape[1]), W[p + ".weight:pp3"], rows, *cur, o, bias=W[p + ".bias"],
                                           W9x2=lambda p=p: self._w9x2(p + ".weight"))
                     else:
-                        ops.conv3x3(full_of(h, h.hi.shape[1]), W[p + ".weight:2"], rows, cur, cur, ops.CONV_UP2, out=o.hi, out_lo=o.lo,
+                        ops.conv3x3(full_of(h, h.hi.shape[1]), W[p + ".weight:2"], rows, *cur, ops.CONV_UP2, out=o.hi, out_lo=o.lo,
                                     bias=W[p + ".bias"])
                 h = o
                 hp = None
-                cur *= 2
+                cur = _dbl(cur)
             if i < 3:
-                taps_up.append((hi_of(h), cur))
+                taps_up.append((hi_of(h), _side(cur)))
                 if i == 2 and on_taps is not None:
                     on_taps(taps_down + [tap_at, tap_r0, tap_r1] + taps_up)
         eps = None
@@ -1488,33 +1521,33 @@ class HipUNet:
             # conv_norm_out -> SiLU -> conv_out: both the normalised activation (the K-doubled operand [hi | lo] . [W | W]) and eps
             # itself (a (hi, lo) pair in one [M, 2 * 8] buffer, combined in fp32 by the CFG / scheduler kernel) keep fp32 accuracy -
             # their fp16 roundings would reach eps one to one (2.8e-4 relative each)
-            n = self._pair(rows * cur * cur, boc[0])
-            ops.groupnorm_hilo(h.hi, h.lo, rows, cur * cur, G, 1e-5, W["conv_norm_out.weight"], W["conv_norm_out.bias"], True,
+            n = self._pair(rows * cur[0] * cur[1], boc[0])
+            ops.groupnorm_hilo(h.hi, h.lo, rows, cur[0] * cur[1], G, 1e-5, W["conv_norm_out.weight"], W["conv_norm_out.bias"], True,
                                out=n.hi, out_lo=n.lo, partial=hp)
-            eps = self._pair(rows * cur * cur, COUT_PAD)
-            ops.conv3x3(n.full, W["conv_out.weight:2"], rows, cur, cur, out=eps.hi, out_lo=eps.lo, bias=W["conv_out.bias"])
+            eps = self._pair(rows * cur[0] * cur[1], COUT_PAD)
+            ops.conv3x3(n.full, W["conv_out.weight:2"], rows, *cur, out=eps.hi, out_lo=eps.lo, bias=W["conv_out.bias"])
         taps = taps_down + [tap_at, tap_r0, tap_r1] + taps_up
         if stash is not None:
-            stash.misc.update(rows=rows, H=H)
+            stash.misc.update(rows=rows, H=H, W=sz[1])
         return eps, (taps if want_taps else None)
 
     # ------------------------------------------------------------------ modules, backward (cond rows)
     def _res_bwd(self, p, dout, S, st: dict):
         cfg, W = self.cfg, self.W
-        H = st["H"]
-        HW, G = H * H, cfg.norm_groups
+        sz = st["sz"]
+        HW, G = sz[0] * sz[1], cfg.norm_groups
         if st.get("half"):        # the shared CFG prefix was evaluated on the cond rows only
             x, h1, st1, st2 = st["x"], st["h1"], st["st1"], st["st2"]
         else:
             x, h1 = st["x"][S * HW:], st["h1"][S * HW:]
             st1, st2 = st["st1"][S:], st["st2"][S:]
-        dn2 = self._conv_wino(p + ".conv2.weight:winoT", dout, S, H)
+        dn2 = self._conv_wino(p + ".conv2.weight:winoT", dout, S, sz)
         if dn2 is None:
-            dn2 = ops.conv3x3(dout, W[p + ".conv2.weight:T"], S, H, H)
+            dn2 = ops.conv3x3(dout, W[p + ".conv2.weight:T"], S, *sz)
         dh1 = ops.groupnorm_bwd(h1, dn2, S, HW, G, st2, W[p + ".norm2.weight"], W[p + ".norm2.bias"], True)
-        dn1 = self._conv_wino(p + ".conv1.weight:winoT", dh1, S, H)
+        dn1 = self._conv_wino(p + ".conv1.weight:winoT", dh1, S, sz)
         if dn1 is None:
-            dn1 = ops.conv3x3(dh1, W[p + ".conv1.weight:T"], S, H, H)
+            dn1 = ops.conv3x3(dh1, W[p + ".conv1.weight:T"], S, *sz)
         if (p + ".conv_shortcut.weight") in W:
             sc = ops.gemm(dout, W[p + ".conv_shortcut.weight:T"])
         else:
@@ -1524,8 +1557,8 @@ class HipUNet:
 
     def _tr_bwd(self, p, dout, S, st: dict):
         cfg, W = self.cfg, self.W
-        H, heads = st["H"], st["heads"]
-        HW = H * H
+        sz, heads = st["sz"], st["heads"]
+        HW = sz[0] * sz[1]
         M0 = S * HW
         C = dout.shape[1]
         dh = C // heads
@@ -1573,10 +1606,10 @@ class HipUNet:
     # ------------------------------------------------------------------ backward
     def backward(self, stash: Stash, tap_grads: Sequence[Optional[torch.Tensor]]) -> torch.Tensor:
         """tap_grads: 9 fp16 tensors [S*s*s, C] (cond rows) in tap order.  Returns d loss / d x for the
-        cond rows, fp16 [S*H*H, 8] (first 4 channels valid)."""
+        cond rows, fp16 [S*H*W, 8] (first 4 channels valid; H x W: the stashed forward's size)."""
         assert self.need_backward and self.inject is None, "backward with injected attention is not supported"
         cfg, W = self.cfg, self.W
-        rows, H = stash.misc["rows"], stash.misc["H"]
+        rows, sz = stash.misc["rows"], (stash.misc["H"], stash.misc.get("W", stash.misc["H"]))
         S = rows // 2
         nb = len(cfg.block_out_channels)
         lpb = cfg.layers_per_block
@@ -1592,7 +1625,7 @@ class HipUNet:
         n_skips = 1 + sum(lpb + (1 if i < nb - 1 else 0) for i in range(nb))
         gskip: List[Optional[torch.Tensor]] = [None] * n_skips
         # ---- up path, reversed (blocks 2, 1, 0; block 3 does not feed any tap)
-        cur = H                                  # spatial size of up block 2's output (after its upsampler)
+        cur = sz                                 # spatial size of up block 2's output (after its upsampler)
         for _ in range(nb - 1 - 3):              # generic: taps end at up block 2
             pass
         # index of the skip consumed first by up block i: pops from the end
@@ -1603,19 +1636,19 @@ class HipUNet:
                 pop_idx -= 1
                 consumed[(i, j)] = pop_idx
         dh = tap_grads[8]
-        cur = H
+        cur = sz
         plan = up_block_plan(cfg)
         for i in (2, 1, 0):
             if i < nb - 1:
                 # upsampler backward: dgrad at the upsampled size, then 2x2 sum-pool
                 p = f"up_blocks.{i}.upsamplers.0.conv"
                 if UP2_DGRAD and (p + ".weight:ppT") in W:      # polyphase: one 4 x 4 stride-2 convolution, 16 instead of 36 tap-products
-                    dh = ops.conv4x4s2(dh, W[p + ".weight:ppT"], S, cur, cur, W9T=W[p + ".weight:T"])
-                    cur //= 2
+                    dh = ops.conv4x4s2(dh, W[p + ".weight:ppT"], S, *cur, W9T=W[p + ".weight:T"])
+                    cur = _half(cur)
                 else:
-                    du = ops.conv3x3(dh, W[p + ".weight:T"], S, cur, cur)
-                    cur //= 2
-                    dh = ops.sumpool2x2(du, S, cur, cur)
+                    du = ops.conv3x3(dh, W[p + ".weight:T"], S, *cur)
+                    cur = _half(cur)
+                    dh = ops.sumpool2x2(du, S, *cur)
             for j in range(lpb, -1, -1):
                 if i > 0:
                     dh = self._tr_bwd(f"up_blocks.{i}.attentions.{j}", dh, S, stash.tr[f"up_blocks.{i}.attentions.{j}"])
@@ -1641,8 +1674,8 @@ class HipUNet:
                 if i < 3:
                     dh = add(dh, tap_grads[i])
                 p = f"down_blocks.{i}.downsamplers.0.conv"
-                dh = ops.conv3x3(dh, W[p + ".weight:T"], S, cur, cur, ops.CONV_S2T)
-                cur *= 2
+                dh = ops.conv3x3(dh, W[p + ".weight:T"], S, *cur, ops.CONV_S2T)
+                cur = _dbl(cur)
             for j in range(lpb - 1, -1, -1):
                 dh = add(dh, gskip[k]); k -= 1
                 if i < nb - 1:
@@ -1650,4 +1683,4 @@ class HipUNet:
                                       stash.tr[f"down_blocks.{i}.attentions.{j}"])
                 dh = self._res_bwd(f"down_blocks.{i}.resnets.{j}", dh, S, stash.res[f"down_blocks.{i}.resnets.{j}"])
         dh = add(dh, gskip[0])
-        return ops.conv3x3(dh, W["conv_in.weight:T"], S, H, H)
+        return ops.conv3x3(dh, W["conv_in.weight:T"], S, *sz)

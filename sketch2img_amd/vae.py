@@ -61,19 +61,20 @@ class _HipVAEBlocks:
         return out
 
     # ------------------------------------------------------------------------------------------ blocks
-    def _res(self, p, x, rows, H):
-        W, G, HW = self.W, self.cfg.norm_groups, H * H
+    def _res(self, p, x, rows, sz):
+        """sz: the map's (height, width)."""
+        W, G, HW = self.W, self.cfg.norm_groups, sz[0] * sz[1]
         n1, _ = ops.groupnorm(x, rows, HW, G, 1e-6, W[p + ".norm1.weight"], W[p + ".norm1.bias"], True)
-        h1 = ops.conv3x3(n1, W[p + ".conv1.weight"], rows, H, H, bias=W[p + ".conv1.bias"])
+        h1 = ops.conv3x3(n1, W[p + ".conv1.weight"], rows, *sz, bias=W[p + ".conv1.bias"])
         del n1
         n2, _ = ops.groupnorm(h1, rows, HW, G, 1e-6, W[p + ".norm2.weight"], W[p + ".norm2.bias"], True)
         del h1
         if (p + ".conv_shortcut.weight") in W:
             x = ops.gemm(x, W[p + ".conv_shortcut.weight"], bias=W[p + ".conv_shortcut.bias"])
-        return ops.conv3x3(n2, W[p + ".conv2.weight"], rows, H, H, bias=W[p + ".conv2.bias"], residual=x)
+        return ops.conv3x3(n2, W[p + ".conv2.weight"], rows, *sz, bias=W[p + ".conv2.bias"], residual=x)
 
-    def _attn(self, p, x, rows, H):
-        W, G, HW = self.W, self.cfg.norm_groups, H * H
+    def _attn(self, p, x, rows, sz):
+        W, G, HW = self.W, self.cfg.norm_groups, sz[0] * sz[1]
         C = x.shape[1]
         g, _ = ops.groupnorm(x, rows, HW, G, 1e-6, W[p + ".group_norm.weight"], W[p + ".group_norm.bias"], False)
         qkv = ops.gemm(g, W[p + ".qkv.weight"], bias=W[p + ".qkv.bias"])
@@ -132,62 +133,62 @@ class HipVAEDecoder(_HipVAEBlocks):
     # ------------------------------------------------------------------------------------------ decode
     @torch.no_grad()
     def decode_tokens(self, z: torch.Tensor):
-        """z float [S, 4, h, h] (already divided by the scaling factor) -> (fp16 NHWC [S*H*H, COUT_PAD], H)."""
+        """z float [S, 4, h, w] (already divided by the scaling factor) -> (fp16 NHWC [S*H*W, COUT_PAD], (H, W))."""
         cfg, W = self.cfg, self.W
-        S, _, h, _ = z.shape
+        S, _, h, w = z.shape
+        sz = (h, w)
         x = ops.nchw_to_nhwc(z.to(self.dev, torch.float32).contiguous(), CIN_PAD)
         x = ops.gemm(x, W["post_quant_conv.weight"], bias=W["post_quant_conv.bias"])
-        x = ops.conv3x3(x, W["decoder.conv_in.weight"], S, h, h, bias=W["decoder.conv_in.bias"])
-        x = self._res("decoder.mid_block.resnets.0", x, S, h)
-        x = self._attn("decoder.mid_block.attentions.0", x, S, h)
-        x = self._res("decoder.mid_block.resnets.1", x, S, h)
-        H = h
+        x = ops.conv3x3(x, W["decoder.conv_in.weight"], S, *sz, bias=W["decoder.conv_in.bias"])
+        x = self._res("decoder.mid_block.resnets.0", x, S, sz)
+        x = self._attn("decoder.mid_block.attentions.0", x, S, sz)
+        x = self._res("decoder.mid_block.resnets.1", x, S, sz)
         for i, res, up in vae_up_plan(cfg):
             for j in range(len(res)):
-                x = self._res(f"decoder.up_blocks.{i}.resnets.{j}", x, S, H)
+                x = self._res(f"decoder.up_blocks.{i}.resnets.{j}", x, S, sz)
             if up:
                 u = f"decoder.up_blocks.{i}.upsamplers.0.conv"
                 if (u + ".weight:pp") in W:      # polyphase: 16 instead of 36 tap-products per low-res pixel
-                    x = ops.conv_up2(x, W[u + ".weight:pp"], S, H, H, bias=W[u + ".bias"], W9=W.get(u + ".weight"))
+                    x = ops.conv_up2(x, W[u + ".weight:pp"], S, *sz, bias=W[u + ".bias"], W9=W.get(u + ".weight"))
                 else:
-                    x = ops.conv3x3(x, W[u + ".weight"], S, H, H, ops.CONV_UP2, bias=W[u + ".bias"])
-                H *= 2
-        n, _ = ops.groupnorm(x, S, H * H, cfg.norm_groups, 1e-6, W["decoder.conv_norm_out.weight"],
+                    x = ops.conv3x3(x, W[u + ".weight"], S, *sz, ops.CONV_UP2, bias=W[u + ".bias"])
+                sz = (2 * sz[0], 2 * sz[1])
+        n, _ = ops.groupnorm(x, S, sz[0] * sz[1], cfg.norm_groups, 1e-6, W["decoder.conv_norm_out.weight"],
                              W["decoder.conv_norm_out.bias"], True)
         del x
-        return ops.conv3x3(n, W["decoder.conv_out.weight"], S, H, H, bias=W["decoder.conv_out.bias"]), H
+        return ops.conv3x3(n, W["decoder.conv_out.weight"], S, *sz, bias=W["decoder.conv_out.bias"]), sz
 
     @torch.no_grad()
     def decode(self, z: torch.Tensor) -> torch.Tensor:
-        """AutoencoderKL.decode(z).sample: float NCHW [S, 3, 8h, 8h]."""
+        """AutoencoderKL.decode(z).sample: float NCHW [S, 3, 8h, 8w]."""
         outs = []
         for s0 in range(0, z.shape[0], self.chunk):
-            y, H = self.decode_tokens(z[s0:s0 + self.chunk])
-            outs.append(ops.nhwc_to_nchw(y, y.shape[0] // (H * H), self.cfg.out_channels, H, H))
+            y, (H, Wd) = self.decode_tokens(z[s0:s0 + self.chunk])
+            outs.append(ops.nhwc_to_nchw(y, y.shape[0] // (H * Wd), self.cfg.out_channels, H, Wd))
         return torch.cat(outs)
 
     @torch.no_grad()
     def decode_latents(self, latents: torch.Tensor) -> torch.Tensor:
-        """modules/pipeline.py:118: latents [S,4,h,h] -> float NHWC [S, 8h, 8h, 3] in [0, 1] (device tensor)."""
+        """modules/pipeline.py:118: latents [S,4,h,w] -> float NHWC [S, 8h, 8w, 3] in [0, 1] (device tensor)."""
         outs = []
         for s0 in range(0, latents.shape[0], self.chunk):
             z = latents[s0:s0 + self.chunk].to(self.dev, torch.float32) * (1.0 / self.cfg.scaling_factor)
-            y, H = self.decode_tokens(z)
-            n = y.shape[0] // (H * H)
-            outs.append(ops.image_postprocess(y, y.shape[0], self.cfg.out_channels).reshape(n, H, H, -1))
+            y, (H, Wd) = self.decode_tokens(z)
+            n = y.shape[0] // (H * Wd)
+            outs.append(ops.image_postprocess(y, y.shape[0], self.cfg.out_channels).reshape(n, H, Wd, -1))
         return torch.cat(outs)
 
 
     @torch.no_grad()
     def decode_to_u8(self, latents: torch.Tensor) -> torch.Tensor:
-        """decode_latents + numpy_to_pil's quantisation on the device: latents [S,4,h,h] -> uint8 [S, 8h, 8h, 3]
+        """decode_latents + numpy_to_pil's quantisation on the device: latents [S,4,h,w] -> uint8 [S, 8h, 8w, 3]
         (what a rank hands to the final gather: 786 432 B per 512x512 image)."""
         outs = []
         for s0 in range(0, latents.shape[0], self.chunk):
             z = latents[s0:s0 + self.chunk].to(self.dev, torch.float32) * (1.0 / self.cfg.scaling_factor)
-            y, H = self.decode_tokens(z)
-            n = y.shape[0] // (H * H)
-            outs.append(ops.image_to_u8(y, y.shape[0], self.cfg.out_channels).reshape(n, H, H, -1))
+            y, (H, Wd) = self.decode_tokens(z)
+            n = y.shape[0] // (H * Wd)
+            outs.append(ops.image_to_u8(y, y.shape[0], self.cfg.out_channels).reshape(n, H, Wd, -1))
         return torch.cat(outs)
 
 
@@ -225,38 +226,40 @@ class HipVAEEncoder(_HipVAEBlocks):
 
     @torch.no_grad()
     def moments(self, img: torch.Tensor):
-        """img float [S, 3, H, W] -> (fp16 NHWC moments [S*h*h, 2*latent], h) with h = H / 8 (4-level layout)."""
+        """img float [S, 3, H, W] -> (fp16 NHWC moments [S*h*w, 2*latent], (h, w)) with h = H / 8, w = W / 8 (4-level layout)."""
         cfg, W = self.cfg, self.W
         S, _, H, Wd = img.shape
-        if H != Wd or H % 2 ** (len(cfg.block_out_channels) - 1):
-            raise ValueError(f"VAE encoder: square images with a side divisible by 8, got {tuple(img.shape)}")
+        f = 2 ** (len(cfg.block_out_channels) - 1)
+        if H % f or Wd % f:
+            raise ValueError(f"VAE encoder: image sides divisible by {f}, got {tuple(img.shape)}")
+        sz = (H, Wd)
         x = ops.nchw_to_nhwc(img.to(self.dev, torch.float32).contiguous(), CIN_PAD)
-        x = ops.conv3x3(x, W["encoder.conv_in.weight"], S, H, H, bias=W["encoder.conv_in.bias"])
+        x = ops.conv3x3(x, W["encoder.conv_in.weight"], S, *sz, bias=W["encoder.conv_in.bias"])
         nb = len(cfg.block_out_channels)
         for i in range(nb):
             for j in range(cfg.layers_per_block):
-                x = self._res(f"encoder.down_blocks.{i}.resnets.{j}", x, S, H)
+                x = self._res(f"encoder.down_blocks.{i}.resnets.{j}", x, S, sz)
             if i != nb - 1:
                 d = f"encoder.down_blocks.{i}.downsamplers.0.conv"
-                x = ops.conv3x3(x, W[d + ".weight"], S, H, H, ops.CONV_S2A, bias=W[d + ".bias"])
-                H //= 2
-        x = self._res("encoder.mid_block.resnets.0", x, S, H)
-        x = self._attn("encoder.mid_block.attentions.0", x, S, H)
-        x = self._res("encoder.mid_block.resnets.1", x, S, H)
-        n, _ = ops.groupnorm(x, S, H * H, cfg.norm_groups, 1e-6, W["encoder.conv_norm_out.weight"],
+                x = ops.conv3x3(x, W[d + ".weight"], S, *sz, ops.CONV_S2A, bias=W[d + ".bias"])
+                sz = (sz[0] // 2, sz[1] // 2)
+        x = self._res("encoder.mid_block.resnets.0", x, S, sz)
+        x = self._attn("encoder.mid_block.attentions.0", x, S, sz)
+        x = self._res("encoder.mid_block.resnets.1", x, S, sz)
+        n, _ = ops.groupnorm(x, S, sz[0] * sz[1], cfg.norm_groups, 1e-6, W["encoder.conv_norm_out.weight"],
                              W["encoder.conv_norm_out.bias"], True)
-        return ops.conv3x3(n, W["encoder.conv_out.weight"], S, H, H, bias=W["encoder.conv_out.bias"]), H
+        return ops.conv3x3(n, W["encoder.conv_out.weight"], S, *sz, bias=W["encoder.conv_out.bias"]), sz
 
     @torch.no_grad()
     def encode(self, img: torch.Tensor, noise: Optional[torch.Tensor] = None, scale: float = 1.0) -> torch.Tensor:
-        """latent_dist.sample() * scale with the N(0,1) draw `noise` [S,4,h,h] (None: latent_dist.mode() * scale)."""
+        """latent_dist.sample() * scale with the N(0,1) draw `noise` [S,4,h,w] (None: latent_dist.mode() * scale)."""
         outs = []
         L = self.cfg.latent_channels
         for s0 in range(0, img.shape[0], self.chunk):
-            m, h = self.moments(img[s0:s0 + self.chunk])
-            n = m.shape[0] // (h * h)
+            m, (h, w) = self.moments(img[s0:s0 + self.chunk])
+            n = m.shape[0] // (h * w)
             nz = None if noise is None else noise[s0:s0 + n].to(self.dev, torch.float32).contiguous()
-            outs.append(ops.gaussian_sample(m, n, L, h * h, nz, scale).reshape(n, L, h, h))
+            outs.append(ops.gaussian_sample(m, n, L, h * w, nz, scale).reshape(n, L, h, w))
         return torch.cat(outs)
 
 
@@ -271,8 +274,8 @@ class _LatentDist:
         if self._mom is None:
             ms, L = [], self._enc.cfg.latent_channels
             for s0 in range(0, self._img.shape[0], self._enc.chunk):
-                m, h = self._enc.moments(self._img[s0:s0 + self._enc.chunk])
-                ms.append(ops.nhwc_to_nchw(m, m.shape[0] // (h * h), 2 * L, h, h))
+                m, (h, w) = self._enc.moments(self._img[s0:s0 + self._enc.chunk])
+                ms.append(ops.nhwc_to_nchw(m, m.shape[0] // (h * w), 2 * L, h, w))
             self._mom = torch.cat(ms)
         return self._mom
 
@@ -292,10 +295,10 @@ class _LatentDist:
         return self._enc.encode(self._img)
 
     def sample(self, generator: Optional[torch.Generator] = None):
-        S, _, H, _ = self._img.shape
-        h = H // 2 ** (len(self._enc.cfg.block_out_channels) - 1)
+        S, _, H, Wd = self._img.shape
+        f = 2 ** (len(self._enc.cfg.block_out_channels) - 1)
         dev = generator.device if generator is not None else self._enc.dev
-        noise = torch.randn(S, self._enc.cfg.latent_channels, h, h, generator=generator, device=dev)
+        noise = torch.randn(S, self._enc.cfg.latent_channels, H // f, Wd // f, generator=generator, device=dev)
         return self._enc.encode(self._img, noise)
 
 

@@ -37,7 +37,7 @@ for seed, t, scale in [(0, 981, 1.0), (1, 881, 1.0), (2, 881, 3.0)]:
     print(f"seed {seed} t {t} scale {scale}: eps rel {rel(e1, e0):.2e}; taps " + " ".join(f"{rel(a, b):.1e}" for a, b in zip(t1, t0)))
     for p in s0.tr:
         a, b = s0.tr[p], s1.tr[p]
-        if a["H"] != h:
+        if a["sz"] != (h, h):
             continue
         M0 = h * h
         cut = lambda d, k, stat=False: d[k] if k in d.get("half", ()) else (d[k][1:] if stat else d[k][M0:])
