@@ -584,6 +584,46 @@ int skg_guidance_update(const void* grad, int ld, const float* x_in, float* x_pr
 #define SKG_BOX_PROBE_WORKGROUPS 512
 int skg_box_probe_mfma(float* out, int iters, void* stream);
 
+/* ---- sketch generator: the anime2sketch U-Net (anime2sketch/model.py UnetGenerator(3, 1, 8, 64, InstanceNorm2d), called by
+ * generate_sketch at trainer.py:36-44 and pic2sketch at anime2sketch/generate.py:7-15) ---------------------------------------
+ * Additive entry points (SKG_ABI_VERSION unchanged).  The down convolutions are skg_conv4x4s2_f16 on the [Cout][16 taps][Cin]
+ * pack of the Conv2d weight; the first one (3 input channels) is skg_a2s_patch_f16 + ONE skg_gemm_f16 with K = 64.
+ *
+ * InstanceNorm2d(C, affine = False, track_running_stats = False) over NHWC fp16 with up to two activated outputs - replaces
+ * nn.InstanceNorm2d followed by the in-place nn.LeakyReLU(0.2) of the next block, the in-place nn.ReLU in front of the up
+ * convolution and the torch.cat of the skip connection:
+ *   n = (x - mean) / sqrt(var + eps) per (row, channel) over HW, biased variance, statistics in fp32 / fp64 of the fp16 values;
+ *   Yk[m][c] = act_k(fp16(n)),  act_k(v) = v >= 0 ? v : slope_k * v   (slope 0.2: LeakyReLU, 0: ReLU, 1: none)
+ * X [rows*HW][ldx >= C]; Y0 / Y1 [rows*HW][ldy_k >= C], each may be a column slice of a wider buffer (the skip half of the
+ * concatenation the up convolution reads) and either may be NULL.  identity != 0: no statistics, n = x (the two activated
+ * copies of a convolution output that has no norm).  C % 64 == 0; all pointers 16-byte aligned, ld % 8 == 0.
+ * Workgroups take (slab of pixels, 64 channels, sample).  HW <= 256: one launch (statistics + apply); larger maps: per-slab partial
+ * sums (256 pixels per slab, longer slabs beyond 65536 pixels: at most 256 of them) into `scratch`, a fold in slab order to
+ * (mean, rstd) per (sample, channel), then the apply launch.  scratch: skg_instnorm_scratch_floats(rows, HW, C) floats,
+ * caller-owned; may be NULL when that is 0 or identity.  No atomics: two runs give identical bits. */
+size_t skg_instnorm_scratch_floats(int rows, int HW, int C);
+int skg_instnorm_act_f16(const void* X, int ldx, int rows, int HW, int C, float eps, int identity, void* Y0, int ldy0,
+                         float slope0, void* Y1, int ldy1, float slope1, float* scratch, void* stream);
+/* nn.ConvTranspose2d(Cin, Cout, kernel_size = 4, stride = 2, padding = 1) (the upconv of every UnetSkipConnectionBlock),
+ * POLYPHASE on the kernel of skg_conv3x3_up2_f16: output pixel (2i+a, 2j+b) reads low-res rows {i-1, i} with filter rows (3, 1)
+ * for a = 0, {i, i+1} with (2, 0) for a = 1, the same for columns.  X [rows*IH*IW][ldx >= Cin] (the [skip | up] concatenation
+ * buffer: Cin up to 1024), Y [rows*2IH*2IW][ldy >= Cout], Wpp [4 phases 2a+b][Cout][4 taps][Cin]
+ * (sketch2img_amd.anime2sketch.pack_convt: no pre-summing).  Cin % 64 == 0, Cout % 8 == 0 (a single output channel is padded
+ * with zero filters).  epilogue SKG_CONVT_EPI_TANH: tanh over the Cout columns of Y (the nn.Tanh of the outermost block), a
+ * second launch over the stored fp16 values.  Returns SKG_E_UNSUPPORTED, nothing launched, when an operand spans 2 GiB or more. */
+#define SKG_CONVT_EPI_NONE 0
+#define SKG_CONVT_EPI_TANH 1
+int skg_convt4x4s2_f16(const void* X, int ldx, const void* Wpp, void* Y, int ldy, int rows, int IH, int IW, int Cin, int Cout,
+                       const void* bias, int epilogue, void* stream);
+/* Operand of the first down convolution (nn.Conv2d(3, 64, 4, 2, 1) on the picture): img float [B][3][H][W] (H, W even) ->
+ * P [B*(H/2)*(W/2)][ldp >= 64] fp16, P[(b, oy, ox)][(ky*4 + kx)*3 + c] = img[b][c][2oy-1+ky][2ox-1+kx] (0 outside), columns 48..63
+ * zero: the layer is then skg_gemm_f16 with K = 64 against sketch2img_amd.anime2sketch.pack_conv_first.  Replaces the float ->
+ * NHWC conversion and a 64-channel zero padding of the picture. */
+int skg_a2s_patch_f16(const float* img, void* P, int ldp, int B, int H, int W, void* stream);
+/* Tail of the generator and of generate_sketch (trainer.py:39-42): y = column 0 of Y [B*H*W][ldy] (fp16, after tanh) ->
+ * y_out float [B][1][H][W] and / or mask float [B][3][H][W] = (1 - y < 0.5 ? 0 : 1) tiled to three channels.  Either may be NULL. */
+int skg_a2s_tail(const void* Y, int ldy, float* y_out, float* mask, int B, int H, int W, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -118,6 +118,12 @@ SIGNATURES = {
     "skg_cfg_dpmpp2m_step": ("i", "ppiippppiiffffffip"),
     "skg_guidance_update": ("i", "pipppiifp"),
     "skg_box_probe_mfma": ("i", "pip"),
+    # sketch generator (anime2sketch.py): additive entry points, same ABI version
+    "skg_instnorm_scratch_floats": ("z", "iii"),
+    "skg_instnorm_act_f16": ("i", "piiiifipifpifpp"),
+    "skg_convt4x4s2_f16": ("i", "pippiiiiiipip"),
+    "skg_a2s_patch_f16": ("i", "ppiiiip"),
+    "skg_a2s_tail": ("i", "pippiiip"),
 }
 
 _CT = {"p": ctypes.c_void_p, "i": ctypes.c_int, "f": ctypes.c_float, "u": ctypes.c_uint,

@@ -14,6 +14,9 @@ Layer 0 keeps the re-association of sketch2img_amd/lgp.py: forward = per-tap GEM
 gather; its weight gradient is the adjoint: scatter d(pre-activation) back to each tap's resolution, then
 dW0[:, tap] = dP_tap^T . F_tap (K = the tap's pixel count), and dW0[:, extras] = dZ0^T . E for the 40 noise-level /
 sinusoid channels.  All weight gradients are plain GEMMs on transposed operands with fp32 output.
+
+The targets (`sketch_latents` of train_step) are the reference's trainer.py:220: sketch2img_amd.anime2sketch.sketch_latents(picture,
+create_model(...), vae) - the sketch generator and the VAE encoder on the same kernels.
 """
 from __future__ import annotations
 

@@ -1054,3 +1054,58 @@ def guidance_update(grad, x_in, x_prev, samples, HW, beta):
     check(lib.skg_guidance_update(_p(grad), _ld(grad), _p(x_in), _p(x_prev), _p(aux), samples, HW, beta,
                                   _stream()), "skg_guidance_update")
     return aux
+
+
+# ---- sketch generator (anime2sketch.py) ------------------------------------------------------------------------------------
+CONVT_EPI_NONE, CONVT_EPI_TANH = 0, 1
+
+
+def instnorm_act(X: torch.Tensor, rows: int, HW: int, out0: Optional[torch.Tensor] = None, slope0: float = 1.0,
+                 out1: Optional[torch.Tensor] = None, slope1: float = 0.0, *, eps: float = 1e-5, identity: bool = False):
+    """InstanceNorm2d(affine=False) of X [rows*HW, C] (view) with up to two activated outputs (views, e.g. the skip half of a
+    concatenation buffer): out_k = act_k(norm(X)), act(v) = v if v >= 0 else slope * v.  identity=True: no statistics."""
+    _f16(X, out0, out1)
+    C = X.shape[1]
+    assert X.shape[0] == rows * HW and all(o is None or o.shape == X.shape for o in (out0, out1))
+    n = 0 if identity else lib.skg_instnorm_scratch_floats(rows, HW, C)
+    scratch = _scratch_buf(("in", _skey(X.device), n), n, X.device) if n else None
+    check(lib.skg_instnorm_act_f16(_p(X), _ld(X), rows, HW, C, eps, int(identity), _p(out0), _ld(out0) if out0 is not None else 0, slope0,
+                                   _p(out1), _ld(out1) if out1 is not None else 0, slope1, _p(scratch), _stream()), "skg_instnorm_act_f16")
+    return out0, out1
+
+
+def convt4x4s2(X: torch.Tensor, Wpp: torch.Tensor, rows: int, IH: int, IW: int, out: Optional[torch.Tensor] = None, *, bias=None,
+               tanh: bool = False):
+    """ConvTranspose2d(4, stride 2, padding 1), polyphase.  X [rows*IH*IW, Cin] (view), Wpp [4, Cout, 4*Cin]
+    (anime2sketch.pack_convt).  Returns [rows*2IH*2IW, Cout]; tanh=True applies tanh to it."""
+    _f16(X, Wpp, bias, out)
+    Cin, Cout = X.shape[1], Wpp.shape[1]
+    assert Wpp.shape == (4, Cout, 4 * Cin) and Wpp.is_contiguous() and X.shape[0] == rows * IH * IW
+    if out is None:
+        out = torch.empty(rows * 4 * IH * IW, Cout, device=X.device, dtype=torch.float16)
+    assert out.shape == (rows * 4 * IH * IW, Cout)
+    check(lib.skg_convt4x4s2_f16(_p(X), _ld(X), _p(Wpp), _p(out), _ld(out), rows, IH, IW, Cin, Cout, _p(bias),
+                                 CONVT_EPI_TANH if tanh else CONVT_EPI_NONE, _stream()), "skg_convt4x4s2_f16")
+    return out
+
+
+def a2s_patch(img: torch.Tensor, out: Optional[torch.Tensor] = None):
+    """float32 [B, 3, H, W] -> fp16 [B*(H/2)*(W/2), 64]: the 4 x 4 stride-2 windows (column (ky*4+kx)*3 + c, 48..63 zero)."""
+    assert img.is_cuda and img.dtype == torch.float32 and img.is_contiguous() and img.shape[1] == 3
+    B, _, H, W = img.shape
+    if out is None:
+        out = torch.empty(B * (H // 2) * (W // 2), 64, device=img.device, dtype=torch.float16)
+    _f16(out)
+    assert out.shape == (B * (H // 2) * (W // 2), 64)
+    check(lib.skg_a2s_patch_f16(_p(img), _p(out), _ld(out), B, H, W, _stream()), "skg_a2s_patch_f16")
+    return out
+
+
+def a2s_tail(Y: torch.Tensor, B: int, H: int, W: int, y: Optional[torch.Tensor] = None, mask: Optional[torch.Tensor] = None):
+    """Column 0 of Y [B*H*W, >= 1] (fp16) -> y float [B, 1, H, W] and / or mask float [B, 3, H, W] = (1 - y >= 0.5), whichever is given."""
+    _f16(Y)
+    assert Y.shape[0] == B * H * W and (y is not None or mask is not None)
+    for t, c in ((y, 1), (mask, 3)):
+        assert t is None or (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.shape == (B, c, H, W))
+    check(lib.skg_a2s_tail(_p(Y), Y.stride(0), _p(y), _p(mask), B, H, W, _stream()), "skg_a2s_tail")
+    return y, mask

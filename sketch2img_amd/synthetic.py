@@ -426,3 +426,55 @@ def clip_text_state_dict(cfg, seed: int = CLIP_TEXT_WEIGHT_SEED) -> Dict[str, to
             w = (torch.rand(shp, generator=g) * 2 - 1) / math.sqrt(math.prod(shp[1:]))
         W[k] = w.half().float()
     return W
+
+
+# ---- anime2sketch generator (anime2sketch.py) ---------------------------------------------------------------------------------
+A2S_WEIGHT_SEED = 20261016
+A2S_DOWN = (3, 64, 128, 256, 512, 512, 512, 512, 512)      # channels of the picture and of d1 .. d8
+
+
+def anime2sketch_param_shapes() -> "OrderedDict[str, tuple]":
+    """state_dict keys -> shapes of the reference's create_model() network (anime2sketch/model.py: UnetGenerator(3, 1, 8, 64,
+    InstanceNorm2d)), in its registration order: the eight down convolutions outside in, then the eight transposed ones inside out."""
+    s: "OrderedDict[str, tuple]" = OrderedDict()
+    prefix = ["model"] + ["model.model.1" + ".model.3" * k for k in range(7)]      # block of level 1 (outermost) .. 8 (innermost)
+    for k in range(8):
+        d = prefix[k] + (".model.0" if k == 0 else ".model.1")
+        s[d + ".weight"] = (A2S_DOWN[k + 1], A2S_DOWN[k], 4, 4); s[d + ".bias"] = (A2S_DOWN[k + 1],)
+    for k in range(7, -1, -1):
+        u = prefix[k] + (".model.3" if k in (0, 7) else ".model.5")
+        cin = A2S_DOWN[k + 1] * (1 if k == 7 else 2)
+        cout = 1 if k == 0 else A2S_DOWN[k]
+        s[u + ".weight"] = (cin, cout, 4, 4); s[u + ".bias"] = (cout,)
+    return s
+
+
+def anime2sketch_state_dict(seed: int = A2S_WEIGHT_SEED) -> Dict[str, torch.Tensor]:
+    """U(-b, b) with b = 1 / sqrt(inputs per output value): 16 Cin for Conv2d, 4 Cin for ConvTranspose2d(4, 2, 1) (each output
+    pixel sees 2 x 2 of the 16 taps); the last bias = 0.55 ~ atanh(0.5) so that generate_sketch's 0.5 threshold cuts through the
+    middle of the output distribution."""
+    g = torch.Generator().manual_seed(seed)
+    shapes = anime2sketch_param_shapes()
+    sd: Dict[str, torch.Tensor] = {}
+    last = list(shapes)[-1]
+    for i, (k, shp) in enumerate(shapes.items()):
+        ws = shapes[k[: -len("bias")] + "weight"] if k.endswith("bias") else shp
+        transposed = i >= 16      # (the eight Conv2d weight / bias pairs come first)
+        bound = 1.0 / math.sqrt((4 * ws[0]) if transposed else (16 * ws[1]))
+        w = (torch.rand(shp, generator=g) * 2 - 1) * bound
+        if k == last:
+            w = torch.full(shp, 0.55)
+        sd[k] = w.half().float()
+    return sd
+
+
+def pictures(first: int, count: int, H: int, W: int) -> torch.Tensor:
+    """Stand-in photographs [count, 3, H, W] in [-1, 1]: per-sample seed 3000 + index, a smooth colour field (a 1/32-resolution
+    random map, bicubically enlarged) + 5 % noise, fp16-representable."""
+    out = []
+    for i in range(first, first + count):
+        g = torch.Generator().manual_seed(3000 + i)
+        low = torch.randn(1, 3, H // 32 + 2, W // 32 + 2, generator=g)
+        field = torch.nn.functional.interpolate(low, size=(H, W), mode="bicubic", align_corners=False)[0]
+        out.append((0.6 * field + 0.05 * torch.randn(3, H, W, generator=g)).clamp(-1.0, 1.0))
+    return torch.stack(out).half().float().contiguous()
