@@ -406,6 +406,13 @@ int skg_attn_bwd_dkv(const void* Q, int ldq, const void* K, int ldk,
                      const void* V, int ldv, const void* dO, int lddo,
                      const float* lse, const float* delta, void* dK, int lddk, void* dV, int lddv,
                      int batch, int heads, int Nq, int Nkv, int dh, float scale, void* stream);
+/* ... with a key stride: K, V, dK, dV rows of batch row b start at b * kv_stride (kv_stride >= Nkv: a padded K / V buffer
+ * such as the injected attention's [N image tokens ; T sketch tokens -> multiple of 8]).  Rows Nkv .. kv_stride - 1 of dK / dV
+ * are left untouched.  kv_stride == Nkv is skg_attn_bwd_dkv bit for bit (same kernel, same grid). */
+int skg_attn_bwd_dkv_strided(const void* Q, int ldq, const void* K, int ldk,
+                             const void* V, int ldv, const void* dO, int lddo,
+                             const float* lse, const float* delta, void* dK, int lddk, void* dV, int lddv,
+                             int batch, int heads, int Nq, int Nkv, int kv_stride, int dh, float scale, void* stream);
 
 /* ---- data movement -----------------------------------------------------------------------------*/
 /* Out[c][m] = In[m][c], fp16, In [M][C] (ldi), Out [C][M] (ldo).  C % 8 == 0, M % 8 == 0. */
@@ -623,6 +630,22 @@ int skg_a2s_patch_f16(const float* img, void* P, int ldp, int B, int H, int W, v
 /* Tail of the generator and of generate_sketch (trainer.py:39-42): y = column 0 of Y [B*H*W][ldy] (fp16, after tanh) ->
  * y_out float [B][1][H][W] and / or mask float [B][3][H][W] = (1 - y < 0.5 ? 0 : 1) tiled to three channels.  Either may be NULL. */
 int skg_a2s_tail(const void* Y, int ldy, float* y_out, float* mask, int B, int H, int W, void* stream);
+
+/* ---- injected-attention (SatMixin) training: weight gradients (csrc/train.hip) -------------------------------------------*/
+/* dW[N][K] (fp32, dense) = or += alpha * dY^T . X;  db[N] (may be NULL) = or += alpha * column sums of dY, same pass.
+ * dY [M][ldy], X [M][ldx] fp16 row-major (ldy >= N, ldx >= K: column views are fine), contraction over the M >= 1 rows (tail
+ * rows masked).  N % 8 == 0, K % 8 == 0, ldy % 8 == 0, ldx % 8 == 0, operands 16-byte aligned.  accumulate != 0: +=.
+ * M is split over workgroups into fp32 slabs in `scratch` (skg_wgrad_scratch_floats(M, N, K) floats) that a second launch
+ * folds in a fixed order: no atomics, bit-repeatable. */
+size_t skg_wgrad_scratch_floats(int M, int N, int K);
+int skg_wgrad_f16(const void* dY, int ldy, const void* X, int ldx, int M, int N, int K, float alpha, int accumulate,
+                  float* dW, float* db, float* scratch, void* stream);
+/* dgamma[c] = or += scale * sum_rows dY[r][c] * (X[r][c] - mean[r]) * rstd[r];  dbeta[c] = or += scale * sum_rows dY[r][c].
+ * stats [M][2] = (mean, rstd) as skg_layernorm_fwd stores them.  C % 8 == 0; scratch: skg_layernorm_param_scratch_floats(C)
+ * floats.  Two stages, fixed order. */
+size_t skg_layernorm_param_scratch_floats(int C);
+int skg_layernorm_param_grads(const void* X, int ldx, const void* dY, int lddy, int M, int C, const float* stats, float scale,
+                              int accumulate, float* dgamma, float* dbeta, float* scratch, void* stream);
 
 #ifdef __cplusplus
 }

@@ -124,6 +124,12 @@ SIGNATURES = {
     "skg_convt4x4s2_f16": ("i", "pippiiiiiipip"),
     "skg_a2s_patch_f16": ("i", "ppiiiip"),
     "skg_a2s_tail": ("i", "pippiiip"),
+    # injected-attention training (sat_train.py): additive entry points, same ABI version
+    "skg_attn_bwd_dkv_strided": ("i", "pipipipipppipiiiiiiifp"),
+    "skg_wgrad_scratch_floats": ("z", "iii"),
+    "skg_wgrad_f16": ("i", "pipiiiifipppp"),
+    "skg_layernorm_param_scratch_floats": ("z", "i"),
+    "skg_layernorm_param_grads": ("i", "pipiiipfipppp"),
 }
 
 _CT = {"p": ctypes.c_void_p, "i": ctypes.c_int, "f": ctypes.c_float, "u": ctypes.c_uint,

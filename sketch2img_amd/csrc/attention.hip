@@ -1628,11 +1628,11 @@ extern "C" int skg_attn_bwd_dq_delta(const void* Q, int ldq, const void* K, int 
                           O, ldo, delta_out);
 }
 
-extern "C" int skg_attn_bwd_dkv(const void* Q, int ldq, const void* K, int ldk,
-                                const void* V, int ldv, const void* dO, int lddo,
-                                const float* lse, const float* delta, void* dK, int lddk, void* dV, int lddv,
-                                int batch, int heads, int Nq, int Nkv, int dh, float scale, void* stream) {
-  SKG_REQUIRE(Q && K && V && dO && lse && delta && dK && dV && common_ok(batch, heads, Nq, Nkv, Nkv, dh, false));
+static int attn_bwd_dkv_impl(const void* Q, int ldq, const void* K, int ldk,
+                             const void* V, int ldv, const void* dO, int lddo,
+                             const float* lse, const float* delta, void* dK, int lddk, void* dV, int lddv,
+                             int batch, int heads, int Nq, int Nkv, int kv_stride, int dh, float scale, void* stream) {
+  SKG_REQUIRE(Q && K && V && dO && lse && delta && dK && dV && common_ok(batch, heads, Nq, Nkv, kv_stride, dh, false));
   SKG_REQUIRE(ldq % 8 == 0 && ldk % 8 == 0 && ldv % 8 == 0 && lddo % 8 == 0 && lddk % 4 == 0 && lddv % 4 == 0);
   SKG_REQUIRE(skg_aligned(Q, 16) && skg_aligned(K, 16) && skg_aligned(V, 16) &&
               skg_aligned(dO, 16) && skg_aligned(dK, 8) && skg_aligned(dV, 8));
@@ -1641,7 +1641,7 @@ extern "C" int skg_attn_bwd_dkv(const void* Q, int ldq, const void* K, int ldk,
   p.V = (const half_t*)V; p.ldv = ldv; p.dO = (const half_t*)dO; p.lddo = lddo;
   p.lse = const_cast<float*>(lse); p.delta = delta; p.O = (half_t*)dK; p.ldo = lddk;
   p.O2 = (half_t*)dV; p.ldo2 = lddv;
-  p.batch = batch; p.heads = heads; p.Nq = Nq; p.Nkv = Nkv; p.kv_stride = Nkv; p.dh = dh; p.scale = scale;
+  p.batch = batch; p.heads = heads; p.Nq = Nq; p.Nkv = Nkv; p.kv_stride = kv_stride; p.dh = dh; p.scale = scale;
   hipStream_t st = (hipStream_t)stream;
   p.nx = skg_cdiv(Nkv, dh <= 40 ? 128 : 64);        // key tiles per wave: 2 up to d = 40, 1 beyond (register budget)
   dim3 grid((unsigned)p.nx * heads * batch);
@@ -1656,6 +1656,22 @@ extern "C" int skg_attn_bwd_dkv(const void* Q, int ldq, const void* K, int ldk,
   }
   SKG_CHECK_LAUNCH("skg_attn_bwd_dkv");
   return SKG_OK;
+}
+
+extern "C" int skg_attn_bwd_dkv(const void* Q, int ldq, const void* K, int ldk,
+                                const void* V, int ldv, const void* dO, int lddo,
+                                const float* lse, const float* delta, void* dK, int lddk, void* dV, int lddv,
+                                int batch, int heads, int Nq, int Nkv, int dh, float scale, void* stream) {
+  return attn_bwd_dkv_impl(Q, ldq, K, ldk, V, ldv, dO, lddo, lse, delta, dK, lddk, dV, lddv, batch, heads, Nq, Nkv, Nkv, dh, scale, stream);
+}
+
+// K, V, dK, dV rows of batch row b start at b * kv_stride (a padded K / V buffer); rows Nkv .. kv_stride - 1 of dK / dV are not written
+extern "C" int skg_attn_bwd_dkv_strided(const void* Q, int ldq, const void* K, int ldk,
+                                        const void* V, int ldv, const void* dO, int lddo,
+                                        const float* lse, const float* delta, void* dK, int lddk, void* dV, int lddv,
+                                        int batch, int heads, int Nq, int Nkv, int kv_stride, int dh, float scale, void* stream) {
+  SKG_REQUIRE(kv_stride >= Nkv);
+  return attn_bwd_dkv_impl(Q, ldq, K, ldk, V, ldv, dO, lddo, lse, delta, dK, lddk, dV, lddv, batch, heads, Nq, Nkv, kv_stride, dh, scale, stream);
 }
 
 #ifdef SKG_PHASES

@@ -207,3 +207,111 @@ class HipInjector:
         a = ops.attn_fwd(q, kvbuf[:, :C], kvbuf[:, C:], rows, heads, N, N + T, L, dh, scale, v_rows=True)
         o = ops.gemm(a, w["wo"], bias=w["bo"])
         return last(o, w["wc"], w["bc"])
+
+
+class HipClipInjectorTrain:
+    """The CLIP-token injector with a stash and a backward: what sat_train.HipSatTrainer installs as ``HipUNet.inject`` while it
+    differentiates one sample (rows = 1).  Nothing is hoisted: the weights change every optimizer step, so sketch_proj, the
+    LayerNorm of the sketch tokens and their K / V are evaluated inside every forward.
+
+    forward (per block, N image tokens, T sketch tokens, L = ceil8(N + T)):
+        x   = [h ; sketch_proj(state)]                    [N + T, C]   (h copied, the projection written behind it)
+        z   = sketch_norm(x), (mean, rstd) per row        one launch over both row groups
+        qkv = z . [Wq ; Wk ; Wv]^T                        [L, 3C], rows >= N + T zero; only the first N rows of q are queries
+        a   = attention(q[:N], k, v; Nkv = N + T, kv_stride = L), lse
+        o   = to_out(a);  out = h + scale * conv1x1(o)
+    kept for the backward: x, the statistics, z, qkv, a, lse, o.
+
+    backward(d out) -> d h (the residual path added), the gradients of the block's 12 tensors accumulated (+=, scaled like
+    d out) into the flat fp32 vector handed to begin(), and d loss / d state += ds . W_proj (fp32 [T, 1024]): the seam where a
+    CLIP-vision backward can attach.  Weight gradients: ops.wgrad on the row-major operands (column views of qkv / d qkv), bias
+    gradients in the same pass, LayerNorm's through ops.layernorm_param_grads."""
+
+    def __init__(self, cfg: UNetConfig, w16, grad_view, device):
+        """w16(key) -> fp16 view of the working copy; grad_view(flat, key) -> fp32 view (state-dict key names)."""
+        self.cfg, self.dev = cfg, torch.device(device)
+        self.w16, self.grad_view = w16, grad_view
+        self.scale = 1.0
+        self.dims = {p: (module_name(p), c, heads) for p, c, heads in block_dims(cfg)}
+        self.state16: Optional[torch.Tensor] = None
+        self.stash: Dict[str, dict] = {}
+        self.g: Optional[torch.Tensor] = None
+        self.dstate: Optional[torch.Tensor] = None
+        self.packs: Dict[str, dict] = {}
+
+    def set_scale(self, scale: float):
+        self.scale = float(scale)
+
+    def refresh(self):
+        """Rebuild the concatenated / transposed operands from the fp16 working copy (once per optimizer step)."""
+        self.packs = {}
+        for path, (n, c, heads) in self.dims.items():
+            w = self.w16
+            wqkv = torch.cat([w(f"{n}.sketch_attn.to_q.weight"), w(f"{n}.sketch_attn.to_k.weight"),
+                              w(f"{n}.sketch_attn.to_v.weight")], 0).contiguous()
+            wo, wc, wp = w(f"{n}.sketch_attn.to_out.0.weight"), w(f"{n}.sketch_conv.weight").reshape(c, c), w(f"{n}.sketch_proj.weight")
+            self.packs[path] = dict(wqkv=wqkv, wqkvT=ops.transpose(wqkv), wo=wo, woT=ops.transpose(wo), wc=wc, wcT=ops.transpose(wc),
+                                    wp=wp, wpT=ops.transpose(wp))
+
+    def begin(self, state16: torch.Tensor, g: torch.Tensor, dstate: torch.Tensor):
+        """One sample: its sketch tokens fp16 [T, 1024], the flat gradient vector to accumulate into, its d state [T, 1024] fp32."""
+        assert state16.dtype == torch.float16 and state16.dim() == 2 and state16.shape[1] == CLIP_DIM
+        self.state16, self.g, self.dstate, self.stash = state16.contiguous(), g, dstate, {}
+
+    def end(self):
+        self.state16 = self.g = self.dstate = None
+        self.stash = {}
+
+    # ---- forward (HipUNet._tr_fwd calls this) ---------------------------------------------------------------------------------
+    def __call__(self, path: str, h, rows: int, N: int, heads: int, cond_only: bool = False, out=None):
+        assert rows == 1 and not cond_only and not isinstance(h, ops.Pair), "training evaluates one all-fp16 sample at a time"
+        n, C, hd = self.dims[path]
+        assert hd == heads and h.shape == (N, C)
+        pk, w = self.packs[path], self.w16
+        T = self.state16.shape[0]
+        NT, L = N + T, (N + T + 7) // 8 * 8
+        dh = C // heads
+        x = torch.empty(NT, C, device=self.dev, dtype=torch.float16)
+        ops.batch_copy(h, N, x, N, 1, N)
+        ops.gemm(self.state16, pk["wp"], out=x[N:], bias=w(f"{n}.sketch_proj.bias"))
+        z, st = ops.layernorm(x, w(f"{n}.sketch_norm.weight"), w(f"{n}.sketch_norm.bias"), want_stats=True)
+        qkv = torch.zeros(L, 3 * C, device=self.dev, dtype=torch.float16)
+        ops.gemm(z, pk["wqkv"], out=qkv[:NT])
+        a, lse = ops.attn_fwd(qkv[:N, :C], qkv[:, C:2 * C], qkv[:, 2 * C:], 1, heads, N, NT, L, dh, dh ** -0.5, want_lse=True,
+                              v_rows=True)
+        o = ops.gemm(a, pk["wo"], bias=w(f"{n}.sketch_attn.to_out.0.bias"))
+        res = ops.gemm(o, pk["wc"], out, bias=w(f"{n}.sketch_conv.bias"), residual=h, alpha=self.scale)
+        self.stash[path] = dict(x=x, st=st, z=z, qkv=qkv, a=a, lse=lse, o=o, N=N, heads=heads)
+        return res
+
+    # ---- backward (HipUNet._tr_bwd calls this through backward_eps(inject_bwd=)) ---------------------------------------------------
+    def backward(self, path: str, dout):
+        n, C, heads = self.dims[path]
+        s, pk, w = self.stash.pop(path), self.packs[path], self.w16
+        N, T = s["N"], self.state16.shape[0]
+        NT, L = N + T, (N + T + 7) // 8 * 8
+        dh = C // heads
+        sc = dh ** -0.5
+        gv = lambda k: self.grad_view(self.g, f"{n}.{k}")
+        acc = dict(accumulate=True)
+        x, z, qkv = s["x"], s["z"], s["qkv"]
+        # out = h + scale * (o . Wc^T + bc)
+        ops.wgrad(dout, s["o"], gv("sketch_conv.weight"), gv("sketch_conv.bias"), alpha=self.scale, **acc)
+        do = ops.gemm(dout, pk["wcT"], alpha=self.scale)
+        ops.wgrad(do, s["a"], gv("sketch_attn.to_out.0.weight"), gv("sketch_attn.to_out.0.bias"), **acc)
+        da = ops.gemm(do, pk["woT"])
+        # attention: queries = the N image rows, keys / values = all N + T rows of the padded buffer
+        dqkv = torch.zeros(L, 3 * C, device=self.dev, dtype=torch.float16)
+        Q, K, V = qkv[:N, :C], qkv[:, C:2 * C], qkv[:, 2 * C:]
+        _, delta = ops.attn_bwd_dq_delta(Q, K, V, da, s["a"], s["lse"], 1, heads, N, NT, L, dh, sc, out=dqkv[:N, :C])
+        ops.attn_bwd_dkv_strided(Q, K, V, da, s["lse"], delta, 1, heads, N, NT, L, dh, sc, dqkv[:, C:2 * C], dqkv[:, 2 * C:])
+        ops.wgrad(dqkv[:N, :C], z[:N], gv("sketch_attn.to_q.weight"), **acc)
+        ops.wgrad(dqkv[:NT, C:2 * C], z, gv("sketch_attn.to_k.weight"), **acc)
+        ops.wgrad(dqkv[:NT, 2 * C:], z, gv("sketch_attn.to_v.weight"), **acc)
+        dz = ops.gemm(dqkv[:NT], pk["wqkvT"])
+        ops.layernorm_param_grads(x, dz, s["st"], gv("sketch_norm.weight"), gv("sketch_norm.bias"), **acc)
+        dx = ops.layernorm_bwd(x, dz, w(f"{n}.sketch_norm.weight"), s["st"])
+        ds = dx[N:]
+        ops.wgrad(ds, self.state16, gv("sketch_proj.weight"), gv("sketch_proj.bias"), **acc)
+        self.dstate += ops.gemm(ds, pk["wpT"], out_f32=True)
+        return ops.axpby(dx[:N], dout)

@@ -833,6 +833,18 @@ def attn_bwd_dkv(Q, K, V, dO, lse, delta, batch, heads, Nq, Nkv, dh, scale, dK=N
     return dK, dV
 
 
+def attn_bwd_dkv_strided(Q, K, V, dO, lse, delta, batch, heads, Nq, Nkv, kv_stride, dh, scale, dK, dV):
+    """attn_bwd_dkv on a padded K / V buffer: rows of batch row b start at b * kv_stride; rows Nkv .. kv_stride - 1 of
+    dK / dV (views of [batch * kv_stride, >= heads * dh] buffers) are left untouched."""
+    _f16(Q, K, V, dO, dK, dV)
+    assert kv_stride >= Nkv and dK.shape[0] >= (batch - 1) * kv_stride + Nkv and dV.shape[0] >= (batch - 1) * kv_stride + Nkv
+    assert K.shape[0] >= (batch - 1) * kv_stride + Nkv and V.shape[0] >= (batch - 1) * kv_stride + Nkv
+    check(lib.skg_attn_bwd_dkv_strided(_p(Q), _ld(Q), _p(K), _ld(K), _p(V), _ld(V), _p(dO), _ld(dO),
+                                       _p(lse), _p(delta), _p(dK), _ld(dK), _p(dV), _ld(dV), batch,
+                                       heads, Nq, Nkv, kv_stride, dh, scale, _stream()), "skg_attn_bwd_dkv_strided")
+    return dK, dV
+
+
 # ---- LGP --------------------------------------------------------------------------------------------
 def lgp_layer0_gather(P: Sequence[torch.Tensor], sizes: Sequence[int], Wextra, bias0, noise, sigma: float,
                       samples: int, h: int, H0: int, out=None, rows: Optional[int] = None, w: Optional[int] = None):
@@ -973,6 +985,48 @@ def adamw_step(param, grad, exp_avg, exp_avg_sq, param_f16, lr, beta1, beta2, ep
     assert param.dtype == grad.dtype == exp_avg.dtype == exp_avg_sq.dtype == torch.float32 and grad.numel() == n
     check(lib.skg_adamw_step(_p(param), _p(grad), _p(exp_avg), _p(exp_avg_sq), _p(param_f16), n, lr, beta1, beta2,
                              eps, weight_decay, step, inv_grad_scale, _stream()), "skg_adamw_step")
+
+
+# ---- injected-attention training (sat_train.py) ---------------------------------------------------------
+def wgrad(dY, X, dW=None, db=None, alpha: float = 1.0, accumulate: bool = False, want_db: bool = False):
+    """dW [N, K] fp32 = or += alpha * dY^T . X (dY [M, N], X [M, K]: fp16 row-major views, contraction over the rows) and,
+    when db is given or want_db is set, db [N] fp32 = or += alpha * colsum(dY) in the same pass (skg_wgrad_f16: no
+    transposed copies, fixed-order reduction).  dW / db must be dense; returns dW or (dW, db)."""
+    _f16(dY, X)
+    M, N = dY.shape
+    K = X.shape[1]
+    assert X.shape[0] == M
+    if dW is None:
+        assert not accumulate
+        dW = torch.empty(N, K, device=dY.device, dtype=torch.float32)
+    if db is None and want_db:
+        assert not accumulate
+        db = torch.empty(N, device=dY.device, dtype=torch.float32)
+    assert dW.dtype == torch.float32 and dW.is_contiguous() and dW.numel() == N * K
+    assert db is None or (db.dtype == torch.float32 and db.is_contiguous() and db.numel() == N)
+    n = lib.skg_wgrad_scratch_floats(M, N, K)
+    scr = _scratch_buf(("wgrad", _skey(dY.device), n), n, dY.device)
+    check(lib.skg_wgrad_f16(_p(dY), _ld(dY), _p(X), _ld(X), M, N, K, alpha, int(accumulate), _p(dW), _p(db), _p(scr),
+                            _stream()), "skg_wgrad_f16")
+    return dW if db is None else (dW, db)
+
+
+def layernorm_param_grads(X, dY, stats, dgamma=None, dbeta=None, scale: float = 1.0, accumulate: bool = False):
+    """(dgamma, dbeta) [C] fp32 = or += scale * (sum_rows dY * xhat, sum_rows dY); stats [M, 2] from layernorm(want_stats=True)."""
+    _f16(X, dY)
+    M, C = X.shape
+    assert dY.shape == (M, C) and stats.dtype == torch.float32 and stats.is_contiguous() and stats.numel() == 2 * M
+    if dgamma is None:
+        assert not accumulate
+        dgamma = torch.empty(C, device=X.device, dtype=torch.float32)
+        dbeta = torch.empty(C, device=X.device, dtype=torch.float32)
+    for t in (dgamma, dbeta):
+        assert t.dtype == torch.float32 and t.is_contiguous() and t.numel() == C
+    n = lib.skg_layernorm_param_scratch_floats(C)
+    scr = _scratch_buf(("lnp", _skey(X.device), n), n, X.device)
+    check(lib.skg_layernorm_param_grads(_p(X), _ld(X), _p(dY), _ld(dY), M, C, _p(stats), scale, int(accumulate),
+                                        _p(dgamma), _p(dbeta), _p(scr), _stream()), "skg_layernorm_param_grads")
+    return dgamma, dbeta
 
 
 # ---- sampler ------------------------------------------------------------------------------------------

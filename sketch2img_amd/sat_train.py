@@ -1,0 +1,233 @@
+"""One training step of the CLIP-token injected attention (SatMixin) on the libskg.so kernels (reference trainer:
+modules/clip_guided_trainer.py:203-236).
+
+    frozen UNet with one SatMixin block per BasicTransformerBlock  ->  every sample noised at its own timestep  ->
+    loss = mse(unet(noisy, t, ehs), noise)  ->  backward through the whole UNet into the 16 injected modules  ->
+    gradient all-reduce across ranks (DDP, bucket_cap_mb = 15)  ->  AdamW, cosine_with_restarts schedule.
+
+How it runs here: one sample at a time (rows = 1) - every sample has its own timestep and the time-embedding bias is folded
+into the conv epilogues per launch - with a Stash, so every block takes the unfused stashing launches; the injector is
+inject.HipClipInjectorTrain (forward with stash, backward with weight gradients); the backward is HipUNet.backward_eps.  The
+gradients of the B samples accumulate (+=) inside one flat fp32 vector; the loss and its seed come from ONE launch over the
+whole batch (skg_lgp_mse_train: the same [B*hw, >= 4] / NCHW layouts), so the seed carries 1 / numel of the whole batch.
+
+What differs from the reference, on purpose (as in lgp_train.py): accelerate's fp16 autocast + GradScaler becomes fp16 compute
+with a STATIC power-of-two loss scale and fp32 master weights; bitsandbytes' AdamW8bit becomes plain fp32 AdamW with the same
+hyper-parameters.  The CLIP vision tower, which the reference trains too, is not differentiated: loss_and_grads returns
+d loss / d sketch_state, the seam where its backward can attach.
+
+Loss scale: gradients of the unscaled loss are 1e-6 ... 1e-5 and underflow fp16 (6 of the 11 parameter kinds off by 30-100 %);
+between 2^10 and 2^16 every tensor is within 5e-3 of the fp32 oracle.  LOSS_SCALE = 2^13 sits in the middle of that
+plateau: the seed 2^13 * 2 (eps - noise) / numel is 2 (eps - noise) at the TINY test size (numel 8192) and (eps - noise) / 4 at
+SD1.5's 4 x 4 x 64 x 64 - both far from fp16's 6e-5 / 65504 limits.
+
+LR schedule - diffusers "cosine_with_restarts", num_cycles = 1 (clip_guided_trainer.py:135-140), for optimizer step s (0-based):
+    s < warmup:   lr * s / max(1, warmup)
+    otherwise:    p = (s - warmup) / max(1, total - warmup);  lr * 0 if p >= 1 else lr * max(0, (1 + cos(pi * ((cycles * p) mod 1))) / 2)
+"""
+from __future__ import annotations
+
+import math
+from typing import Dict, Optional, Sequence, Tuple
+
+import torch
+
+from . import ops
+from .config import UNetConfig
+from .inject import CLIP_DIM, HipClipInjectorTrain, block_dims, module_name
+
+LOSS_SCALE = 8192.0        # 2^13, see the module docstring
+_LEAVES = ("sketch_proj.weight", "sketch_proj.bias", "sketch_norm.weight", "sketch_norm.bias", "sketch_attn.to_q.weight",
+           "sketch_attn.to_k.weight", "sketch_attn.to_v.weight", "sketch_attn.to_out.0.weight", "sketch_attn.to_out.0.bias",
+           "sketch_conv.weight", "sketch_conv.bias")
+
+
+def param_shapes(cfg: UNetConfig) -> "Dict[str, Tuple[int, ...]]":
+    """SatMixin.state_dict() keys / shapes of the CLIP variant, in the checkpoint's order."""
+    out: Dict[str, Tuple[int, ...]] = {}
+    for path, c, _ in block_dims(cfg):
+        n = module_name(path)
+        for leaf in _LEAVES:
+            if leaf == "sketch_proj.weight":
+                shp: Tuple[int, ...] = (c, CLIP_DIM)
+            elif leaf == "sketch_conv.weight":
+                shp = (c, c, 1)
+            elif leaf.endswith("bias") or leaf.startswith("sketch_norm"):
+                shp = (c,)
+            else:
+                shp = (c, c)
+            out[f"{n}.{leaf}"] = shp
+    return out
+
+
+def cosine_with_restarts(step: int, warmup: int, total: int, cycles: int = 1) -> float:
+    """The multiplier diffusers' get_cosine_with_hard_restarts_schedule_with_warmup applies at optimizer step `step`."""
+    if step < warmup:
+        return float(step) / float(max(1, warmup))
+    p = float(step - warmup) / float(max(1, total - warmup))
+    if p >= 1.0:
+        return 0.0
+    return max(0.0, 0.5 * (1.0 + math.cos(math.pi * ((float(cycles) * p) % 1.0))))
+
+
+def mse_seed(eps16: torch.Tensor, noise: torch.Tensor, B: int, h: int, loss_scale: float = LOSS_SCALE):
+    """eps16 fp16 [B*h*h, >= 4] (the UNet's output rows of all samples), noise fp32 [B, 4, h, h] ->
+    (loss = mean((eps - noise)^2) over the whole batch, d eps = loss_scale * 2 (eps - noise) / numel as fp16
+    [B*h*h, EPS_SEED_LD], 4 valid channels, the rest zero)."""
+    from .unet import EPS_SEED_LD
+    noise = noise.to(eps16.device, torch.float32).contiguous()
+    assert noise.shape == (B, 4, h, h) and eps16.shape[0] == B * h * h
+    seed, parts = ops.lgp_mse_train(eps16, noise, B, h, EPS_SEED_LD, loss_scale)
+    return parts.sum(), seed
+
+
+def add_noise(latents: torch.Tensor, noise: torch.Tensor, timesteps: Sequence[int], alphas_cumprod: torch.Tensor):
+    """DDPMScheduler.add_noise with host-side fp32 scalars per sample."""
+    acp = alphas_cumprod.to(torch.float32)
+    a = torch.stack([acp[int(t)] ** 0.5 for t in timesteps]).view(-1, 1, 1, 1).to(latents.device)
+    s = torch.stack([(1 - acp[int(t)]) ** 0.5 for t in timesteps]).view(-1, 1, 1, 1).to(latents.device)
+    return a * latents + s * noise
+
+
+class HipSatTrainer:
+    def __init__(self, cfg: UNetConfig, state_dict: Dict[str, torch.Tensor], device="cuda", lr: float = 2e-4,
+                 betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 1e-2, warmup_steps: int = 150,
+                 total_steps: int = 10000, num_cycles: int = 1, scale: float = 1.0):
+        dev = self.dev = torch.device(device)
+        self.cfg = cfg
+        self.lr, self.betas, self.eps, self.wd = lr, betas, eps, weight_decay
+        self.warmup, self.total, self.cycles = warmup_steps, total_steps, num_cycles
+        self.step_count = 0
+        # flat fp32 master vector in the checkpoint's key order, every tensor 16-byte aligned in the fp16 copy
+        self.layout: Dict[str, Tuple[int, torch.Size]] = {}
+        off = 0
+        for k, shp in param_shapes(cfg).items():
+            assert tuple(state_dict[k].shape) == tuple(shp), (k, tuple(state_dict[k].shape), shp)
+            self.layout[k] = (off, torch.Size(shp))
+            off += (math.prod(shp) + 7) // 8 * 8
+        self.n = off
+        self.p = torch.zeros(off, device=dev, dtype=torch.float32)
+        for k, (o, shp) in self.layout.items():
+            self.p[o:o + shp.numel()] = state_dict[k].detach().to(dev, torch.float32).reshape(-1)
+        self.p16 = self.p.to(torch.float16)
+        self.m = torch.zeros_like(self.p)
+        self.v = torch.zeros_like(self.p)
+        self.injector = HipClipInjectorTrain(cfg, self.w16, self.grad_view, dev)
+        self.injector.set_scale(scale)
+        self._packs_stale = True
+
+    # ------------------------------------------------------------------------------------------ views
+    def w16(self, key: str) -> torch.Tensor:
+        o, shp = self.layout[key]
+        return self.p16[o:o + shp.numel()].view(shp)
+
+    def grad_view(self, g: torch.Tensor, key: str) -> torch.Tensor:
+        o, shp = self.layout[key]
+        return g[o:o + shp.numel()].view(shp)
+
+    # ------------------------------------------------------------------------------------------ fwd + bwd
+    @torch.no_grad()
+    def loss_and_grads(self, net, latents: torch.Tensor, noise: torch.Tensor, timesteps: Sequence[int], ehs: torch.Tensor,
+                       sketch_state: torch.Tensor, alphas_cumprod: torch.Tensor, loss_scale: float = LOSS_SCALE):
+        """latents, noise fp32 [B, 4, h, h]; timesteps: B ints; ehs [B, 77, D]; sketch_state [B, T, 1024].
+        loss_scale: a power of two (step() divides by LOSS_SCALE: leave the default unless the caller rescales itself).
+        Returns (loss, flat fp32 gradient x LOSS_SCALE in the layout of the master vector, d loss / d sketch_state x LOSS_SCALE
+        fp32 [B, T, 1024])."""
+        fw = self.forward_batch(net, latents, noise, timesteps, ehs, sketch_state, alphas_cumprod, loss_scale)
+        return self.backward_batch(net, fw)
+
+    @torch.no_grad()
+    def forward_batch(self, net, latents, noise, timesteps, ehs, sketch_state, alphas_cumprod, loss_scale: float = LOSS_SCALE):
+        """The stashing forward of every sample, the loss and its seed (the loss is a mean over the whole batch, so all
+        forwards come first).  Returns what backward_batch consumes."""
+        from .unet import CIN_PAD, Stash
+        if net.residual_fp32:
+            raise NotImplementedError("HipSatTrainer: the accuracy mode (residual_fp32) is not supported - build the HipUNet "
+                                      "without residual_fp32")
+        B, _, h, w = latents.shape
+        assert h == w, "square maps only"
+        dev = self.dev
+        if self._packs_stale:
+            self.injector.refresh()
+            self._packs_stale = False
+        noise = noise.to(dev, torch.float32).contiguous()
+        noisy = add_noise(latents.to(dev, torch.float32), noise, timesteps, alphas_cumprod)
+        state16 = sketch_state.to(dev, torch.float16)
+        T = state16.shape[1]
+        hw = h * h
+        g = torch.zeros(self.n, device=dev, dtype=torch.float32)
+        dstate = torch.zeros(B, T, CLIP_DIM, device=dev, dtype=torch.float32)
+        prev = net.inject
+        net.inject = self.injector
+        try:
+            eps_all = torch.empty(B * hw, 8, device=dev, dtype=torch.float16)
+            kept = []
+            for b in range(B):
+                net.prepare_context(ehs[b:b + 1])
+                x32 = ops.nchw_to_nhwc(noisy[b:b + 1].contiguous(), CIN_PAD)
+                stash = Stash()
+                self.injector.begin(state16[b], g, dstate[b])
+                eps, _ = net.forward(x32, int(timesteps[b]), 1, h, stash, want_taps=False, want_eps=True)
+                ops.batch_copy(eps, hw, eps_all[b * hw:], hw, 1, hw)
+                kept.append((stash, self.injector.stash, net.ctx))
+            loss, seed = mse_seed(eps_all, noise, B, h, loss_scale)
+        finally:
+            self.injector.end()
+            net.inject = prev
+        return dict(loss=loss, seed=seed, kept=kept, g=g, dstate=dstate, state16=state16, hw=hw)
+
+    @torch.no_grad()
+    def backward_batch(self, net, fw: dict):
+        """HipUNet.backward_eps of every sample into the flat gradient vector.  -> (loss, g, d sketch_state)."""
+        g, dstate, kept, hw = fw["g"], fw["dstate"], fw["kept"], fw["hw"]
+        prev, prev_ctx = net.inject, net.ctx
+        net.inject = self.injector
+        try:
+            for b in range(len(kept)):
+                stash, istash, ctx = kept[b]
+                net.ctx = ctx                                      # (the cross-attention K / V of this sample's prompt)
+                self.injector.begin(fw["state16"][b], g, dstate[b])
+                self.injector.stash = istash
+                net.backward_eps(stash, fw["seed"][b * hw:(b + 1) * hw], inject_bwd=self.injector.backward)
+                kept[b] = None
+        finally:
+            self.injector.end()
+            net.inject, net.ctx = prev, prev_ctx
+        return fw["loss"], g, dstate
+
+    # ------------------------------------------------------------------------------------------ collective
+    def all_reduce(self, g: torch.Tensor, bucket_bytes: int = 15 << 20) -> torch.Tensor:
+        """Average the flat gradient over the ranks: dist.allreduce_mean_ (15 MB buckets like the reference's DDP)."""
+        from .dist import allreduce_mean_
+        return allreduce_mean_(g, bucket_bytes)
+
+    # ------------------------------------------------------------------------------------------ optimizer
+    def current_lr(self) -> float:
+        return self.lr * cosine_with_restarts(self.step_count, self.warmup, self.total, self.cycles)
+
+    @torch.no_grad()
+    def step(self, g: torch.Tensor) -> bool:
+        """AdamW on the fp32 master vector (g carries LOSS_SCALE), fp16 copy refreshed.  A non-finite gradient skips the step:
+        returns False with p, m, v and the step count untouched (the static-scale form of GradScaler's skipped step)."""
+        if not bool(torch.isfinite(g).all()):
+            return False
+        lr = self.current_lr()
+        self.step_count += 1
+        ops.adamw_step(self.p, g, self.m, self.v, self.p16, lr, self.betas[0], self.betas[1], self.eps, self.wd,
+                       self.step_count, 1.0 / LOSS_SCALE)
+        self._packs_stale = True
+        return True
+
+    def state_dict(self) -> Dict[str, torch.Tensor]:
+        """The reference's checkpoint (sketch_attn_model.pt): fp32 master weights under SatMixin's keys."""
+        return {k: self.p[o:o + shp.numel()].view(shp).clone() for k, (o, shp) in self.layout.items()}
+
+
+@torch.no_grad()
+def train_step(trainer: HipSatTrainer, net, latents: torch.Tensor, ehs: torch.Tensor, sketch_state: torch.Tensor,
+               timesteps: Sequence[int], noise: torch.Tensor, alphas_cumprod: torch.Tensor):
+    """clip_guided_trainer.py:203-236 for one batch: noise the latents, UNet forward / backward per sample, gradient all-reduce
+    across ranks, AdamW.  Returns (loss (0-dim tensor), whether the optimizer stepped, d loss / d sketch_state x LOSS_SCALE)."""
+    loss, g, dstate = trainer.loss_and_grads(net, latents, noise, timesteps, ehs, sketch_state, alphas_cumprod)
+    trainer.all_reduce(g)
+    return loss, trainer.step(g), dstate

@@ -57,6 +57,7 @@ _HP_WINO = os.environ.get("SKG_HP_WINO", "0") != "0"
 CIN_PAD = 64      # latent channels padded to one 64-deep K tile of the LDS-DMA implicit-GEMM conv
 COUT_PAD = 8      # conv_out / conv_in-dgrad output channels padded to the 8-channel store granule
 CTX_PAD = 8       # text tokens padded to a multiple of 8 (77 -> 80)
+EPS_SEED_LD = 32  # columns of the d eps seed of backward_eps: one 32-deep K step of conv_out's data gradient (4 valid channels)
 
 
 # spatial sizes inside the UNet are (height, width) pairs; every level keeps the latent's aspect ratio (both sides are
@@ -409,6 +410,8 @@ class HipUNet:
                         W[k + ":T"] = pack_conv_dgrad(v, dev, cin_pad=COUT_PAD)
                 elif k == "conv_out.weight":
                     W[k] = pack_conv(v, dev, cout_pad=COUT_PAD)
+                    if bw:      # backward from eps (backward_eps): d eps arrives in EPS_SEED_LD columns, 4 of them valid
+                        W[k + ":T"] = pack_conv_dgrad(v, dev, cout_pad=EPS_SEED_LD)
                 else:
                     W[k] = pack_conv(v, dev)
                     if bw:
@@ -1070,9 +1073,11 @@ class HipUNet:
                     on_taps(taps_down + [tap_at, tap_r0, tap_r1] + taps_up)
         eps = None
         if want_eps:
-            n, _ = ops.groupnorm(h, rows, cur[0] * cur[1], cfg.norm_groups, 1e-5, W["conv_norm_out.weight"],
-                                 W["conv_norm_out.bias"], True, partial=hp)
+            n, nst = ops.groupnorm(h, rows, cur[0] * cur[1], cfg.norm_groups, 1e-5, W["conv_norm_out.weight"],
+                                   W["conv_norm_out.bias"], True, partial=hp)
             eps = ops.conv3x3(n, W["conv_out.weight"], rows, *cur, bias=W["conv_out.bias"])
+            if stash is not None:      # what backward_eps reads (references only: no extra launch)
+                stash.misc.update(out_h=h, out_st=nst)
         taps = taps_down + [tap_at, tap_r0, tap_r1] + taps_up
         if stash is not None:
             stash.misc.update(rows=rows, H=H, W=sz[1])
@@ -1532,15 +1537,18 @@ class HipUNet:
         return eps, (taps if want_taps else None)
 
     # ------------------------------------------------------------------ modules, backward (cond rows)
-    def _res_bwd(self, p, dout, S, st: dict):
+    def _res_bwd(self, p, dout, S, st: dict, r0: Optional[int] = None):
+        """S: number of differentiated rows; r0: the first of them in the stashed tensors (default S: the cond half of a
+        CFG-doubled batch; backward_eps passes rows // 2 with S = rows - rows // 2, so rows = 1 differentiates its one row)."""
         cfg, W = self.cfg, self.W
         sz = st["sz"]
         HW, G = sz[0] * sz[1], cfg.norm_groups
+        r0 = S if r0 is None else r0
         if st.get("half"):        # the shared CFG prefix was evaluated on the cond rows only
             x, h1, st1, st2 = st["x"], st["h1"], st["st1"], st["st2"]
         else:
-            x, h1 = st["x"][S * HW:], st["h1"][S * HW:]
-            st1, st2 = st["st1"][S:], st["st2"][S:]
+            x, h1 = st["x"][r0 * HW:], st["h1"][r0 * HW:]
+            st1, st2 = st["st1"][r0:], st["st2"][r0:]
         dn2 = self._conv_wino(p + ".conv2.weight:winoT", dout, S, sz)
         if dn2 is None:
             dn2 = ops.conv3x3(dout, W[p + ".conv2.weight:T"], S, *sz)
@@ -1555,19 +1563,23 @@ class HipUNet:
         return ops.groupnorm_bwd(x, dn1, S, HW, G, st1, W[p + ".norm1.weight"], W[p + ".norm1.bias"], True,
                                  residual=sc)
 
-    def _tr_bwd(self, p, dout, S, st: dict):
+    def _tr_bwd(self, p, dout, S, st: dict, r0: Optional[int] = None, inject_bwd: Optional[Callable] = None):
+        """S / r0: see _res_bwd.  inject_bwd(block path, d p1) -> d (p1 in front of the injected attention): the backward of the
+        injector the stashed forward ran between the self-attention and norm2 (backward_eps)."""
         cfg, W = self.cfg, self.W
         sz, heads = st["sz"], st["heads"]
         HW = sz[0] * sz[1]
-        M0 = S * HW
+        r0 = S if r0 is None else r0
+        M0 = S * HW                                              # rows of every gradient tensor
+        O0 = r0 * HW                                             # where the differentiated rows start in the stashed tensors
         C = dout.shape[1]
         dh = C // heads
         scale = dh ** -0.5
         t = p + ".transformer_blocks.0"
         half = st.get("half", ())
-        c = lambda a: a[M0:]
-        cc = lambda k: st[k] if k in half else st[k][M0:]        # activations [rows*HW, .] of the cond rows
-        cs = lambda k: st[k] if k in half else st[k][S:]         # per-row statistics / lse of the cond rows
+        c = lambda a: a[O0:]
+        cc = lambda k: st[k] if k in half else st[k][O0:]        # activations [rows*HW, .] of the cond rows
+        cs = lambda k: st[k] if k in half else st[k][r0:]        # per-row statistics / lse of the cond rows
         dp3 = ops.gemm(dout, W[p + ".proj_out.weight:T"])
         dgg = ops.gemm(dp3, W[t + ".ff.net.2.weight:T"])
         df = ops.geglu_bwd(st["f"], dgg, interleaved=True)            # f is stashed for the cond rows only
@@ -1578,13 +1590,15 @@ class HipUNet:
         cb = self.ctx["blocks"][t + ".attn2"]
         L, Lp = self.ctx["L"], self.ctx["Lp"]
         if _ATTN_DQ_DELTA:      # delta = sum_d dO O in the prologue of the dQ launch (one launch and one read of dO fewer)
-            dq2, _ = ops.attn_bwd_dq_delta(cc("q2"), cb["K"][S * Lp:], cb["V"][S * Lp:], do2, cc("o2"), cs("lse2"), S, heads, HW, L, Lp, dh, scale)
+            dq2, _ = ops.attn_bwd_dq_delta(cc("q2"), cb["K"][r0 * Lp:], cb["V"][r0 * Lp:], do2, cc("o2"), cs("lse2"), S, heads, HW, L, Lp, dh, scale)
         else:
             delta2 = ops.attn_bwd_delta(cc("o2"), do2, S, heads, HW, dh)
-            dq2 = ops.attn_bwd_dq(cc("q2"), cb["K"][S * Lp:], cb["V"][S * Lp:], do2, cs("lse2"),
+            dq2 = ops.attn_bwd_dq(cc("q2"), cb["K"][r0 * Lp:], cb["V"][r0 * Lp:], do2, cs("lse2"),
                                   delta2, S, heads, HW, L, Lp, dh, scale)
         da2 = ops.gemm(dq2, W[t + ".attn2.to_q.weight:T"])
         dp1 = ops.layernorm_bwd(cc("p1"), da2, W[t + ".norm2.weight"], cc("st2"), residual=dp2)
+        if inject_bwd is not None:      # the stashed p1 is the injector's output: through it to the self-attention's output
+            dp1 = inject_bwd(t, dp1)
         # self-attention
         do1 = ops.gemm(dp1, W[t + ".attn1.to_out.0.weight:T"])
         qkv = cc("qkv")
@@ -1608,9 +1622,41 @@ class HipUNet:
         """tap_grads: 9 fp16 tensors [S*s*s, C] (cond rows) in tap order.  Returns d loss / d x for the
         cond rows, fp16 [S*H*W, 8] (first 4 channels valid; H x W: the stashed forward's size)."""
         assert self.need_backward and self.inject is None, "backward with injected attention is not supported"
+        rows = stash.misc["rows"]
+        return self._backward_chain(stash, tap_grads[8], tap_grads, 2, rows // 2, rows // 2, None, False)
+
+    def backward_eps(self, stash: Stash, d_eps: torch.Tensor, inject_bwd: Optional[Callable] = None) -> Optional[torch.Tensor]:
+        """Backward from the UNet's output.  d_eps: fp16 [S*H*W, EPS_SEED_LD] (first 4 channels valid, the rest zero) for the rows
+        from rows // 2 on (S = rows - rows // 2: the cond half of a CFG-doubled batch, or the single row of a rows = 1 evaluation) of
+        a forward(..., stash, want_eps=True).  conv_out's data gradient, conv_norm_out's GroupNorm + SiLU backward, then every up
+        block, the mid block and the down path.  inject_bwd: see _tr_bwd - the forward ran with an injector, whose parameter
+        gradients are the point; the chain then stops in front of down_blocks.0.attentions.0 (nothing trainable lies further
+        up) and returns None.  Without an injector: d loss / d x like backward().  All-fp16 mode, square maps, eager."""
+        assert self.need_backward, "built with need_backward=False: no :T packs"
+        if self.residual_fp32:
+            raise NotImplementedError("backward_eps: the accuracy mode (residual_fp32) is not supported")
+        assert (self.inject is None) == (inject_bwd is None), "an injected forward needs the injector's backward (and only it)"
         cfg, W = self.cfg, self.W
         rows, sz = stash.misc["rows"], (stash.misc["H"], stash.misc.get("W", stash.misc["H"]))
-        S = rows // 2
+        if sz[0] != sz[1]:
+            raise NotImplementedError("backward_eps: square maps only")
+        assert "out_h" in stash.misc, "the stashed forward ran without want_eps"
+        r0 = rows // 2
+        S = rows - r0
+        HW = sz[0] * sz[1]
+        assert d_eps.shape == (S * HW, EPS_SEED_LD)
+        dn = ops.conv3x3(d_eps, W["conv_out.weight:T"], S, *sz)
+        dh = ops.groupnorm_bwd(stash.misc["out_h"][r0 * HW:], dn, S, HW, cfg.norm_groups, stash.misc["out_st"][r0:],
+                               W["conv_norm_out.weight"], W["conv_norm_out.bias"], True)
+        nb = len(cfg.block_out_channels)
+        return self._backward_chain(stash, dh, [None] * 9, nb - 1, S, r0, inject_bwd, inject_bwd is not None)
+
+    def _backward_chain(self, stash: Stash, dh, tap_grads, first_up: int, S: int, r0: int, inject_bwd, stop_early: bool):
+        """The reversed graph from the output of up block `first_up` (after its upsampler, if it has one) to the input.
+        S rows are differentiated, starting at row r0 of the stashed tensors.  stop_early: return None after
+        down_blocks.0.attentions.0 instead of finishing the first ResnetBlock and conv_in."""
+        cfg, W = self.cfg, self.W
+        sz = (stash.misc["H"], stash.misc.get("W", stash.misc["H"]))
         nb = len(cfg.block_out_channels)
         lpb = cfg.layers_per_block
 
@@ -1624,8 +1670,8 @@ class HipUNet:
         # skip index bookkeeping: skips = [conv_in] + per down block (lpb resnet outs [+ downsample out])
         n_skips = 1 + sum(lpb + (1 if i < nb - 1 else 0) for i in range(nb))
         gskip: List[Optional[torch.Tensor]] = [None] * n_skips
-        # ---- up path, reversed (blocks 2, 1, 0; block 3 does not feed any tap)
-        cur = sz                                 # spatial size of up block 2's output (after its upsampler)
+        # ---- up path, reversed (backward: blocks 2, 1, 0 - block 3 does not feed any tap; backward_eps: from block nb - 1)
+        cur = sz                                 # spatial size of up block first_up's output (after its upsampler; nb = 4)
         for _ in range(nb - 1 - 3):              # generic: taps end at up block 2
             pass
         # index of the skip consumed first by up block i: pops from the end
@@ -1635,10 +1681,9 @@ class HipUNet:
             for j in range(lpb + 1):
                 pop_idx -= 1
                 consumed[(i, j)] = pop_idx
-        dh = tap_grads[8]
         cur = sz
         plan = up_block_plan(cfg)
-        for i in (2, 1, 0):
+        for i in range(first_up, -1, -1):
             if i < nb - 1:
                 # upsampler backward: dgrad at the upsampled size, then 2x2 sum-pool
                 p = f"up_blocks.{i}.upsamplers.0.conv"
@@ -1651,21 +1696,21 @@ class HipUNet:
                     dh = ops.sumpool2x2(du, S, *cur)
             for j in range(lpb, -1, -1):
                 if i > 0:
-                    dh = self._tr_bwd(f"up_blocks.{i}.attentions.{j}", dh, S, stash.tr[f"up_blocks.{i}.attentions.{j}"])
-                dcat = self._res_bwd(f"up_blocks.{i}.resnets.{j}", dh, S, stash.res[f"up_blocks.{i}.resnets.{j}"])
+                    dh = self._tr_bwd(f"up_blocks.{i}.attentions.{j}", dh, S, stash.tr[f"up_blocks.{i}.attentions.{j}"], r0, inject_bwd)
+                dcat = self._res_bwd(f"up_blocks.{i}.resnets.{j}", dh, S, stash.res[f"up_blocks.{i}.resnets.{j}"], r0)
                 ch = plan[i][j][0]
                 k = consumed[(i, j)]
                 gskip[k] = add(gskip[k], dcat[:, ch:])
                 dh = dcat[:, :ch]
-            if i > 0:
+            if 0 < i <= 3:
                 dh = add(dh, tap_grads[6 + i - 1])      # output of up block i-1 (after its upsampler)
         # ---- mid
         dh = add(dh, tap_grads[5])
-        dh = self._res_bwd("mid_block.resnets.1", dh, S, stash.res["mid_block.resnets.1"])
+        dh = self._res_bwd("mid_block.resnets.1", dh, S, stash.res["mid_block.resnets.1"], r0)
         dh = add(dh, tap_grads[3])
-        dh = self._tr_bwd("mid_block.attentions.0", dh, S, stash.tr["mid_block.attentions.0"])
+        dh = self._tr_bwd("mid_block.attentions.0", dh, S, stash.tr["mid_block.attentions.0"], r0, inject_bwd)
         dh = add(dh, tap_grads[4])
-        dh = self._res_bwd("mid_block.resnets.0", dh, S, stash.res["mid_block.resnets.0"])
+        dh = self._res_bwd("mid_block.resnets.0", dh, S, stash.res["mid_block.resnets.0"], r0)
         # ---- down path, reversed
         k = n_skips - 1
         for i in range(nb - 1, -1, -1):
@@ -1680,7 +1725,9 @@ class HipUNet:
                 dh = add(dh, gskip[k]); k -= 1
                 if i < nb - 1:
                     dh = self._tr_bwd(f"down_blocks.{i}.attentions.{j}", dh, S,
-                                      stash.tr[f"down_blocks.{i}.attentions.{j}"])
-                dh = self._res_bwd(f"down_blocks.{i}.resnets.{j}", dh, S, stash.res[f"down_blocks.{i}.resnets.{j}"])
+                                      stash.tr[f"down_blocks.{i}.attentions.{j}"], r0, inject_bwd)
+                    if stop_early and i == 0 and j == 0:
+                        return None
+                dh = self._res_bwd(f"down_blocks.{i}.resnets.{j}", dh, S, stash.res[f"down_blocks.{i}.resnets.{j}"], r0)
         dh = add(dh, gskip[0])
         return ops.conv3x3(dh, W["conv_in.weight:T"], S, *sz)
