@@ -219,7 +219,7 @@ def gemm_geglu_keep(A: torch.Tensor, B: torch.Tensor, bias: Optional[torch.Tenso
 def ff_block(X, gamma, beta, eps: float, pack: torch.Tensor, bias1_pack: torch.Tensor, bias2: torch.Tensor,
              out=None, want_stats: bool = False, keep_from: Optional[int] = None):
     """Fused feed-forward sub-block at C = 320: out = X + b2 + W2 . geglu(W1 . LayerNorm(X) + b1) in one launch
-    (skg_ff_block_f16; pack / bias1_pack from unet.pack_ff_block).  out may be X.
+    (skg_ff_block_f16; pack / bias1_pack from packs.pack_ff_block).  out may be X.
     keep_from=m0: rows >= m0 also store the FF1 output (interleaved pack, what geglu_bwd reads) -> returned last.
     X (and out) may be ops.Pair objects (accuracy mode: skg_ff_block_f16_hilo)."""
     pair = isinstance(X, Pair)
@@ -251,7 +251,7 @@ def ff_block(X, gamma, beta, eps: float, pack: torch.Tensor, bias1_pack: torch.T
 def ff_block_proj(X, gamma, beta, eps: float, pack: torch.Tensor, bias1_pack: torch.Tensor, bias2: torch.Tensor, bias_proj: torch.Tensor,
                   R: torch.Tensor, out=None, want_stats: bool = False, keep_from: Optional[int] = None, gn: Optional[Tuple[int, int]] = None):
     """ff_block followed by Transformer2DModel.proj_out and the outer residual in the same launch (skg_ff_block_proj_f16):
-    out = R + bias_proj + W_proj . fp16(X + FF(LayerNorm(X))); pack = unet.pack_ff_block(..., w_proj) (five chunks more).
+    out = R + bias_proj + W_proj . fp16(X + FF(LayerNorm(X))); pack = packs.pack_ff_block(..., w_proj) (five chunks more).
     gn = (HW, groups): also the GroupNorm partial sums of out.  Returns (out, stats | None, pre | None, GNPartial | None);
     out must not be X (it may be R)."""
     pair = isinstance(X, Pair)
@@ -290,7 +290,7 @@ def ff_block_proj(X, gamma, beta, eps: float, pack: torch.Tensor, bias1_pack: to
 def xattn_block(X, HW: int, heads: int, Nkv: int, gamma, beta, eps: float, wpack: torch.Tensor, kvpack: torch.Tensor,
                 bias_out: torch.Tensor, scale: float, out=None, keep_from: Optional[int] = None):
     """Fused cross-attention sub-block at C = 320, 8 heads: out = X + bo + Wo . Attention(Wq . LayerNorm(X), K, V) over the text
-    keys of each row's image, in one launch (skg_xattn_block_f16; packs from unet.pack_xattn_weights / pack_xattn_kv).
+    keys of each row's image, in one launch (skg_xattn_block_f16; packs from packs.pack_xattn_weights / pack_xattn_kv).
     X (and out) may be ops.Pair objects (accuracy mode: skg_xattn_block_f16_hilo)."""
     pair = isinstance(X, Pair)
     Xh = X.hi if pair else X
@@ -413,7 +413,7 @@ def groupnorm_wino(X: torch.Tensor, rows: int, IH: int, IW: int, groups: int, ep
 def conv3x3_wino(X: Optional[torch.Tensor], U: torch.Tensor, rows: int, IH: int, IW: int, out: Optional[torch.Tensor] = None, *, bias=None,
                  residual=None, relu: bool = False, out_lo=None, residual_lo=None, V: Optional[torch.Tensor] = None):
     """3x3 stride-1 convolution by Winograd F(2x2, 3x3) (skg_conv3x3_wino_f16): X [rows*IH*IW, Cin] (view), U [Cout, 16*Cin] =
-    unet.pack_conv_wino(weight).  Returns [rows*IH*IW, Cout].  Raises SkgError(rc = -2) when declined (odd map, Cin % 64, no room for the
+    packs.pack_conv_wino(weight).  Returns [rows*IH*IW, Cout].  Raises SkgError(rc = -2) when declined (odd map, Cin % 64, no room for the
     16 fp32 slabs in the stream's workspace): the caller runs conv3x3.  X = None, V = groupnorm_wino(...)[0]: the input transform exists."""
     _f16(X, U, bias, residual, out_lo, residual_lo, V)
     Cout = U.shape[0]
@@ -440,7 +440,7 @@ def conv3x3_wino(X: Optional[torch.Tensor], U: torch.Tensor, rows: int, IH: int,
 
 def conv_up2(X: torch.Tensor, Wpp: torch.Tensor, rows: int, IH: int, IW: int, out: Optional[torch.Tensor] = None, *, bias=None, W9=None):
     """Nearest-2x upsample + 3x3 conv, polyphase (four 4-tap convs over the low-res input).  X [rows*IH*IW, Cin] (view),
-    Wpp [4, Cout, 4*Cin] (unet.pack_conv_up2).  Returns [rows*2IH*2IW, Cout].  W9: the layer's ordinary 9-tap pack - the
+    Wpp [4, Cout, 4*Cin] (packs.pack_conv_up2).  Returns [rows*2IH*2IW, Cout].  W9: the layer's ordinary 9-tap pack - the
     fall-back when the launch is declined (SKG_E_UNSUPPORTED)."""
     _f16(X, Wpp, bias)
     Cin, Cout = X.shape[1], Wpp.shape[1]
@@ -459,7 +459,7 @@ def conv_up2(X: torch.Tensor, Wpp: torch.Tensor, rows: int, IH: int, IW: int, ou
 
 def conv_up2_hilo(X2: torch.Tensor, Wpp3: torch.Tensor, rows: int, IH: int, IW: int, out: Pair, *, bias=None, W9x2=None):
     """Accuracy mode: conv_up2 on the pair buffer X2 = [x_hi | x_lo] ([rows*IH*IW, 2C]) with (hi, lo) pre-summed weights
-    Wpp3 [4, Cout, 4 * 3C] (unet.pack_conv_up2_hilo); the output is the pair `out`.  W9x2 (a callable returning the layer's 9-tap
+    Wpp3 [4, Cout, 4 * 3C] (packs.pack_conv_up2_hilo); the output is the pair `out`.  W9x2 (a callable returning the layer's 9-tap
     [W | W] pack, built on first use): the fall-back when the polyphase launch is declined (an operand >= 2 GiB - the pair
     buffer is twice as wide, so the limit comes at half the batch size of conv_up2's): ADVICE r4."""
     _f16(X2, Wpp3, bias, out.hi, out.lo)
@@ -506,7 +506,7 @@ def gemm_rows(A: torch.Tensor, B: torch.Tensor, out: torch.Tensor, seg_rows: int
 
 def conv4x4s2(X: torch.Tensor, W16: torch.Tensor, rows: int, IH: int, IW: int, out: Optional[torch.Tensor] = None, *, bias=None, W9T=None):
     """4 x 4 stride-2 convolution, padding 1 (the data gradient of conv_up2).  X [rows*IH*IW, Cin] (view), W16 [Cout, 16*Cin]
-    (unet.pack_conv_up2_dgrad).  Returns [rows*(IH/2)*(IW/2), Cout]."""
+    (packs.pack_conv_up2_dgrad).  Returns [rows*(IH/2)*(IW/2), Cout]."""
     _f16(X, W16, bias)
     Cin, Cout = X.shape[1], W16.shape[0]
     assert W16.shape == (Cout, 16 * Cin) and W16.is_contiguous() and X.shape[0] == rows * IH * IW

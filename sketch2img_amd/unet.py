@@ -9,8 +9,7 @@ modules/pipeline.py:159.  Weights use the diffusers state_dict key names.
 Data layout in HBM: every activation is fp16, token-major [rows*H*W, C]; rows are
 ordered [uncond rows of all samples ; cond rows of all samples] so the backward pass (cond rows
 only - the uncond gradient is discarded at modules/pipeline.py:159) works on the contiguous second
-half of every stashed buffer.  Weight packs: Linear / 1x1 conv [N][K]; conv3x3
-[Cout][ky][kx][Cin]; each has a second "dgrad" pack (transposed / tap-flipped) for backward.
+half of every stashed buffer.  Weight-pack layouts: packs.py (which packs a net has: HipUNet._pack / _pack_hp here).
 
 Work hoisted out of the per-step loop because it does not depend on the latent:
   * the time-embedding MLP and every ResnetBlock2D.time_emb_proj(silu(temb)) -> one fused bias
@@ -28,6 +27,9 @@ import torch
 
 from . import ops
 from .config import UNetConfig, up_block_plan
+from .packs import (CIN_PAD, COUT_PAD, CTX_PAD, EPS_SEED_LD, _h, _pad_vec, pack_conv, pack_conv_dgrad,      # noqa: F401 (re-exported)
+                    pack_conv_up2, pack_conv_up2_dgrad, pack_conv_up2_hilo, pack_conv_wino, pack_ff_block, pack_xattn_kv,
+                    pack_xattn_weights)
 
 _GN_FROM_PRODUCER = os.environ.get("SKG_GN_PRODUCER", "1") != "0"      # A/B switches (bench.py on one box)
 _GEGLU_KEEP = os.environ.get("SKG_GEGLU_KEEP", "1") != "0"
@@ -54,11 +56,6 @@ _WINO_GN = os.environ.get("SKG_WINO_GN", "1") != "0"                # the GroupN
 # pair output through the output transform, the K-doubled shortcut as a pair GEMM whose result is the residual
 _HP_WINO = os.environ.get("SKG_HP_WINO", "0") != "0"
 
-CIN_PAD = 64      # latent channels padded to one 64-deep K tile of the LDS-DMA implicit-GEMM conv
-COUT_PAD = 8      # conv_out / conv_in-dgrad output channels padded to the 8-channel store granule
-CTX_PAD = 8       # text tokens padded to a multiple of 8 (77 -> 80)
-EPS_SEED_LD = 32  # columns of the d eps seed of backward_eps: one 32-deep K step of conv_out's data gradient (4 valid channels)
-
 
 # spatial sizes inside the UNet are (height, width) pairs; every level keeps the latent's aspect ratio (both sides are
 # multiples of 2^(levels - 1), so each stride-2 level halves both exactly and each nearest-2x upsample lands on the skip's size)
@@ -74,102 +71,6 @@ def _side(sz: Tuple[int, int]):
     """What a tap / residual sample carries as its size: the side s of a square map (the form of square evaluations),
     else (height, width)."""
     return sz[0] if sz[0] == sz[1] else sz
-
-
-def _h(t: torch.Tensor, dev) -> torch.Tensor:
-    return t.detach().to(device=dev, dtype=torch.float16).contiguous()
-
-
-def pack_conv(w: torch.Tensor, dev, cin_pad: int = 0, cout_pad: int = 0) -> torch.Tensor:
-    """[Cout,Cin,3,3] -> [Cout(+pad)][ky][kx][Cin(+pad)] flattened to [Cout, 9*Cin]."""
-    co, ci = w.shape[:2]
-    p = w.permute(0, 2, 3, 1)
-    if cin_pad > ci:
-        p = torch.nn.functional.pad(p, (0, cin_pad - ci))
-    if cout_pad > co:
-        p = torch.nn.functional.pad(p, (0, 0, 0, 0, 0, 0, 0, cout_pad - co))
-    return _h(p.reshape(p.shape[0], -1), dev)
-
-
-def pack_conv_wino(w: torch.Tensor, dev, dgrad: bool = False) -> torch.Tensor:
-    """Winograd F(2x2, 3x3) weight pack of a 3x3 convolution [Cout, Cin, 3, 3] -> U [Cout, 16 * Cin] fp16: U = G g G^T per (cout, cin),
-    formed in fp32 and rounded once; component c = 4 i + j at columns [c Cin, (c + 1) Cin) (ops.conv3x3_wino, csrc/wino.hip).
-    dgrad: the pack of the convolution's DATA GRADIENT - itself a 3x3 convolution with the taps flipped and in / out swapped."""
-    g = w.detach().to(device=dev, dtype=torch.float32)                   # (formed on the target device, elementwise: no BLAS call at pack time)
-    if dgrad:
-        g = g.flip(2, 3).transpose(0, 1)
-
-    def G3(a, b, c):                                                     # G = [[1, 0, 0], [.5, .5, .5], [.5, -.5, .5], [0, 0, 1]] applied along one axis
-        return a, 0.5 * (a + b + c), 0.5 * (a - b + c), c
-
-    rows = G3(g[:, :, 0, :], g[:, :, 1, :], g[:, :, 2, :])               # G g: 4 x [Cout, Cin, 3]
-    U = torch.stack([torch.stack(G3(r[:, :, 0], r[:, :, 1], r[:, :, 2]), 1) for r in rows], 1)      # (G g) G^T: [Cout, 4 (i), 4 (j), Cin]
-    return _h(U.reshape(U.shape[0], -1), dev)
-
-
-def pack_conv_dgrad(w: torch.Tensor, dev, cin_pad: int = 0, cout_pad: int = 0) -> torch.Tensor:
-    """dgrad pack: Wd[ci][ky'][kx'][co] = W[co][ci][2-ky'][2-kx'] -> [Cin, 9*Cout].
-    ``cin_pad`` pads the OUTPUT rows (the conv's input channels), ``cout_pad`` the contraction."""
-    co, ci = w.shape[:2]
-    p = w.flip(2, 3).permute(1, 2, 3, 0)
-    if cout_pad > co:
-        p = torch.nn.functional.pad(p, (0, cout_pad - co))
-    if cin_pad > ci:
-        p = torch.nn.functional.pad(p, (0, 0, 0, 0, 0, 0, 0, cin_pad - ci))
-    return _h(p.reshape(p.shape[0], -1), dev)
-
-
-def pack_conv_up2(w: torch.Tensor, dev) -> torch.Tensor:
-    """Polyphase pack of a 3x3 filter applied after a nearest 2x upsample (ops.conv_up2): [4 phases 2a+b][Cout][4 taps][Cin].
-    Output pixel (2i+a, 2j+b) reads low-res rows {i-1, i} (a = 0) or {i, i+1} (a = 1): the filter rows that land on one
-    low-res row are summed (fp32, one fp16 rounding), the same for columns."""
-    w = w.detach().float()
-    co, ci = w.shape[:2]
-    phases = []
-    for a in (0, 1):
-        rws = (w[:, :, 0], w[:, :, 1] + w[:, :, 2]) if a == 0 else (w[:, :, 0] + w[:, :, 1], w[:, :, 2])      # [co, ci, kx]
-        for b in (0, 1):
-            taps = []
-            for r in rws:
-                taps += [r[:, :, 0], r[:, :, 1] + r[:, :, 2]] if b == 0 else [r[:, :, 0] + r[:, :, 1], r[:, :, 2]]
-            phases.append(torch.stack(taps, 1).reshape(co, 4 * ci))                                            # [co][tap][ci]
-    return _h(torch.stack(phases, 0), dev)
-
-
-def pack_conv_up2_hilo(w: torch.Tensor, dev) -> torch.Tensor:
-    """Accuracy-mode polyphase pack (ops.conv_up2_hilo): the pre-summed weights of pack_conv_up2 kept as (hi, lo) fp16 pairs,
-    per phase and tap [W_hi | W_hi | W_lo] against the operand blocks [x_hi | x_lo | x_hi]: [4][Cout][4 taps][3 Cin]."""
-    w = w.detach().float()
-    co, ci = w.shape[:2]
-    phases = []
-    for a in (0, 1):
-        rws = (w[:, :, 0], w[:, :, 1] + w[:, :, 2]) if a == 0 else (w[:, :, 0] + w[:, :, 1], w[:, :, 2])      # [co, ci, kx]
-        for b in (0, 1):
-            taps = []
-            for r in rws:
-                taps += [r[:, :, 0], r[:, :, 1] + r[:, :, 2]] if b == 0 else [r[:, :, 0] + r[:, :, 1], r[:, :, 2]]
-            t = torch.stack(taps, 1)                                                                           # [co][tap][ci] fp32
-            hi = t.half()
-            lo = (t - hi.float()).half()
-            phases.append(torch.cat([hi, hi, lo], 2).reshape(co, 12 * ci))
-    return torch.stack(phases, 0).contiguous().to(dev)
-
-
-def pack_conv_up2_dgrad(w: torch.Tensor, dev) -> torch.Tensor:
-    """Data gradient of the polyphase upsample + conv (ops.conv4x4s2): [Cin][16 taps ky*4+kx][Cout], the transposed pre-summed
-    weights of pack_conv_up2.  dX[p] = sum over phases a and taps ty of Wpp[a][ty]^T dY[2 (p - oy(a, ty)) + a] with
-    oy(0, .) = (-1, 0), oy(1, .) = (0, +1): rows 2p - 1 .. 2p + 2 of dY, window row ky = 0..3 <-> (a, ty) = (1,1), (0,1), (1,0), (0,0)."""
-    w = w.detach().float()
-    co, ci = w.shape[:2]
-
-    def split(t, axis):          # 3 filter taps along `axis` -> the four window positions along that axis
-        t0, t1, t2 = t.unbind(axis)
-        return [t2, t1 + t2, t0 + t1, t0]      # ky = 0: (a=1, ty=1) = w2;  1: (0,1) = w1 + w2;  2: (1,0) = w0 + w1;  3: (0,0) = w0
-    taps = []
-    for r in split(w, 2):                                        # 4 x [co, ci, kx]
-        taps += split(r, 2)                                      # 16 x [co, ci], order ky * 4 + kx
-    p = torch.stack(taps, 0)                                     # [16, co, ci]
-    return _h(p.permute(2, 0, 1).reshape(ci, 16 * co), dev)
 
 
 UP2_POLYPHASE = os.environ.get("SKG_UP2_POLY", "1") != "0"      # A/B switch (bench.py on one box)
@@ -201,113 +102,6 @@ UP2_SMALL_MAPS = os.environ.get("SKG_UP2_SMALL", "1") != "0"    # A/B: polyphase
 UP2_DGRAD = os.environ.get("SKG_UP2_DGRAD", "1") != "0"         # A/B: the upsampler's backward as one 4 x 4 stride-2 convolution
 
 
-def pack_ff_block(w1: torch.Tensor, b1: torch.Tensor, w2: torch.Tensor, dev, w_proj: Optional[torch.Tensor] = None):
-    """Fragment-major pack of a GEGLU feed-forward (diffusers FeedForward: net.0.proj [2F, C] = value rows then gate rows,
-    net.2 [C, F]) for skg_ff_block_f16 (csrc/ffblock.hip): every 512-half piece is one MFMA A operand in lane order, so
-    the kernel fetches it with one LDS-DMA instruction and reads it with one conflict-free ds_read_b128.
-    Chunk c = hidden units 32c .. 32c+31:
-      40 W1 pieces (t, ks): t = value 0-15, value 16-31, gate 0-15, gate 16-31; [lane = 16 g + l][i] = W1[row(t, l)][32 ks + 8 g + i]
-      20 W2 pieces u:       [lane = 16 g + l][i] = W2[16 u + l][32 c + 16 (i >> 2) + 4 g + (i & 3)]
-    (the hidden-unit order of the second product is the accumulator layout of the first).
-    w_proj [C, C] (Transformer2DModel.proj_out, skg_ff_block_proj_f16): five more chunks j behind them whose first 40 pieces are
-      (t, ks): [lane = 16 g + l][i] = Wp[16 (4 j + t) + l][32 ks + 16 (i >> 2) + 4 g + (i & 3)]   (the block output's accumulator order)
-    and whose last 20 pieces are zeros.
-    Returns (pack fp16 [F/32 (+ 5), 60, 512], bias1 fp32 [F/32, 4, 16])."""
-    F2, C = w1.shape
-    F = F2 // 2
-    assert w2.shape == (C, F) and C % 32 == 0 and F % 32 == 0
-    nch, KS, NU = F // 32, C // 32, C // 16
-    # (host-side packing: the state dict may live on the device after a broadcast)
-    w1h, w2h, b1 = w1.detach().to("cpu", torch.float16), w2.detach().to("cpu", torch.float16), b1.detach().cpu()
-    rows = torch.stack([w1h[:F].reshape(nch, 2, 16, C), w1h[F:].reshape(nch, 2, 16, C)], 1)     # [c, val|gate, half, l, C]
-    rows = rows.reshape(nch, 4, 16, KS, 4, 8)                                                     # [c, t, l, ks, g, i]
-    p1 = rows.permute(0, 1, 3, 4, 2, 5).reshape(nch, 4 * KS, 512)                                 # [c, (t, ks), (g, l, i)]
-    w2r = w2h.reshape(NU, 16, nch, 2, 4, 4)                                                       # [u, l, c, i_hi, g, i_lo]
-    p2 = w2r.permute(2, 0, 4, 1, 3, 5).reshape(nch, NU, 512)                                      # [c, u, (g, l, i_hi, i_lo)]
-    pack = torch.cat([p1, p2], 1)
-    if w_proj is not None:
-        assert w_proj.shape == (C, C) and NU % 4 == 0
-        wp = w_proj.detach().to("cpu", torch.float16).reshape(NU, 16, KS, 2, 4, 4)             # [u, l, ks, i_hi, g, i_lo]
-        pp = wp.permute(0, 2, 4, 1, 3, 5).reshape(NU // 4, 4 * KS, 512)                        # [j, (t, ks), (g, l, i_hi, i_lo)]
-        pack = torch.cat([pack, torch.cat([pp, torch.zeros(NU // 4, NU, 512, dtype=torch.float16)], 1)], 0)
-    pack = pack.contiguous().to(dev)
-    b1h = b1.to(torch.float16).float()
-    bias1 = torch.stack([b1h[:F].reshape(nch, 2, 16), b1h[F:].reshape(nch, 2, 16)], 1).reshape(nch, 4, 16).contiguous().to(dev)
-    return pack, bias1
-
-
-def pack_xattn_weights(wq: torch.Tensor, wo: torch.Tensor, heads: int, dev):
-    """Fragment-major pack of attn2.to_q [C, C] and attn2.to_out.0 [C, C] for skg_xattn_block_f16 (csrc/xattn.hip), C = 320; per head h
-    the kernel's LDS image in pieces of 512 halves.
-    8 heads of 40 (SD1.5; head width padded to 48), 60 pieces:
-      30 Wq pieces (t, ks):  [lane = 16 g + l][i] = Wq[40 h + 16 t + l][32 ks + 8 g + i]         (rows 40..47 of the head: zeros)
-      Wo image (30 pieces):  20 K = 32 fragments  [lane][i] = Wo[16 u + l][40 h + 16 (i >> 2) + 4 g + (i & 3)]
-                             20 K = 16 fragments  [lane][i < 4] = Wo[16 u + l][40 h + 32 + 4 g + i]   (d >= 40: zeros)
-    5 heads of 64 (SD2.1), 80 pieces: 40 Wq pieces (t < 4, ks) as above, then 2 x 20 K = 32 fragments
-      [s][u]: [lane][i] = Wo[16 u + l][64 h + 32 s + 16 (i >> 2) + 4 g + (i & 3)].
-    Returns fp16 [heads, 60 | 80, 512]."""
-    C = wq.shape[0]
-    dh = C // heads
-    assert wq.shape == (C, C) and wo.shape == (C, C) and C == 320 and dh in (40, 64)
-    KS, NU = C // 32, C // 16
-    DP = 48 if dh == 40 else 64
-    NT = DP // 16
-    wqh, woh = wq.detach().to("cpu", torch.float16), wo.detach().to("cpu", torch.float16)      # host-side packing
-    out = []
-    for h in range(heads):
-        q = torch.zeros(DP, C, dtype=torch.float16)
-        q[:dh] = wqh[h * dh:(h + 1) * dh]
-        pq = q.reshape(NT, 16, KS, 4, 8).permute(0, 2, 3, 1, 4).reshape(NT * KS, 512)          # [t, ks][g, l, i]
-        o = torch.zeros(C, DP, dtype=torch.float16)
-        o[:, :dh] = woh[:, h * dh:(h + 1) * dh]
-        o32 = o[:, :32].reshape(NU, 16, 2, 4, 4).permute(0, 3, 1, 2, 4).reshape(-1)             # [u][g, l, i_hi, i_lo]
-        if dh == 40:
-            tail = o[:, 32:].reshape(NU, 16, 4, 4).permute(0, 2, 1, 3).reshape(-1)              # [u][g, l, i]
-        else:
-            tail = o[:, 32:].reshape(NU, 16, 2, 4, 4).permute(0, 3, 1, 2, 4).reshape(-1)        # the second K = 32 step: d 32..63
-        out.append(torch.cat([pq.reshape(-1), o32, tail]).reshape(-1, 512))
-    return torch.stack(out).contiguous().to(dev)
-
-
-def pack_xattn_kv(K: torch.Tensor, V: torch.Tensor, rows: int, Lp: int, L: int, heads: int) -> torch.Tensor:
-    """Fragment-major pack of the text keys / values of every batch row for skg_xattn_block_f16: K, V [rows * Lp, C] (what
-    prepare_context hoists per prompt), L <= 80 valid keys per row.  Per (row, head), pieces of 512 halves.
-    Head width 40 (16 pieces):
-      K image: 5 K = 32 fragments [lane = 16 g + l][i] = K[key 16 kt + l][40 h + 16 (i >> 2) + 4 g + (i & 3)], then 5 K = 16
-               fragments [lane][i < 4] = K[key 16 kt + l][40 h + 32 + 4 g + i]                                   (8 pieces)
-      V image: (dt, s) K = 32 fragments [lane][i] = V[key 32 s + 16 (i >> 2) + 4 g + (i & 3)][40 h + 16 dt + l], then 3 K = 16
-               fragments [lane][i < 4] = V[key 64 + 4 g + i][40 h + 16 dt + l]                                   (8 pieces)
-    Head width 64 (20 pieces): K image [s][kt] 2 x 5 K = 32 fragments (d = 64 h + 32 s + ...), V image (dt < 4, s) 8 K = 32 fragments
-    then 4 K = 16 fragments (2 pieces); no padding.
-    Keys >= L and head columns >= the head width are zeros.  Returns fp16 [rows, heads, 16 | 20, 512] on K's device."""
-    C = K.shape[1]
-    dh = C // heads
-    assert dh in (40, 64) and L <= 80 and K.shape == V.shape == (rows * Lp, C)
-    dev = K.device
-    DP = 48 if dh == 40 else 64
-    NT = DP // 16
-    k = torch.zeros(rows, heads, 80, DP, device=dev, dtype=torch.float16)
-    v = torch.zeros(rows, heads, 80, DP, device=dev, dtype=torch.float16)
-    k[:, :, :L, :dh] = K.reshape(rows, Lp, heads, dh)[:, :L].permute(0, 2, 1, 3)
-    v[:, :, :L, :dh] = V.reshape(rows, Lp, heads, dh)[:, :L].permute(0, 2, 1, 3)
-    R = rows * heads
-    k, v = k.reshape(R, 80, DP), v.reshape(R, 80, DP)
-    k32 = k[:, :, :32].reshape(R, 5, 16, 2, 4, 4).permute(0, 1, 4, 2, 3, 5).reshape(R, 5 * 512)      # [kt][g, l, i_hi, i_lo]
-    v32 = v[:, :64].reshape(R, 2, 2, 4, 4, NT, 16).permute(0, 5, 1, 3, 6, 2, 4).reshape(R, 2 * NT * 512)   # [dt, s][g, l, i_hi, i_lo]
-    v16 = v[:, 64:].reshape(R, 4, 4, NT, 16).permute(0, 3, 1, 4, 2).reshape(R, NT * 256)             # [dt][g, l, i]
-    if dh == 64:
-        k32b = k[:, :, 32:].reshape(R, 5, 16, 2, 4, 4).permute(0, 1, 4, 2, 3, 5).reshape(R, 5 * 512)
-        return torch.cat([k32, k32b, v32, v16], 1).reshape(rows, heads, 20, 512).contiguous()
-    k16 = k[:, :, 32:].reshape(R, 5, 16, 4, 4).permute(0, 1, 3, 2, 4).reshape(R, 5 * 256)            # [kt][g, l, i]
-    pad_k = torch.zeros(R, 4096 - 5 * 768, device=dev, dtype=torch.float16)
-    pad_v = torch.zeros(R, 4096 - 6 * 512 - 3 * 256, device=dev, dtype=torch.float16)
-    return torch.cat([k32, k16, pad_k, v32, v16, pad_v], 1).reshape(rows, heads, 16, 512).contiguous()
-
-
-def _pad_vec(v: torch.Tensor, n: int) -> torch.Tensor:
-    return torch.nn.functional.pad(v, (0, n - v.shape[0])) if n > v.shape[0] else v
-
-
 @dataclass
 class Stash:
     """Activations kept by a grad-enabled forward for the backward pass."""
@@ -333,12 +127,89 @@ class _Packs(dict):
         return dict.__contains__(self, k) or k in self.lazy
 
 
+def _hi(v):
+    """The fp16 tensor of a value of either representation (taps, stashes and hi-only operands carry it)."""
+    return v.hi if isinstance(v, ops.Pair) else v
+
+
+def _rows_of(v, m0: int, m1: int):
+    if isinstance(v, ops.Pair):
+        return ops.Pair(v.hi[m0:m1], v.lo[m0:m1], None if v.full is None else v.full[m0:m1])
+    return v[m0:m1]
+
+
+def _copy_up(src, dst, M1: int):
+    """Shared CFG front: the cond rows `src` (M1 of them, the second half of `dst`) -> the uncond rows of dst."""
+    if not isinstance(src, ops.Pair):
+        ops.batch_copy(src, M1, dst, M1, 1, M1)
+    elif src.full is not None and dst.full is not None:
+        ops.batch_copy(src.full, M1, dst.full, M1, 1, M1)
+    else:
+        ops.batch_copy(src.hi, M1, dst.hi, M1, 1, M1)
+        ops.batch_copy(src.lo, M1, dst.lo, M1, 1, M1)
+
+
+class _ConcatBuffers:
+    """torch.cat((h, skip)) of the up path without copies: the buffer [h | skip] of every up resnet is filled in place - the
+    down-path layer that produces a skip writes it straight into the right-hand columns (and keeps using that strided view as its
+    own output), the up-path layer that produces h into the left-hand ones.  Buffer u belongs to up block u // (layers + 1); the
+    skips are consumed in the reverse order of their production.  A buffer has the representation of its consumer: fp16 in the
+    plain zone, else the pair buffer [h_hi | skip_hi | h_lo | skip_lo] - every view handed out then is an ops.Pair inside it."""
+
+    def __init__(self, net: "HipUNet", rows: int, down_only: bool):
+        cfg = net.cfg
+        lpb1, rev = cfg.layers_per_block + 1, list(reversed(cfg.block_out_channels))
+        n = len(rev) * lpb1
+        self.ch_h = [rev[0] if u == 0 else (rev[u // lpb1 - 1] if u % lpb1 == 0 else rev[u // lpb1]) for u in range(n)]
+        self.pair = [not net._plain_up(u // lpb1) for u in range(n)]
+        self.bufs: List[Optional[torch.Tensor]] = [None] * n
+        self.skips: list = []                                # every skip produced so far (what down_only returns) ...
+        self.parts: List[Optional[ops.GNPartial]] = []       # ... and its GroupNorm partial sums, when its producer left them
+        self.rows, self.dev, self.down_only, self.groups = rows, net.dev, down_only, cfg.norm_groups
+
+    def _width(self, u: int) -> int:
+        return self.bufs[u].shape[1] // (2 if self.pair[u] else 1)
+
+    def skip_slot(self, ch_s: int, size: Tuple[int, int]):
+        """The columns of the concat buffer that will consume the skip produced next (None when down_only: no up path follows);
+        the producer's output goes to push()."""
+        if self.down_only:
+            return None
+        u = len(self.bufs) - 1 - len(self.skips)
+        ch, ct = self.ch_h[u], self.ch_h[u] + ch_s
+        buf = self.bufs[u] = torch.empty(self.rows * size[0] * size[1], (2 if self.pair[u] else 1) * ct, device=self.dev,
+                                         dtype=torch.float16)
+        return ops.Pair(buf[:, ch:ct], buf[:, ct + ch:]) if self.pair[u] else buf[:, ch:]
+
+    def push(self, skip, part):
+        self.skips.append(skip)
+        self.parts.append(part)
+
+    def h_slot(self, u: int):
+        """The left-hand columns of buffer u: where the up-path layer in front of it writes h."""
+        buf, ch, ct = self.bufs[u], self.ch_h[u], self._width(u)
+        return ops.Pair(buf[:, :ch], buf[:, ct:ct + ch]) if self.pair[u] else buf[:, :ch]
+
+    def whole(self, u: int):
+        buf, ct = self.bufs[u], self._width(u)
+        return ops.Pair(buf[:, :ct], buf[:, ct:], buf) if self.pair[u] else buf
+
+    def concat_part(self, u: int, hp):
+        """GroupNorm partial sums of buffer u for its consumer's norm1 - hp (of h) and the skip's, regrouped - or None where either
+        producer left none or the widths do not allow it."""
+        sp = self.parts.pop()
+        ch = self.ch_h[u]
+        if _GN_CONCAT and hp is not None and sp is not None and ops.gn_concat_ok(ch, self._width(u) - ch, self.groups, hp.groups, sp.groups):
+            return (hp, ch, sp)
+        return None
+
+
 class HipUNet:
     def __init__(self, cfg: UNetConfig, state_dict: Dict[str, torch.Tensor], device="cuda",
                  need_backward: bool = True, residual_fp32: bool = False):
         """residual_fp32: opt-in ACCURACY mode that meets north_star's <= 1e-3 max eps deviation from the fp32 reference: the
         residual stream and every conv output that feeds a norm or the residual sum are kept as (hi, lo) pairs of fp16 tensors
-        (~22 mantissa bits), see forward() / _forward_hp().  Where the stream itself is a matmul operand the pair is the K-doubled
+        (~22 mantissa bits), see forward().  Where the stream itself is a matmul operand the pair is the K-doubled
         operand (shortcuts, downsamplers, proj_out, conv_out) - EXCEPT the three nearest-2x upsampler convolutions, which read the hi
         part only and write a pair (round 5: SKG_HP_UP_TRIPLE=1 restores their pair operand; the declined-launch fall-back keeps the
         hi-only operand too).  Guided steps work: the pair forward stashes the hi activations and the ordinary backward runs on them."""
@@ -349,7 +220,10 @@ class HipUNet:
         self.W: Dict[str, torch.Tensor] = _Packs()
         self.hp_norm_pairs: set = set()
         nb = len(cfg.block_out_channels)
-        self.hp_plain_levels = max(0, min(HP_PLAIN_LEVELS, nb - 1)) if residual_fp32 else 0
+        # the zone: how many of the outermost resolution levels (level of down_blocks.i = i, of mid_block = nb - 1, of up_blocks.i =
+        # nb - 1 - i) carry (hi, lo) pairs; the deeper levels - every level in the default mode, the HP_PLAIN_LEVELS deepest in the
+        # accuracy mode - run the fp16 kernels
+        self.pair_levels = nb - max(0, min(HP_PLAIN_LEVELS, nb - 1)) if residual_fp32 else 0
         self._pack(state_dict)
         if residual_fp32:
             assert all(c % 64 == 0 for c in cfg.block_out_channels), \
@@ -362,17 +236,23 @@ class HipUNet:
         self.inject: Optional[Callable] = None      # set by modules.*_guided_attn.SatMixin
 
     def _hp_plain(self, name: str) -> bool:
-        """Accuracy mode: does this module (state-dict prefix) run the default fp16 kernels (HP_PLAIN_LEVELS)?  Resolution level of
-        down_blocks.i = i, of mid_block = nb - 1, of up_blocks.i = nb - 1 - i; plain iff level >= nb - hp_plain_levels."""
-        if not self.residual_fp32 or self.hp_plain_levels == 0:
-            return not self.residual_fp32
-        nb, pl = len(self.cfg.block_out_channels), self.hp_plain_levels
+        """Does this module (state-dict prefix) run the default fp16 kernels?  Every one in the default mode; in the accuracy mode the
+        blocks of the plain zone (HP_PLAIN_LEVELS), nothing outside the blocks (conv_in, conv_norm_out, conv_out)."""
+        if not self.residual_fp32:
+            return True
         part = name.split(".")
         if part[0] == "down_blocks":
-            return int(part[1]) >= nb - pl
+            return self._plain_down(int(part[1]))
         if part[0] == "up_blocks":
-            return int(part[1]) <= pl - 1
-        return part[0] == "mid_block"
+            return self._plain_up(int(part[1]))
+        return part[0] == "mid_block" and self._plain_up(0)
+
+    def _plain_down(self, i: int) -> bool:
+        return i >= self.pair_levels
+
+    def _plain_up(self, i: int) -> bool:
+        """up block i - and mid_block, which shares the level of up block 0"""
+        return len(self.cfg.block_out_channels) - 1 - i >= self.pair_levels
 
     # ------------------------------------------------------------------ packing
     def _pack(self, sd):
@@ -823,36 +703,32 @@ class HipUNet:
                 ops.gemm(ggc, W[t + ".ff.net.2.weight"], p3[M0:], bias=W[t + ".ff.net.2.bias"], residual=p2[M0:])
         else:
             a3, st3 = ops.layernorm(p2, W[t + ".norm3.weight"], W[t + ".norm3.bias"], want_stats=True)
-        if ffb:
-            pass
-        elif not keep and C % 64 == 0:        # no backward will follow: gate inside the GEMM epilogue (half the bytes)
-            f = None
-            gg = ops.gemm(a3, W[t + ".ff.net.0.proj.weight"], bias=W[t + ".ff.net.0.proj.bias"], geglu=True)
-        elif C % 64 == 0 and rows % 2 == 0:
-            # guided step: only the cond half (second half of the rows) is differentiated, so only it needs the
-            # pre-activation f; the uncond half takes the fused-GEGLU GEMM (a fifth of the bytes of GEMM + gate kernel)
-            M0 = (rows // 2) * HW
-            gg = torch.empty(rows * HW, 4 * C, device=x.device, dtype=torch.float16)
-            ops.gemm(a3[:M0], W[t + ".ff.net.0.proj.weight"], bias=W[t + ".ff.net.0.proj.bias"], geglu=True, out=gg[:M0])
-            # cond rows: the same fused epilogue also stores the pre-activation the gate's backward needs
-            if _GEGLU_KEEP:
-                _, f = ops.gemm_geglu_keep(a3[M0:], W[t + ".ff.net.0.proj.weight"], W[t + ".ff.net.0.proj.bias"], out=gg[M0:])
+            if not keep and C % 64 == 0:        # no backward will follow: gate inside the GEMM epilogue (half the bytes)
+                f = None
+                gg = ops.gemm(a3, W[t + ".ff.net.0.proj.weight"], bias=W[t + ".ff.net.0.proj.bias"], geglu=True)
+            elif C % 64 == 0 and rows % 2 == 0:
+                # guided step: only the cond half (second half of the rows) is differentiated, so only it needs the
+                # pre-activation f; the uncond half takes the fused-GEGLU GEMM (a fifth of the bytes of GEMM + gate kernel)
+                M0 = (rows // 2) * HW
+                gg = torch.empty(rows * HW, 4 * C, device=x.device, dtype=torch.float16)
+                ops.gemm(a3[:M0], W[t + ".ff.net.0.proj.weight"], bias=W[t + ".ff.net.0.proj.bias"], geglu=True, out=gg[:M0])
+                # cond rows: the same fused epilogue also stores the pre-activation the gate's backward needs
+                if _GEGLU_KEEP:
+                    _, f = ops.gemm_geglu_keep(a3[M0:], W[t + ".ff.net.0.proj.weight"], W[t + ".ff.net.0.proj.bias"], out=gg[M0:])
+                else:
+                    f = ops.gemm(a3[M0:], W[t + ".ff.net.0.proj.weight"], bias=W[t + ".ff.net.0.proj.bias"])
+                    ops.geglu(f, out=gg[M0:], interleaved=True)
             else:
-                f = ops.gemm(a3[M0:], W[t + ".ff.net.0.proj.weight"], bias=W[t + ".ff.net.0.proj.bias"])
-                ops.geglu(f, out=gg[M0:], interleaved=True)
-        else:
-            f = ops.gemm(a3, W[t + ".ff.net.0.proj.weight"], bias=W[t + ".ff.net.0.proj.bias"])
-            gg = ops.geglu(f, interleaved=True)
-            f = f[(rows // 2) * HW:]
-        if not ffb:
+                f = ops.gemm(a3, W[t + ".ff.net.0.proj.weight"], bias=W[t + ".ff.net.0.proj.bias"])
+                gg = ops.geglu(f, interleaved=True)
+                f = f[(rows // 2) * HW:]
             p3 = ops.gemm(gg, W[t + ".ff.net.2.weight"], bias=W[t + ".ff.net.2.bias"], residual=p2)
-        if ffp:
-            pass
-        elif want_part and self._gn_from_producer(rows, HW, C):
-            out, opart = ops.gemm(p3, W[p + ".proj_out.weight"], out, bias=W[p + ".proj_out.bias"], residual=x,
-                                  gn_stats=(HW, cfg.norm_groups))
-        else:
-            out = ops.gemm(p3, W[p + ".proj_out.weight"], out, bias=W[p + ".proj_out.bias"], residual=x)
+        if not ffp:
+            if want_part and self._gn_from_producer(rows, HW, C):
+                out, opart = ops.gemm(p3, W[p + ".proj_out.weight"], out, bias=W[p + ".proj_out.bias"], residual=x,
+                                      gn_stats=(HW, cfg.norm_groups))
+            else:
+                out = ops.gemm(p3, W[p + ".proj_out.weight"], out, bias=W[p + ".proj_out.bias"], residual=x)
         if keep:
             # half: the tensors of the text-independent part hold the cond rows only (r1 == rows // 2)
             # (`half` is derived from what each tensor actually holds - r1 rows or all of them - whatever the injector did, so that
@@ -896,6 +772,43 @@ class HipUNet:
             raise NotImplementedError(f"non-square latents {sz}: both sides must be multiples of {f}")
 
     # ------------------------------------------------------------------ forward
+    def _conv_gn(self, x, wkey: str, bkey: str, rows: int, sz: Tuple[int, int], mode: int, out):
+        """A convolution whose output may leave GroupNorm partial sums behind: -> (out, the sums or None).  out: an fp16 view, a
+        Pair (the pair epilogue), or None (a fresh fp16 tensor); the sums come with it where the level of the OUTPUT takes its
+        statistics from the producers (_gn_from_producer)."""
+        W = self.W
+        osz = _half(sz) if mode == ops.CONV_S2 else sz
+        hi, lo = (out.hi, out.lo) if isinstance(out, ops.Pair) else (out, None)
+        gn = self.cfg.norm_groups if self._gn_from_producer(rows, osz[0] * osz[1], W[wkey].shape[0]) else None
+        res = ops.conv3x3(x, W[wkey], rows, *sz, mode, out=hi, bias=W[bkey], gn_groups=gn, out_lo=lo)
+        o, part = res if gn is not None else (res, None)
+        return (o if lo is None else out), part
+
+    def _upsample(self, p: str, h, rows: int, sz: Tuple[int, int], out):
+        """The nearest-2x upsampler convolution `p` of an up block: h (fp16: the block lies in the plain zone, or a Pair) -> out (the
+        `h` columns of the next level's first concat buffer: fp16 inside the plain zone, else a Pair)."""
+        W, wk, b = self.W, p + ".weight", self.W[p + ".bias"]
+        if not isinstance(out, ops.Pair):
+            # polyphase: 16 instead of 36 tap-products per low-res pixel (four launches; one grid on the small maps)
+            if (wk + ":pp") in W and (UP2_SMALL_MAPS or (rows * sz[0] * sz[1] // 128) * (h.shape[1] // 160) >= 200):
+                return ops.conv_up2(h, W[wk + ":pp"], rows, *sz, out=out, bias=b, W9=W[wk])
+            return ops.conv3x3(h, W[wk], rows, *sz, ops.CONV_UP2, out=out, bias=b)
+        pair_in = isinstance(h, ops.Pair)      # (leaving the plain zone: h is fp16 and the hi-only launch is the natural one)
+        if (not pair_in or not HP_UP_TRIPLE) and (wk + ":pp") in W and (wk + ":pp3") not in W:
+            try:
+                ops.conv_up2_pairout(_hi(h), W[wk + ":pp"], rows, *sz, out, bias=b)
+            except ops.SkgError as e:      # declined (an operand >= 2 GiB): the 9-tap gather form on the SAME hi-only operand
+                if e.rc != -2:               # (ADVICE r5: both routes of the mode must see the same operand; pair output either way)
+                    raise
+                ops.conv3x3(_hi(h), W[wk], rows, *sz, ops.CONV_UP2, out=out.hi, out_lo=out.lo, bias=b)
+        elif not pair_in:
+            ops.conv3x3(h, W[wk], rows, *sz, ops.CONV_UP2, out=out.hi, out_lo=out.lo, bias=b)
+        elif (wk + ":pp3") in W:      # polyphase, K axis [x_hi | x_lo | x_hi] . [W_hi | W_hi | W_lo]: 12 instead of 18 tap-products
+            ops.conv_up2_hilo(self._full_of(h), W[wk + ":pp3"], rows, *sz, out, bias=b, W9x2=lambda: self._w9x2(wk))
+        else:
+            ops.conv3x3(self._full_of(h), W[wk + ":2"], rows, *sz, ops.CONV_UP2, out=out.hi, out_lo=out.lo, bias=b)
+        return out
+
     def forward(self, x32: torch.Tensor, t: int, rows: int, H: int, stash: Optional[Stash] = None,
                 want_taps: bool = True, want_eps: bool = True, down_only: bool = False, shared_input: bool = False,
                 on_taps: Optional[Callable] = None, W: Optional[int] = None):
@@ -913,120 +826,97 @@ class HipUNet:
 
         on_taps(taps): called as soon as the ninth tap exists (after the third up block), before the last up block and
         conv_out are launched - the guidance branch (LGP + backward-to-input) depends on nothing later, so the sampler can put
-        it on a second stream while this one finishes eps (sampler.HipSampler.fork_guidance)."""
+        it on a second stream while this one finishes eps (sampler.HipSampler.fork_guidance).
+
+        One walk for both modes.  The blocks of the `pair_levels` outermost resolution levels (none in the default mode) carry the
+        residual stream as (hi, lo) pairs: the same graph, the same kernels for every contraction, pair-aware epilogues / norms
+        (skg_*_hilo), the same GroupNorm statistics from the producers' epilogues and the same shared CFG front; eps then is a pair
+        too.  The deeper levels - the plain zone - run the default kernels on fp16 tensors (their pairs buy ~4 % of what the mode's
+        pairs buy, tools/eps_decompose_stream.py): the stride-2 convolution that enters the zone reads the pair and writes fp16, the
+        upsampler that leaves it reads fp16 and writes a pair; skips produced inside the zone are consumed inside it (the U-Net's
+        skips connect equal resolutions).  Taps always carry the fp16 (hi) tensor."""
         sz = (H, H if W is None else W)
         cfg, W = self.cfg, self.W
         assert self.ctx is not None and self.ctx["rows"] == rows, "call prepare_context first"
         if sz[0] != sz[1]:
             self._check_rect(sz)
         self.prepare_timesteps([t])
-        if self.residual_fp32:
-            assert not down_only, "accuracy mode: the whole UNet (with or without a stash, with or without an injector)"
-            return self._forward_hp(x32, t, rows, H, want_taps, want_eps, stash, on_taps, shared_input, W=sz[1])
+        assert not (down_only and self.residual_fp32), "accuracy mode: the whole UNet (with or without a stash, with or without an injector)"
         if stash is not None:
             stash.misc.update(rows=rows, H=H, W=sz[1])
         tb = self.tbias[int(t)]
         boc = cfg.block_out_channels
-        nb = len(boc)
-        # torch.cat((h, skip)) of the up path without copies: the buffer [h | skip] of every up resnet exists from the
-        # start; the down-path layer that produces a skip writes it straight into the right-hand columns (and keeps
-        # using that strided view as its own output), the up-path layer that produces h into the left-hand ones.
-        lpb1 = cfg.layers_per_block + 1
-        rev = list(reversed(boc))
-        n_skips = 1 + sum(cfg.layers_per_block + (1 if i < nb - 1 else 0) for i in range(nb))
-        cats: List[Optional[torch.Tensor]] = [None] * (nb * lpb1)
-        ch_h = [rev[0] if u == 0 else (rev[u // lpb1 - 1] if u % lpb1 == 0 else rev[u // lpb1]) for u in range(nb * lpb1)]
-
-        def skip_slot(ch_s: int, size: int):
-            """Right-hand columns of the concat buffer that will consume the skip produced next."""
-            u = n_skips - 1 - len(skips)
-            if down_only:
-                return None
-            cats[u] = torch.empty(rows * size[0] * size[1], ch_h[u] + ch_s, device=self.dev, dtype=torch.float16)
-            return cats[u][:, ch_h[u]:]
-
-        skips: List[torch.Tensor] = []
-        skip_parts: List[Optional[ops.GNPartial]] = []       # partial sums of each skip, when its producer left them
-        G = cfg.norm_groups
+        nb, lpb, lpb1 = len(boc), cfg.layers_per_block, cfg.layers_per_block + 1
+        cats = _ConcatBuffers(self, rows, down_only)
+        blocks = lambda plain: (self._res_fwd, self._tr_fwd) if plain else (self._res_fwd_hp, self._tr_fwd_hp)
         # hp: GroupNorm partial sums of h left behind by the kernel that produced it, whenever the next consumer of h is a
         # GroupNorm of the 64 x 64 / 32 x 32 levels (None otherwise: concatenated inputs, small maps)
-        shared = shared_input and rows % 2 == 0 and rows >= 2 and not down_only and nb > 1 and cfg.layers_per_block >= 1
+        shared = shared_input and rows % 2 == 0 and rows >= 2 and not down_only and nb > 1 and lpb >= 1
         cur = sz
-        HW = sz[0] * sz[1]
+        res, tr = blocks(self._plain_down(0))
         if shared:
-            S1, M1 = rows // 2, (rows // 2) * HW
-            slot = skip_slot(boc[0], sz)                          # the skip of conv_in, all rows
-            if self._gn_from_producer(S1, HW, boc[0]):
-                h1, hp1 = ops.conv3x3(x32[M1:], W["conv_in.weight"], S1, *sz, out=slot[M1:], bias=W["conv_in.bias"], gn_groups=G)
-            else:
-                h1, hp1 = ops.conv3x3(x32[M1:], W["conv_in.weight"], S1, *sz, out=slot[M1:], bias=W["conv_in.bias"]), None
-            ops.batch_copy(h1, M1, slot, M1, 1, M1)
-            skips.append(slot)
-            skip_parts.append(self._dup_partial(hp1))
-            x_full = torch.empty(rows * HW, boc[0], device=self.dev, dtype=torch.float16)
-            h1, hp1 = self._res_fwd("down_blocks.0.resnets.0", h1, S1, cur, tb, stash, out=x_full[M1:], xpart=hp1,
-                                    want_part=True, half=True)
-            ops.batch_copy(h1, M1, x_full, M1, 1, M1)
-            h, hp = self._tr_fwd("down_blocks.0.attentions.0", h1, rows, cur, cfg.num_heads[0], stash,
-                                 out=skip_slot(boc[0], cur), xpart=hp1, want_part=0 < cfg.layers_per_block - 1,
-                                 shared=True, x_full=x_full)
-            skips.append(h)
-            skip_parts.append(hp)
-        elif self._gn_from_producer(rows, HW, boc[0]):
-            h, hp = ops.conv3x3(x32, W["conv_in.weight"], rows, *sz, out=skip_slot(boc[0], sz), bias=W["conv_in.bias"],
-                                gn_groups=G)
+            S1, M1 = rows // 2, (rows // 2) * sz[0] * sz[1]
+            slot = cats.skip_slot(boc[0], sz)                      # the skip of conv_in, all rows
+            hc = _rows_of(slot, M1, 2 * M1)
+            _, hp1 = self._conv_gn(x32[M1:], "conv_in.weight", "conv_in.bias", S1, sz, ops.CONV_S1, hc)
+            _copy_up(hc, slot, M1)
+            cats.push(slot, self._dup_partial(hp1))
+            x_full = self._pair(rows * sz[0] * sz[1], boc[0]) if isinstance(slot, ops.Pair) else \
+                torch.empty(rows * sz[0] * sz[1], boc[0], device=self.dev, dtype=torch.float16)
+            h1, hp1 = res("down_blocks.0.resnets.0", hc, S1, cur, tb, stash, out=_rows_of(x_full, M1, 2 * M1), xpart=hp1,
+                          want_part=True, half=True)
+            _copy_up(h1, x_full, M1)
+            h, hp = tr("down_blocks.0.attentions.0", h1, rows, cur, cfg.num_heads[0], stash, out=cats.skip_slot(boc[0], cur),
+                       xpart=hp1, want_part=0 < lpb - 1, shared=True, x_full=x_full)
         else:
-            h, hp = ops.conv3x3(x32, W["conv_in.weight"], rows, *sz, out=skip_slot(boc[0], sz), bias=W["conv_in.bias"]), None
-        if not shared:
-            skips.append(h)
-            skip_parts.append(hp)
+            h, hp = self._conv_gn(x32, "conv_in.weight", "conv_in.bias", rows, sz, ops.CONV_S1, cats.skip_slot(boc[0], sz))
+        cats.push(h, hp)
         taps_down = []
         for i in range(nb):
-            for j in range(cfg.layers_per_block):
+            plain = self._plain_down(i)
+            res, tr = blocks(plain)
+            for j in range(lpb):
                 if shared and i == 0 and j == 0:
                     continue                                      # done above, once for both halves
+                rp, ap = f"down_blocks.{i}.resnets.{j}", f"down_blocks.{i}.attentions.{j}"
                 if i < nb - 1:
-                    h, hp = self._res_fwd(f"down_blocks.{i}.resnets.{j}", h, rows, cur, tb, stash, xpart=hp, want_part=True)
+                    h, hp = res(rp, h, rows, cur, tb, stash, xpart=hp, want_part=True)
                     # the block's last transformer feeds the downsampling conv, the others the next resnet's norm1
-                    h, hp = self._tr_fwd(f"down_blocks.{i}.attentions.{j}", h, rows, cur, cfg.num_heads[i], stash,
-                                         out=skip_slot(boc[i], cur), xpart=hp, want_part=j < cfg.layers_per_block - 1)
+                    h, hp = tr(ap, h, rows, cur, cfg.num_heads[i], stash, out=cats.skip_slot(boc[i], cur), xpart=hp,
+                               want_part=j < lpb - 1)
                 else:
-                    h, hp = self._res_fwd(f"down_blocks.{i}.resnets.{j}", h, rows, cur, tb, stash,
-                                          out=skip_slot(boc[i], cur), xpart=hp, want_part=True)
-                skips.append(h)
-                skip_parts.append(hp)
+                    h, hp = res(rp, h, rows, cur, tb, stash, out=cats.skip_slot(boc[i], cur), xpart=hp, want_part=True)
+                cats.push(h, hp)
             if i < nb - 1:
+                # (its output - a skip - has the representation of the next level: entering the plain zone, the pair is the
+                # K-doubled operand and the output fp16)
                 p = f"down_blocks.{i}.downsamplers.0.conv"
-                half = _half(cur)
-                if self._gn_from_producer(rows, half[0] * half[1], boc[i]):
-                    h, hp = ops.conv3x3(h, W[p + ".weight"], rows, *cur, ops.CONV_S2, out=skip_slot(boc[i], half),
-                                        bias=W[p + ".bias"], gn_groups=G)
-                else:
-                    h, hp = ops.conv3x3(h, W[p + ".weight"], rows, *cur, ops.CONV_S2, out=skip_slot(boc[i], half),
-                                        bias=W[p + ".bias"]), None
-                cur = half
-                skips.append(h)
-                skip_parts.append(hp)
+                o = cats.skip_slot(boc[i], _half(cur))
+                x, wkey = (h, p + ".weight") if plain else (self._full_of(h), p + ".weight:2")
+                h, hp = self._conv_gn(x, wkey, p + ".bias", rows, cur, ops.CONV_S2, o)
+                cur = _half(cur)
+                cats.push(h, hp)
             if i < 3:
-                taps_down.append((h, _side(cur)))
+                taps_down.append((_hi(h), _side(cur)))
         if down_only:
             # modules/sketch_encoder.py:39-98: the forward stops after the down path and returns the per-block
             # tuples of residual samples ((tensor [rows*s*s, C], s), ...) - what SatMixin.set_res_samples consumes
             # (on a non-square map: (tensor [rows*sh*sw, C], (sh, sw)))
             out, k = [], 1
             for i in range(nb):
-                n = cfg.layers_per_block + (1 if i < nb - 1 else 0)
+                n = lpb + (1 if i < nb - 1 else 0)
                 lv = lambda i: _side((sz[0] >> i, sz[1] >> i))
-                sizes = [lv(i)] * cfg.layers_per_block + ([lv(i + 1)] if i < nb - 1 else [])
-                out.append(tuple((skips[k + j], sizes[j]) for j in range(n)))
+                sizes = [lv(i)] * lpb + ([lv(i + 1)] if i < nb - 1 else [])
+                out.append(tuple((cats.skips[k + j], sizes[j]) for j in range(n)))
                 k += n
             return out
-        h, hp = self._res_fwd("mid_block.resnets.0", h, rows, cur, tb, stash, xpart=hp, want_part=True)
-        tap_r0 = (h, _side(cur))
-        h, hp = self._tr_fwd("mid_block.attentions.0", h, rows, cur, cfg.num_heads[-1], stash, xpart=hp, want_part=True)
-        tap_at = (h, _side(cur))
-        h, _ = self._res_fwd("mid_block.resnets.1", h, rows, cur, tb, stash, out=cats[0][:, :ch_h[0]], xpart=hp)
-        tap_r1 = (h, _side(cur))
+        res, tr = blocks(self._plain_up(0))
+        h, hp = res("mid_block.resnets.0", h, rows, cur, tb, stash, xpart=hp, want_part=True)
+        tap_r0 = (_hi(h), _side(cur))
+        h, hp = tr("mid_block.attentions.0", h, rows, cur, cfg.num_heads[-1], stash, xpart=hp, want_part=True)
+        tap_at = (_hi(h), _side(cur))
+        h, _ = res("mid_block.resnets.1", h, rows, cur, tb, stash, out=cats.h_slot(0), xpart=hp)
+        tap_r1 = (_hi(h), _side(cur))
         hp = None
         taps_up = []
         rev_heads = tuple(reversed(cfg.num_heads))
@@ -1034,61 +924,65 @@ class HipUNet:
         for i in range(nb):
             if i > last_needed:
                 break
+            res, tr = blocks(self._plain_up(i))
             for j in range(lpb1):
                 u = i * lpb1 + j
-                skips.pop()                                   # already sits in cats[u][:, ch_h[u]:]
-                sp = skip_parts.pop() if skip_parts else None
-                cat = cats[u]
+                rp, ap = f"up_blocks.{i}.resnets.{j}", f"up_blocks.{i}.attentions.{j}"
                 # norm1 of a resnet that reads [h | skip]: both halves' producers may have left their sums behind
-                cpart = None
-                if _GN_CONCAT and hp is not None and sp is not None and ops.gn_concat_ok(ch_h[u], cat.shape[1] - ch_h[u], G, hp.groups, sp.groups):
-                    cpart = (hp, ch_h[u], sp)
+                # (regrouped where the widths allow, else the norm makes its own pass)
+                cpart = cats.concat_part(u, hp)
                 # where this layer's output goes: the next concat buffer of the same block, else a fresh tensor
-                nxt = cats[u + 1][:, :ch_h[u + 1]] if j < lpb1 - 1 else None
+                nxt = cats.h_slot(u + 1) if j < lpb1 - 1 else None
                 if i > 0:
-                    # (norm1 reads the concatenation: regrouped producer sums where the widths allow, else its own pass)
-                    h, hp = self._res_fwd(f"up_blocks.{i}.resnets.{j}", cat, rows, cur, tb, stash, xpart=cpart, want_part=True)
+                    h, hp = res(rp, cats.whole(u), rows, cur, tb, stash, xpart=cpart, want_part=True)
                     # the transformer's output goes to conv_norm_out (the very last one) or into the next concatenation,
                     # whose GroupNorm regroups its sums with the skip's; the block's last output feeds the upsampling conv
                     keep = (want_eps and i == nb - 1 and j == lpb1 - 1) or j < lpb1 - 1
-                    h, hp = self._tr_fwd(f"up_blocks.{i}.attentions.{j}", h, rows, cur, rev_heads[i], stash, out=nxt,
-                                         xpart=hp, want_part=keep)
+                    h, hp = tr(ap, h, rows, cur, rev_heads[i], stash, out=nxt, xpart=hp, want_part=keep)
                 else:
-                    h, hp = self._res_fwd(f"up_blocks.{i}.resnets.{j}", cat, rows, cur, tb, stash, out=nxt, xpart=cpart,
-                                          want_part=j < lpb1 - 1)
+                    h, hp = res(rp, cats.whole(u), rows, cur, tb, stash, out=nxt, xpart=cpart, want_part=j < lpb1 - 1)
             if i < nb - 1:
-                p = f"up_blocks.{i}.upsamplers.0.conv"
-                u = (i + 1) * lpb1
-                # polyphase: 16 instead of 36 tap-products per low-res pixel (four launches; one grid on the small maps)
-                if (p + ".weight:pp") in W and (UP2_SMALL_MAPS or (rows * cur[0] * cur[1] // 128) * (h.shape[1] // 160) >= 200):
-                    h = ops.conv_up2(h, W[p + ".weight:pp"], rows, *cur, out=cats[u][:, :ch_h[u]], bias=W[p + ".bias"], W9=W[p + ".weight"])
-                else:
-                    h = ops.conv3x3(h, W[p + ".weight"], rows, *cur, ops.CONV_UP2, out=cats[u][:, :ch_h[u]],
-                                    bias=W[p + ".bias"])
+                h = self._upsample(f"up_blocks.{i}.upsamplers.0.conv", h, rows, cur, cats.h_slot((i + 1) * lpb1))
                 hp = None              # (the next concatenation's widths do not line up with 32 groups per half)
                 cur = _dbl(cur)
             if i < 3:
-                taps_up.append((h, _side(cur)))
+                taps_up.append((_hi(h), _side(cur)))
                 if i == 2 and on_taps is not None:
                     on_taps(taps_down + [tap_at, tap_r0, tap_r1] + taps_up)
         eps = None
-        if want_eps:
-            n, nst = ops.groupnorm(h, rows, cur[0] * cur[1], cfg.norm_groups, 1e-5, W["conv_norm_out.weight"],
-                                   W["conv_norm_out.bias"], True, partial=hp)
+        HW = cur[0] * cur[1]
+        if want_eps and isinstance(h, ops.Pair):
+            # conv_norm_out -> SiLU -> conv_out: both the normalised activation (the K-doubled operand [hi | lo] . [W | W]) and eps
+            # itself (a (hi, lo) pair in one [M, 2 * 8] buffer, combined in fp32 by the CFG / scheduler kernel) keep fp32 accuracy -
+            # their fp16 roundings would reach eps one to one (2.8e-4 relative each)
+            n = self._pair(rows * HW, boc[0])
+            ops.groupnorm_hilo(h.hi, h.lo, rows, HW, cfg.norm_groups, 1e-5, W["conv_norm_out.weight"], W["conv_norm_out.bias"], True,
+                               out=n.hi, out_lo=n.lo, partial=hp)
+            eps = self._pair(rows * HW, COUT_PAD)
+            ops.conv3x3(n.full, W["conv_out.weight:2"], rows, *cur, out=eps.hi, out_lo=eps.lo, bias=W["conv_out.bias"])
+        elif want_eps:
+            n, nst = ops.groupnorm(h, rows, HW, cfg.norm_groups, 1e-5, W["conv_norm_out.weight"], W["conv_norm_out.bias"], True,
+                                   partial=hp)
             eps = ops.conv3x3(n, W["conv_out.weight"], rows, *cur, bias=W["conv_out.bias"])
             if stash is not None:      # what backward_eps reads (references only: no extra launch)
                 stash.misc.update(out_h=h, out_st=nst)
         taps = taps_down + [tap_at, tap_r0, tap_r1] + taps_up
-        if stash is not None:
-            stash.misc.update(rows=rows, H=H, W=sz[1])
         return eps, (taps if want_taps else None)
 
-
-    # ------------------------------------------------------------------ accuracy mode (residual_fp32)
-    _Pair = ops.Pair      # (hi, lo) views with one pitch; `full` = the [M, 2C] tensor [hi | lo] when the two are its halves
-
+    # ------------------------------------------------------------------ modules of the pair zone (accuracy mode, residual_fp32)
     def _pair(self, M: int, C: int) -> ops.Pair:
         return ops.Pair.empty(M, C, self.dev)
+
+    @staticmethod
+    def _full_of(pv: ops.Pair) -> torch.Tensor:
+        """[hi | lo] as ONE operand: the pair's own buffer, or a packed copy when it lives inside a concat buffer."""
+        if pv.full is not None:
+            return pv.full
+        C = pv.hi.shape[1]
+        buf = torch.empty(pv.hi.shape[0], 2 * C, device=pv.hi.device, dtype=torch.float16)
+        ops.axpby(pv.hi, None, out=buf[:, :C])
+        ops.axpby(pv.lo, None, out=buf[:, C:])
+        return buf
 
     def _gn_hp(self, x, rows, HW, eps, name, silu, partial=None):
         """-> (normalised fp16 tensor, statistics [rows, groups, 2]); partial: the producer's epilogue sums (see ops.groupnorm_hilo).
@@ -1101,7 +995,7 @@ class HipUNet:
         return ops.groupnorm_hilo(x.hi, x.lo, rows, HW, self.cfg.norm_groups, eps, self.W[name + ".weight"],
                                   self.W[name + ".bias"], silu, want_stats=True, partial=partial)
 
-    def _res_fwd_hp(self, p, x, rows, sz, tb, out=None, full_of=None, stash=None, xpart=None, want_part=False, half=False):
+    def _res_fwd_hp(self, p, x, rows, sz, tb, stash: Optional[Stash] = None, out=None, xpart=None, want_part=False, half=False):
         """As _res_fwd on pairs.  Returns (out pair, GroupNorm partial sums of out or None)."""
         W = self.W
         G = self.cfg.norm_groups
@@ -1132,7 +1026,7 @@ class HipUNet:
             # Winograd conv2, pair output; its residual is the block input pair or the K-doubled shortcut GEMM's pair output
             if (p + ".conv_shortcut.weight") in W:
                 sc = self._pair(M, Cout)
-                xf = x.full if x.full is not None else full_of(x, x.hi.shape[1])
+                xf = self._full_of(x)
                 ops.gemm(xf, W[p + ".conv_shortcut.weight:2"], out=sc.hi, out_lo=sc.lo, bias=W[p + ".conv_shortcut.bias"])
             else:
                 sc = x
@@ -1141,7 +1035,7 @@ class HipUNet:
                 return out, None
         if (p + ".conv2.weight:sc2") in W:
             # conv2 + the K-doubled shortcut [x_hi | x_lo] . [W_sc | W_sc] in one launch, pair output
-            xf = x.full if x.full is not None else full_of(x, x.hi.shape[1])
+            xf = self._full_of(x)
             wsc2 = w2n if n2_pair else W[p + ".conv2.weight:sc2"]
             try:
                 if want_part and fuse:
@@ -1157,7 +1051,7 @@ class HipUNet:
                 w2n = w2n[:, : 9 * n2.shape[1]]
         if (p + ".conv_shortcut.weight") in W:
             sc = self._pair(M, Cout)                                 # the stream as a matmul operand: [hi | lo] . [W | W]
-            xf = x.full if x.full is not None else full_of(x, x.hi.shape[1])
+            xf = self._full_of(x)
             ops.gemm(xf, W[p + ".conv_shortcut.weight:2"], out=sc.hi, out_lo=sc.lo, bias=W[p + ".conv_shortcut.bias"])
         else:
             sc = x
@@ -1172,7 +1066,8 @@ class HipUNet:
                         residual=sc.hi, residual_lo=sc.lo)
         return out, opart
 
-    def _tr_fwd_hp(self, p, x, rows, sz, heads, out=None, stash=None, xpart=None, want_part=False, shared=False, x_full=None):
+    def _tr_fwd_hp(self, p, x, rows, sz, heads, stash: Optional[Stash] = None, out=None, xpart=None, want_part=False, shared=False,
+                   x_full=None):
         """As _tr_fwd on pairs (shared / x_full: the shared CFG front, see _tr_fwd: x holds the cond rows only)."""
         W = self.W
         HW, M = sz[0] * sz[1], rows * sz[0] * sz[1]
@@ -1193,16 +1088,15 @@ class HipUNet:
         qkv = ops.gemm(a1, W[t + ".attn1.qkv"])
         o1, lse1 = ops.attn_fwd(qkv[:, :C], qkv[:, C:2 * C], qkv[:, 2 * C:], r1, heads, HW, HW, HW, dh, scale,
                                 want_lse=True, v_rows=True)
-        P = HipUNet._Pair
         p1_full = self._pair(M, C) if shared else None
-        p1 = P(p1_full.hi[M1:], p1_full.lo[M1:], p1_full.full[M1:]) if shared else self._pair(M, C)
+        p1 = _rows_of(p1_full, M1, M) if shared else self._pair(M, C)
         ops.gemm(o1, W[t + ".attn1.to_out.0.weight"], out=p1.hi, out_lo=p1.lo, bias=W[t + ".attn1.to_out.0.bias"],
                  residual=pin.hi, residual_lo=pin.lo)
         x_c, p1_c = x, p1
         if self.inject is not None:
             if shared and getattr(self.inject, "halves_equal", False):
                 nf = self._pair(M, C)
-                p1 = self.inject(t, p1, rows, HW, heads, cond_only=True, out=P(nf.hi[M1:], nf.lo[M1:], nf.full[M1:]))
+                p1 = self.inject(t, p1, rows, HW, heads, cond_only=True, out=_rows_of(nf, M1, M))
                 p1_full = nf
             else:
                 if shared:                                    # the injected K / V differ between the halves: diverge here
@@ -1245,6 +1139,18 @@ class HipUNet:
         ffb = _FF_BLOCK and (t + ".ff.pack") in W and (not keep or (rows % 2 == 0 and _FF_KEEP))
         f = None
         ffp = ffb and _FF_PROJ and _FF_PROJ_HP and (t + ".ff.packp") in W and HW % 128 == 0
+
+        def keep_entry(st3, f):
+            # the stash entry of a guided step (the backward differentiates the fp16 - hi - values)
+            # half: which tensors of the text-independent part hold the cond rows only - derived from their shapes, as _tr_fwd does
+            # (with an injector the shared front ends earlier: x / p1 / q2 are full size while gst .. lse1 are not)
+            own = r1 != rows and self.inject is None
+            ent = dict(x=(x_c if own else x).hi, gst=gst, pin=pin.hi, st1=st1, qkv=qkv, o1=o1, lse1=lse1, p1=(p1_c if own else p1).hi,
+                       st2=st2, q2=q2_c if own else q2)
+            half = self._stash_half(ent, r1, rows, HW)
+            half = tuple(k for k in half if k not in xk_half) + xk_half
+            stash.tr[p] = dict(ent, o2=o2, lse2=lse2, p2=p2.hi, st3=st3, f=f, sz=sz, heads=heads, half=half)
+
         if ffp:
             # ... with proj_out (on the pair p3 = hi + lo: W . hi + W . lo on the same fragments) and the outer residual pair in the
             # same launch (skg_ff_block_proj_f16_hilo): the K-doubled proj_out GEMM and the [M, 2C] round trip of p3 disappear
@@ -1254,12 +1160,7 @@ class HipUNet:
                                                  W[t + ".ff.net.2.bias"], W[p + ".proj_out.bias"], x, out=out, want_stats=keep,
                                                  keep_from=(rows // 2) * HW if keep else None, gn=gn)
             if keep:
-                own = r1 != rows and self.inject is None
-                ent = dict(x=(x_c if own else x).hi, gst=gst, pin=pin.hi, st1=st1, qkv=qkv, o1=o1, lse1=lse1, p1=(p1_c if own else p1).hi,
-                           st2=st2, q2=q2_c if own else q2)
-                half = self._stash_half(ent, r1, rows, HW)
-                half = tuple(k for k in half if k not in xk_half) + xk_half
-                stash.tr[p] = dict(ent, o2=o2, lse2=lse2, p2=p2.hi, st3=st3, f=f, sz=sz, heads=heads, half=half)
+                keep_entry(st3, f)
             return out, opart
         if ffb:
             # C = 320: norm3 -> FF1 -> gate -> FF2 + residual in ONE row-local launch on the pair (guided steps: the same launch
@@ -1272,32 +1173,22 @@ class HipUNet:
                 p3 = ops.ff_block(p2, *ffargs)
         else:
             a3, st3 = ops.layernorm_hilo(p2.hi, p2.lo, W[t + ".norm3.weight"], W[t + ".norm3.bias"], want_stats=True)
-        if ffb:
-            pass
-        elif keep and C % 64 == 0 and rows % 2 == 0:     # guided step: the cond half's gate also keeps its pre-activation
-            M0 = (rows // 2) * HW
-            gg = torch.empty(M, 4 * C, device=self.dev, dtype=torch.float16)
-            ops.gemm(a3[:M0], W[t + ".ff.net.0.proj.weight"], bias=W[t + ".ff.net.0.proj.bias"], geglu=True, out=gg[:M0])
-            _, f = ops.gemm_geglu_keep(a3[M0:], W[t + ".ff.net.0.proj.weight"], W[t + ".ff.net.0.proj.bias"], out=gg[M0:])
-        elif C % 64 == 0:
-            gg = ops.gemm(a3, W[t + ".ff.net.0.proj.weight"], bias=W[t + ".ff.net.0.proj.bias"], geglu=True)
-        else:
-            ff = ops.gemm(a3, W[t + ".ff.net.0.proj.weight"], bias=W[t + ".ff.net.0.proj.bias"])
-            gg = ops.geglu(ff, interleaved=True)
-            f = ff[(rows // 2) * HW:]
-        if keep:
-            # half: which tensors of the text-independent part hold the cond rows only - derived from their shapes, as _tr_fwd does
-            # (with an injector the shared front ends earlier: x / p1 / q2 are full size while gst .. lse1 are not)
-            own = r1 != rows and self.inject is None
-            ent = dict(x=(x_c if own else x).hi, gst=gst, pin=pin.hi, st1=st1, qkv=qkv, o1=o1, lse1=lse1, p1=(p1_c if own else p1).hi,
-                       st2=st2, q2=q2_c if own else q2)
-            half = self._stash_half(ent, r1, rows, HW)
-            half = tuple(k for k in half if k not in xk_half) + xk_half
-            stash.tr[p] = dict(ent, o2=o2, lse2=lse2, p2=p2.hi, st3=st3, f=f, sz=sz, heads=heads, half=half)
-        if not ffb:
+            if keep and C % 64 == 0 and rows % 2 == 0:     # guided step: the cond half's gate also keeps its pre-activation
+                M0 = (rows // 2) * HW
+                gg = torch.empty(M, 4 * C, device=self.dev, dtype=torch.float16)
+                ops.gemm(a3[:M0], W[t + ".ff.net.0.proj.weight"], bias=W[t + ".ff.net.0.proj.bias"], geglu=True, out=gg[:M0])
+                _, f = ops.gemm_geglu_keep(a3[M0:], W[t + ".ff.net.0.proj.weight"], W[t + ".ff.net.0.proj.bias"], out=gg[M0:])
+            elif C % 64 == 0:
+                gg = ops.gemm(a3, W[t + ".ff.net.0.proj.weight"], bias=W[t + ".ff.net.0.proj.bias"], geglu=True)
+            else:
+                ff = ops.gemm(a3, W[t + ".ff.net.0.proj.weight"], bias=W[t + ".ff.net.0.proj.bias"])
+                gg = ops.geglu(ff, interleaved=True)
+                f = ff[(rows // 2) * HW:]
             p3 = self._pair(M, C)
             ops.gemm(gg, W[t + ".ff.net.2.weight"], out=p3.hi, out_lo=p3.lo, bias=W[t + ".ff.net.2.bias"],
                      residual=p2.hi, residual_lo=p2.lo)
+        if keep:
+            keep_entry(st3, f)
         out = out or self._pair(M, C)
         opart = None
         if want_part and self._gn_from_producer(rows, HW, C):
@@ -1307,234 +1198,6 @@ class HipUNet:
             ops.gemm(p3.full, W[p + ".proj_out.weight:2"], out=out.hi, out_lo=out.lo, bias=W[p + ".proj_out.bias"],
                      residual=x.hi, residual_lo=x.lo)
         return out, opart
-
-    def _forward_hp(self, x32, t, rows, H, want_taps, want_eps, stash=None, on_taps=None, shared_input=False, W=None):
-        """The forward of forward() with the residual stream as (hi, lo) pairs; the same graph, the same kernels for every
-        contraction, pair-aware epilogues / norms (skg_*_hilo), the same GroupNorm statistics from the producers' epilogues and
-        the same shared CFG front.  Concatenations [h | skip] are pair buffers [h_hi | skip_hi | h_lo | skip_lo], filled in
-        place by their producers.  Round 6: the blocks of the `hp_plain_levels` deepest resolution levels run the DEFAULT kernels
-        on plain fp16 tensors (their pairs buy ~4 % of what the mode's pairs buy, tools/eps_decompose_stream.py): the stride-2
-        convolution that enters the zone reads the pair and writes fp16, the upsampler that leaves it reads fp16 and writes a pair;
-        skips produced inside the zone are consumed inside it (the U-Net's skips connect equal resolutions)."""
-        sz = (H, H if W is None else W)
-        cfg, W = self.cfg, self.W
-        if stash is not None:
-            stash.misc.update(rows=rows, H=H, W=sz[1])
-        tb = self.tbias[int(t)]
-        boc = cfg.block_out_channels
-        nb = len(boc)
-        G = cfg.norm_groups
-        lpb1 = cfg.layers_per_block + 1
-        rev = list(reversed(boc))
-        n_skips = 1 + sum(cfg.layers_per_block + (1 if i < nb - 1 else 0) for i in range(nb))
-        ch_h = [rev[0] if u == 0 else (rev[u // lpb1 - 1] if u % lpb1 == 0 else rev[u // lpb1]) for u in range(nb * lpb1)]
-        cats: List[Optional[torch.Tensor]] = [None] * (nb * lpb1)
-        P = HipUNet._Pair
-        n_made = [0]
-        skip_parts: List[Optional[ops.GNPartial]] = []       # partial sums of each skip, when its producer left them
-        pl = self.hp_plain_levels
-        plain_up = lambda i: i <= pl - 1                      # up block i (and concat buffer u with u // lpb1 == i) is in the plain zone
-        plain_down = lambda i: i >= nb - pl                   # down block i
-
-        def skip_slot(ch_s: int, size: int):
-            """The view inside the concat buffer that will consume the skip produced next: a pair view, or - the consumer is a
-            block of the plain zone - the fp16 right-hand columns."""
-            u = n_skips - 1 - n_made[0]
-            n_made[0] += 1
-            ct = ch_h[u] + ch_s
-            if plain_up(u // lpb1):
-                cats[u] = torch.empty(rows * size[0] * size[1], ct, device=self.dev, dtype=torch.float16)
-                return cats[u][:, ch_h[u]:]
-            cats[u] = torch.empty(rows * size[0] * size[1], 2 * ct, device=self.dev, dtype=torch.float16)
-            return P(cats[u][:, ch_h[u]:ct], cats[u][:, ct + ch_h[u]:], None)
-
-        def full_of(pv, C):
-            """[hi | lo] as ONE operand: the pair's own buffer, or a packed copy when it lives inside a concat buffer."""
-            if pv.full is not None:
-                return pv.full
-            buf = torch.empty(pv.hi.shape[0], 2 * C, device=self.dev, dtype=torch.float16)
-            ops.axpby(pv.hi, None, out=buf[:, :C])
-            ops.axpby(pv.lo, None, out=buf[:, C:])
-            return buf
-
-        def rows_of(pv, m0, m1):
-            return P(pv.hi[m0:m1], pv.lo[m0:m1], None if pv.full is None else pv.full[m0:m1])
-
-        def conv_pair(x, wkey, bkey, size, mode, o, r=rows, want=False):
-            """conv with a pair output (+ the GroupNorm sums of its hi part where the level takes them from the producers)"""
-            osz = _half(size) if mode == ops.CONV_S2 else size
-            if want and self._gn_from_producer(r, osz[0] * osz[1], o.hi.shape[1]):
-                return ops.conv3x3(x, W[wkey], r, *size, mode, out=o.hi, out_lo=o.lo, bias=W[bkey], gn_groups=G)[1]
-            ops.conv3x3(x, W[wkey], r, *size, mode, out=o.hi, out_lo=o.lo, bias=W[bkey])
-            return None
-
-        def conv_plain(x, wkey, bkey, size, mode, o):
-            """conv with an fp16 output (the plain zone; forward()'s form)"""
-            osz = _half(size) if mode == ops.CONV_S2 else size
-            if self._gn_from_producer(rows, osz[0] * osz[1], o.shape[1]):
-                return ops.conv3x3(x, W[wkey], rows, *size, mode, out=o, bias=W[bkey], gn_groups=G)[1]
-            ops.conv3x3(x, W[wkey], rows, *size, mode, out=o, bias=W[bkey])
-            return None
-
-        hi_of = lambda v: v.hi if isinstance(v, ops.Pair) else v
-        shared = shared_input and rows % 2 == 0 and rows >= 2 and nb > 1 and cfg.layers_per_block >= 1
-        cur = sz
-        taps_down = []
-        h = skip_slot(boc[0], sz)
-        if shared:
-            S1, M1 = rows // 2, (rows // 2) * sz[0] * sz[1]
-            hc = rows_of(h, M1, 2 * M1)
-            hp1 = conv_pair(x32[M1:], "conv_in.weight", "conv_in.bias", sz, ops.CONV_S1, hc, r=S1, want=True)
-            ops.batch_copy(hc.hi, M1, h.hi, M1, 1, M1)
-            ops.batch_copy(hc.lo, M1, h.lo, M1, 1, M1)
-            skip_parts.append(self._dup_partial(hp1))
-            x_full = self._pair(rows * sz[0] * sz[1], boc[0])
-            h1, hp1 = self._res_fwd_hp("down_blocks.0.resnets.0", hc, S1, cur, tb, out=rows_of(x_full, M1, 2 * M1), full_of=full_of,
-                                       stash=stash, xpart=hp1, want_part=True, half=True)
-            ops.batch_copy(h1.full, M1, x_full.full, M1, 1, M1)
-            h, hp = self._tr_fwd_hp("down_blocks.0.attentions.0", h1, rows, cur, cfg.num_heads[0], out=skip_slot(boc[0], cur),
-                                    stash=stash, xpart=hp1, want_part=0 < cfg.layers_per_block - 1, shared=True, x_full=x_full)
-            skip_parts.append(hp)
-        else:
-            hp = conv_pair(x32, "conv_in.weight", "conv_in.bias", sz, ops.CONV_S1, h, want=True)
-            skip_parts.append(hp)
-        for i in range(nb):
-            for j in range(cfg.layers_per_block):
-                if shared and i == 0 and j == 0:
-                    continue
-                rp, ap = f"down_blocks.{i}.resnets.{j}", f"down_blocks.{i}.attentions.{j}"
-                if plain_down(i):      # forward()'s form on fp16 tensors
-                    if i < nb - 1:
-                        h, hp = self._res_fwd(rp, h, rows, cur, tb, stash, xpart=hp, want_part=True)
-                        h, hp = self._tr_fwd(ap, h, rows, cur, cfg.num_heads[i], stash, out=skip_slot(boc[i], cur), xpart=hp,
-                                             want_part=j < cfg.layers_per_block - 1)
-                    else:
-                        h, hp = self._res_fwd(rp, h, rows, cur, tb, stash, out=skip_slot(boc[i], cur), xpart=hp, want_part=True)
-                elif i < nb - 1:
-                    h, hp = self._res_fwd_hp(rp, h, rows, cur, tb, full_of=full_of, stash=stash, xpart=hp, want_part=True)
-                    h, hp = self._tr_fwd_hp(ap, h, rows, cur, cfg.num_heads[i], out=skip_slot(boc[i], cur), stash=stash, xpart=hp,
-                                            want_part=j < cfg.layers_per_block - 1)
-                else:
-                    h, hp = self._res_fwd_hp(rp, h, rows, cur, tb, out=skip_slot(boc[i], cur), full_of=full_of, stash=stash, xpart=hp,
-                                             want_part=True)
-                skip_parts.append(hp)
-            if i < nb - 1:
-                p = f"down_blocks.{i}.downsamplers.0.conv"
-                o = skip_slot(boc[i], _half(cur))               # (a pair, or fp16 when the consumer - the same level of the up path - is plain)
-                if plain_down(i):
-                    hp = conv_plain(h, p + ".weight", p + ".bias", cur, ops.CONV_S2, o)
-                elif isinstance(o, ops.Pair):
-                    hp = conv_pair(full_of(h, boc[i]), p + ".weight:2", p + ".bias", cur, ops.CONV_S2, o, want=True)
-                else:                                         # entering the plain zone: the pair as K-doubled operand, fp16 out
-                    hp = conv_plain(full_of(h, boc[i]), p + ".weight:2", p + ".bias", cur, ops.CONV_S2, o)
-                h = o
-                cur = _half(cur)
-                skip_parts.append(hp)
-            if i < 3:
-                taps_down.append((hi_of(h), _side(cur)))
-        if pl > 0:
-            h, hp = self._res_fwd("mid_block.resnets.0", h, rows, cur, tb, stash, xpart=hp, want_part=True)
-            tap_r0 = (h, _side(cur))
-            h, hp = self._tr_fwd("mid_block.attentions.0", h, rows, cur, cfg.num_heads[-1], stash, xpart=hp, want_part=True)
-            tap_at = (h, _side(cur))
-            h, _ = self._res_fwd("mid_block.resnets.1", h, rows, cur, tb, stash, out=cats[0][:, :ch_h[0]], xpart=hp)
-            tap_r1 = (h, _side(cur))
-        else:
-            h, hp = self._res_fwd_hp("mid_block.resnets.0", h, rows, cur, tb, full_of=full_of, stash=stash, xpart=hp, want_part=True)
-            tap_r0 = (h.hi, _side(cur))
-            h, hp = self._tr_fwd_hp("mid_block.attentions.0", h, rows, cur, cfg.num_heads[-1], stash=stash, xpart=hp, want_part=True)
-            tap_at = (h.hi, _side(cur))
-            ct0 = cats[0].shape[1] // 2
-            h, _ = self._res_fwd_hp("mid_block.resnets.1", h, rows, cur, tb, out=P(cats[0][:, :ch_h[0]], cats[0][:, ct0:ct0 + ch_h[0]]),
-                                    stash=stash, xpart=hp)
-            tap_r1 = (h.hi, _side(cur))
-        hp = None
-        taps_up = []
-        rev_heads = tuple(reversed(cfg.num_heads))
-        last_needed = 2 if not want_eps else nb - 1
-        for i in range(nb):
-            if i > last_needed:
-                break
-            for j in range(lpb1):
-                u = i * lpb1 + j
-                sp = skip_parts.pop() if skip_parts else None
-                rp, ap = f"up_blocks.{i}.resnets.{j}", f"up_blocks.{i}.attentions.{j}"
-                if plain_up(i):        # forward()'s form
-                    cat = cats[u]
-                    cpart = None
-                    if _GN_CONCAT and hp is not None and sp is not None and ops.gn_concat_ok(ch_h[u], cat.shape[1] - ch_h[u], G, hp.groups, sp.groups):
-                        cpart = (hp, ch_h[u], sp)
-                    nxt = cats[u + 1][:, :ch_h[u + 1]] if j < lpb1 - 1 else None
-                    if i > 0:
-                        h, hp = self._res_fwd(rp, cat, rows, cur, tb, stash, xpart=cpart, want_part=True)
-                        h, hp = self._tr_fwd(ap, h, rows, cur, rev_heads[i], stash, out=nxt, xpart=hp, want_part=j < lpb1 - 1)
-                    else:
-                        h, hp = self._res_fwd(rp, cat, rows, cur, tb, stash, out=nxt, xpart=cpart, want_part=j < lpb1 - 1)
-                    continue
-                ct = cats[u].shape[1] // 2
-                cat = P(cats[u][:, :ct], cats[u][:, ct:], cats[u])
-                cpart = None
-                if _GN_CONCAT and hp is not None and sp is not None and ops.gn_concat_ok(ch_h[u], ct - ch_h[u], G, hp.groups, sp.groups):
-                    cpart = (hp, ch_h[u], sp)
-                nxt = None
-                if j < lpb1 - 1:
-                    ctn = cats[u + 1].shape[1] // 2
-                    nxt = P(cats[u + 1][:, :ch_h[u + 1]], cats[u + 1][:, ctn:ctn + ch_h[u + 1]])
-                if i > 0:
-                    h, hp = self._res_fwd_hp(rp, cat, rows, cur, tb, stash=stash, xpart=cpart, want_part=True)
-                    keepp = (want_eps and i == nb - 1 and j == lpb1 - 1) or j < lpb1 - 1
-                    h, hp = self._tr_fwd_hp(ap, h, rows, cur, rev_heads[i], out=nxt, stash=stash, xpart=hp, want_part=keepp)
-                else:
-                    h, hp = self._res_fwd_hp(rp, cat, rows, cur, tb, out=nxt, stash=stash, xpart=cpart, want_part=j < lpb1 - 1)
-            if i < nb - 1:
-                p = f"up_blocks.{i}.upsamplers.0.conv"
-                u = (i + 1) * lpb1
-                if plain_up(i + 1):    # inside the plain zone: forward()'s form
-                    o = cats[u][:, :ch_h[u]]
-                    if (p + ".weight:pp") in W and (UP2_SMALL_MAPS or (rows * cur[0] * cur[1] // 128) * (h.shape[1] // 160) >= 200):
-                        ops.conv_up2(h, W[p + ".weight:pp"], rows, *cur, out=o, bias=W[p + ".bias"], W9=W[p + ".weight"])
-                    else:
-                        ops.conv3x3(h, W[p + ".weight"], rows, *cur, ops.CONV_UP2, out=o, bias=W[p + ".bias"])
-                else:
-                    ctn = cats[u].shape[1] // 2
-                    o = P(cats[u][:, :ch_h[u]], cats[u][:, ctn:ctn + ch_h[u]])
-                    hin = hi_of(h)                            # (leaving the plain zone: h is fp16 and the hi-only launch is the natural one)
-                    if (plain_up(i) or not HP_UP_TRIPLE) and (p + ".weight:pp") in W and (p + ".weight:pp3") not in W:
-                        try:
-                            ops.conv_up2_pairout(hin, W[p + ".weight:pp"], rows, *cur, o, bias=W[p + ".bias"])
-                        except ops.SkgError as e:      # declined (an operand >= 2 GiB): the 9-tap gather form on the SAME hi-only operand
-                            if e.rc != -2:               # (ADVICE r5: both routes of the mode must see the same operand; pair output either way)
-                                raise
-                            ops.conv3x3(hin, W[p + ".weight"], rows, *cur, ops.CONV_UP2, out=o.hi, out_lo=o.lo, bias=W[p + ".bias"])
-                    elif plain_up(i):
-                        ops.conv3x3(hin, W[p + ".weight"], rows, *cur, ops.CONV_UP2, out=o.hi, out_lo=o.lo, bias=W[p + ".bias"])
-                    elif (p + ".weight:pp3") in W:      # polyphase, K axis [x_hi | x_lo | x_hi] . [W_hi | W_hi | W_lo]: 12 instead of 18 tap-products
-                        ops.conv_up2_hilo(full_of(h, h.hi.shape[1]), W[p + ".weight:pp3"], rows, *cur, o, bias=W[p + ".bias"],
-                                          W9x2=lambda p=p: self._w9x2(p + ".weight"))
-                    else:
-                        ops.conv3x3(full_of(h, h.hi.shape[1]), W[p + ".weight:2"], rows, *cur, ops.CONV_UP2, out=o.hi, out_lo=o.lo,
-                                    bias=W[p + ".bias"])
-                h = o
-                hp = None
-                cur = _dbl(cur)
-            if i < 3:
-                taps_up.append((hi_of(h), _side(cur)))
-                if i == 2 and on_taps is not None:
-                    on_taps(taps_down + [tap_at, tap_r0, tap_r1] + taps_up)
-        eps = None
-        if want_eps:
-            # conv_norm_out -> SiLU -> conv_out: both the normalised activation (the K-doubled operand [hi | lo] . [W | W]) and eps
-            # itself (a (hi, lo) pair in one [M, 2 * 8] buffer, combined in fp32 by the CFG / scheduler kernel) keep fp32 accuracy -
-            # their fp16 roundings would reach eps one to one (2.8e-4 relative each)
-            n = self._pair(rows * cur[0] * cur[1], boc[0])
-            ops.groupnorm_hilo(h.hi, h.lo, rows, cur[0] * cur[1], G, 1e-5, W["conv_norm_out.weight"], W["conv_norm_out.bias"], True,
-                               out=n.hi, out_lo=n.lo, partial=hp)
-            eps = self._pair(rows * cur[0] * cur[1], COUT_PAD)
-            ops.conv3x3(n.full, W["conv_out.weight:2"], rows, *cur, out=eps.hi, out_lo=eps.lo, bias=W["conv_out.bias"])
-        taps = taps_down + [tap_at, tap_r0, tap_r1] + taps_up
-        if stash is not None:
-            stash.misc.update(rows=rows, H=H, W=sz[1])
-        return eps, (taps if want_taps else None)
 
     # ------------------------------------------------------------------ modules, backward (cond rows)
     def _res_bwd(self, p, dout, S, st: dict, r0: Optional[int] = None):
