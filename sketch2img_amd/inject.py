@@ -25,6 +25,7 @@ import torch
 
 from . import ops
 from .config import UNetConfig
+from .unet import _fresh, _hi, _layernorm, _produce
 
 SKETCH_TOKENS = 257
 CLIP_DIM = 1024
@@ -152,16 +153,10 @@ class HipInjector:
                     ops.batch_copy(src, src.shape[0], dst, src.shape[0], 1, src.shape[0])
                 return out
             return h
-        if pair:
-            hp, h = h, h.hi
-            res = out or ops.Pair.empty(h.shape[0], h.shape[1], self.dev)
-            norm = lambda g, b: ops.layernorm_hilo(hp.hi, hp.lo, g, b)
-            # h + scale * conv1x1(o) in fp32 on the pair
-            last = lambda o, wc, bc: (ops.gemm(o, wc, out=res.hi, out_lo=res.lo, bias=bc, residual=hp.hi, residual_lo=hp.lo,
-                                               alpha=self.scale), res)[1]
-        else:
-            norm = lambda g, b: ops.layernorm(h, g, b)
-            last = lambda o, wc, bc: ops.gemm(o, wc, out, bias=bc, residual=h, alpha=self.scale)
+        norm = lambda g, b: _layernorm(h, g, b)
+        # h + scale * conv1x1(o), on a pair in fp32 (the result is a pair again)
+        res = _fresh(h, *_hi(h).shape) if pair and out is None else out
+        last = lambda o, wc, bc: _produce("gemm", o, wc, out=res, bias=bc, residual=h, alpha=self.scale)[0]
         w = self.W[path]
         C = w["C"]
         dh = C // heads

@@ -32,11 +32,10 @@ from .packs import (CIN_PAD, COUT_PAD, CTX_PAD, EPS_SEED_LD, _h, _pad_vec, pack_
                     pack_xattn_weights)
 
 _GN_FROM_PRODUCER = os.environ.get("SKG_GN_PRODUCER", "1") != "0"      # A/B switches (bench.py on one box)
-_GEGLU_KEEP = os.environ.get("SKG_GEGLU_KEEP", "1") != "0"
 _GN_CONCAT = os.environ.get("SKG_GN_CONCAT", "1") != "0"
 _FF_BLOCK = os.environ.get("SKG_FF_BLOCK", "1") != "0"              # fused feed-forward sub-block at C = 320 (csrc/ffblock.hip)
 _XATTN_BLOCK = os.environ.get("SKG_XATTN_BLOCK", "1") != "0"        # fused cross-attention sub-block at C = 320, 8 heads (csrc/xattn.hip)
-_FF_KEEP = os.environ.get("SKG_FF_KEEP", "1") != "0"                # ... also for the cond rows of a guided step (stashing launch)
+_FF_KEEP = os.environ.get("SKG_FF_KEEP", "1") != "0"                # ... also in a guided step (stashing launch; 0 = all rows unfused there)
 _XATTN_HEADS = (8,) if os.environ.get("SKG_XATTN_D64", "1") == "0" else (8, 5)     # head counts of the fused cross-attention launch at C = 320 (5 x 64: round 5)
 _XATTN_KEEP = os.environ.get("SKG_XATTN_KEEP", "1") != "0"          # the fused cross-attention launch also in guided steps (stashing launch)
 _XATTN_KEEP_HP = os.environ.get("SKG_XATTN_KEEP_HP", "1") != "0"    # ... and in the accuracy mode's guided steps (pairs)
@@ -147,6 +146,34 @@ def _copy_up(src, dst, M1: int):
     else:
         ops.batch_copy(src.hi, M1, dst.hi, M1, 1, M1)
         ops.batch_copy(src.lo, M1, dst.lo, M1, 1, M1)
+
+
+def _fresh(like, M: int, C: int):
+    """An uninitialised [M, C] value of `like`'s representation."""
+    if isinstance(like, ops.Pair):
+        return ops.Pair.empty(M, C, like.hi.device)
+    return torch.empty(M, C, device=like.device, dtype=torch.float16)
+
+
+def _produce(fn: str, *args, out=None, residual=None, gn: Optional[Tuple[int, int]] = None, **kw):
+    """ops.<fn> (gemm, conv3x3, conv3x3_sc, conv3x3_wino) with `out` / `residual` of either representation: a Pair goes in as
+    out= / out_lo= (residual= / residual_lo=), its pair epilogue.  gn = (HW, groups): the GroupNorm partial sums of the output come
+    with it.  -> (the output in the representation of `out`, a fresh fp16 tensor without one; the sums or None)."""
+    for name, v in (("out", out), ("residual", residual)):
+        if isinstance(v, ops.Pair):
+            kw[name], kw[name + "_lo"] = v.hi, v.lo
+        elif v is not None:
+            kw[name] = v
+    if gn is not None:
+        kw.update({"gn_stats": gn} if fn == "gemm" else {"gn_groups": gn[1]})
+    res = getattr(ops, fn)(*args, **kw)
+    o, part = res if gn is not None else (res, None)
+    return (out if isinstance(out, ops.Pair) else o), part
+
+
+def _layernorm(v, gamma, beta, **kw):
+    """LayerNorm of a value of either representation (a pair is normalised as hi + lo) -> fp16."""
+    return ops.layernorm_hilo(v.hi, v.lo, gamma, beta, **kw) if isinstance(v, ops.Pair) else ops.layernorm(v, gamma, beta, **kw)
 
 
 class _ConcatBuffers:
@@ -505,11 +532,12 @@ class HipUNet:
 
     def _conv_wino(self, key: str, x, rows: int, sz: Tuple[int, int], **kw):
         """The 3x3 convolution `key` (a weight name + ':wino' / ':winoT') by Winograd F(2x2, 3x3) when the pack exists and the launch is
-        large enough; None when the path does not take it (the caller runs the implicit GEMM)."""
+        large enough (out= / residual=: fp16 or Pair, see _produce); None when the path does not take it (the caller runs the
+        implicit GEMM)."""
         if not self._wino_ok(key, rows, sz):
             return None
         try:
-            return ops.conv3x3_wino(x, self.W[key], rows, *sz, **kw)
+            return _produce("conv3x3_wino", x, self.W[key], rows, *sz, **kw)[0]
         except ops.SkgError as e:      # declined (no room for the slabs in the stream's workspace)
             if e.rc != -2:
                 raise
@@ -517,8 +545,8 @@ class HipUNet:
 
     def _gn_conv_wino(self, nkey: str, wkey: str, x, rows: int, sz: Tuple[int, int], eps: float, **kw):
         """GroupNorm + SiLU `nkey` and the Winograd convolution `wkey` behind it with the norm writing the convolution's input transform
-        (ops.groupnorm_wino: no normalised tensor in memory).  -> (conv output, statistics), or None when either step declines (nothing
-        was consumed: the caller runs groupnorm and the convolution as before)."""
+        (ops.groupnorm_wino: no normalised tensor in memory; fp16 only).  -> (conv output, statistics), or None when either step
+        declines (nothing was consumed: the caller runs groupnorm and the convolution as before)."""
         if not _WINO_GN or not self._wino_ok(wkey, rows, sz):
             return None
         W = self.W
@@ -530,216 +558,213 @@ class HipUNet:
                 raise
             return None
 
+    def _norm(self, x, rows: int, HW: int, eps: float, name: str, silu: bool, partial=None, pair_out: bool = False):
+        """GroupNorm(+SiLU) `name` of x (fp16 or Pair) -> (normalised fp16 tensor, statistics [rows, groups, 2]); partial: the producer's
+        epilogue sums.  pair_out, or a norm listed in hp_norm_pairs (pair input only): the output is a pair too - an ops.Pair whose
+        .full is the K-doubled operand [hi | lo] of its consumer."""
+        args = (rows, HW, self.cfg.norm_groups, eps, self.W[name + ".weight"], self.W[name + ".bias"], silu)
+        if not isinstance(x, ops.Pair):
+            return ops.groupnorm(x, *args, partial=partial)
+        if not (pair_out or name in self.hp_norm_pairs):
+            return ops.groupnorm_hilo(x.hi, x.lo, *args, want_stats=True, partial=partial)
+        n = _fresh(x, *x.hi.shape)
+        _, st = ops.groupnorm_hilo(x.hi, x.lo, *args, out=n.hi, out_lo=n.lo, want_stats=True, partial=partial)
+        return n, st
+
+    def _operand(self, v, key: str, suffix: str):
+        """(A, B) of the contraction `key` that reads v: a pair is the K-doubled operand [hi | lo] against the [W | W] pack
+        `key + suffix` (':2' where the stream is the operand, ':n2' behind a norm with a pair output)."""
+        return (self._full_of(v), self.W[key + suffix]) if isinstance(v, ops.Pair) else (v, self.W[key])
+
+    def _shortcut(self, p: str, x, M: int, Cout: int):
+        """What conv2 of ResnetBlock p adds as its residual when the shortcut is not folded into its launch: the block input, or
+        conv_shortcut of it (x's representation)."""
+        if (p + ".conv_shortcut.weight") not in self.W:
+            return x
+        return _produce("gemm", *self._operand(x, p + ".conv_shortcut.weight", ":2"), out=_fresh(x, M, Cout),
+                        bias=self.W[p + ".conv_shortcut.bias"])[0]
+
     def _res_fwd(self, p, x, rows, sz, tb, stash: Optional[Stash], out=None, xpart=None, want_part=False, half=False):
-        """xpart: GroupNorm partial sums of x from its producer (or None).  Returns (out, partial sums of out or None):
+        """x: fp16, or a Pair in the accuracy mode's pair zone - the output (and conv1's, which feeds norm2) has its representation.
+        xpart: GroupNorm partial sums of x from its producer (or None).  Returns (out, partial sums of out or None):
         they are produced when want_part is set and the level takes its statistics from the producers.
         half: `rows` are the COND rows only (the shared CFG prefix, see forward): the stash says so."""
-        cfg, W = self.cfg, self.W
-        G, HW = cfg.norm_groups, sz[0] * sz[1]
-        Cout = W[p + ".conv1.weight"].shape[0]
+        W, pair = self.W, isinstance(x, ops.Pair)
+        G, HW, M = self.cfg.norm_groups, sz[0] * sz[1], rows * sz[0] * sz[1]
+        k1, k2 = p + ".conv1.weight", p + ".conv2.weight"
+        Cout = W[k1].shape[0]
         fuse = self._gn_from_producer(rows, HW, Cout)
-        # small maps: conv1 / conv2 by Winograd F(2x2, 3x3), the GroupNorm in front writing the input transform where its slice fits a workgroup
-        h1 = st1 = None
-        if not fuse and xpart is None:
-            got = self._gn_conv_wino(p + ".norm1", p + ".conv1.weight:wino", x, rows, sz, 1e-5, bias=tb[p])
-            if got is not None:
-                h1, st1 = got
+        # small maps (no statistics from the producers): conv1 / conv2 by Winograd F(2x2, 3x3) - in the pair zone under _HP_WINO only, and
+        # never with the norm in front writing the input transform (ops.groupnorm_wino has no pair input) or for a norm output that is a pair
+        wino1 = not fuse and (not pair or _HP_WINO)
+        h1 = st1 = part1 = None
+        if wino1 and not pair and xpart is None:
+            h1, st1 = self._gn_conv_wino(p + ".norm1", k1 + ":wino", x, rows, sz, 1e-5, bias=tb[p]) or (None, None)
         if h1 is None:
-            n1, st1 = ops.groupnorm(x, rows, HW, G, 1e-5, W[p + ".norm1.weight"], W[p + ".norm1.bias"], True, partial=xpart)
-            h1 = None if fuse else self._conv_wino(p + ".conv1.weight:wino", n1, rows, sz, bias=tb[p])
-        if h1 is not None:
-            part1 = None
-        elif fuse:
-            h1, part1 = ops.conv3x3(n1, W[p + ".conv1.weight"], rows, *sz, bias=tb[p], gn_groups=G)
-        else:
-            h1, part1 = ops.conv3x3(n1, W[p + ".conv1.weight"], rows, *sz, bias=tb[p]), None
-        opart = None
-        done = False
+            n1, st1 = self._norm(x, rows, HW, 1e-5, p + ".norm1", True, partial=xpart)
+            h1o = _fresh(x, M, Cout)
+            if wino1 and not isinstance(n1, ops.Pair):
+                h1 = self._conv_wino(k1 + ":wino", n1, rows, sz, out=h1o, bias=tb[p])
+            if h1 is None:
+                h1, part1 = _produce("conv3x3", *self._operand(n1, k1, ":n2"), rows, *sz, out=h1o, bias=tb[p], gn=(HW, G) if fuse else None)
+        out = _fresh(x, M, Cout) if out is None else out
+        ogn = (HW, G) if want_part and fuse else None
         has_sc = (p + ".conv_shortcut.weight") in W
-        wino2 = (self._wino_ok(p + ".conv2.weight:wino", rows, sz) and not (want_part and fuse) and (not has_sc or _WINO >= 2))
-        n2 = st2 = None
-        if wino2:
+        # (fp16: also a large map whose consumer folds no sums; a channel-changing block takes shortcut GEMM + Winograd from _WINO = 2 on)
+        wino2 = ((wino1 or not (pair or want_part)) and self._wino_ok(k2 + ":wino", rows, sz) and (pair or not has_sc or _WINO >= 2))
+        n2 = st2 = sc = opart = None
+        done = False
+        if wino2 and not pair:
             # Winograd conv2 with the block input - or the shortcut GEMM's output - as its residual
-            sc = ops.gemm(x, W[p + ".conv_shortcut.weight"], bias=W[p + ".conv_shortcut.bias"]) if has_sc else x
-            got = self._gn_conv_wino(p + ".norm2", p + ".conv2.weight:wino", h1, rows, sz, 1e-5, out=out, bias=W[p + ".conv2.bias"], residual=sc)
+            sc = self._shortcut(p, x, M, Cout)
+            got = self._gn_conv_wino(p + ".norm2", k2 + ":wino", h1, rows, sz, 1e-5, out=out, bias=W[p + ".conv2.bias"], residual=sc)
             if got is not None:
                 (out, st2), done = got, True
         if not done:
-            n2, st2 = ops.groupnorm(h1, rows, HW, G, 1e-5, W[p + ".norm2.weight"], W[p + ".norm2.bias"], True, partial=part1)
-        if wino2 and not done:
-            o = self._conv_wino(p + ".conv2.weight:wino", n2, rows, sz, out=out, bias=W[p + ".conv2.bias"], residual=sc)
-            if o is not None:
-                out, done = o, True
-        if not done and (p + ".conv2.weight:sc") in W:
-            # the 1x1 shortcut as K tiles behind conv2's 3x3 walk: one launch, no [M, Cout] round trip of the shortcut output
+            n2, st2 = self._norm(h1, rows, HW, 1e-5, p + ".norm2", True, partial=part1)
+        n2_pair = isinstance(n2, ops.Pair)
+        if wino2 and not done and not n2_pair:
+            sc = self._shortcut(p, x, M, Cout) if sc is None else sc
+            done = self._conv_wino(k2 + ":wino", n2, rows, sz, out=out, bias=W[p + ".conv2.bias"], residual=sc) is not None
+        a2 = n2.full if n2_pair else n2
+        ksc = k2 + (":sc2" if pair else ":sc")
+        if not done and ksc in W:
+            # the 1x1 shortcut as K tiles behind conv2's 3x3 walk: one launch, no [M, Cout] round trip of the shortcut output (pair zone:
+            # the K-doubled shortcut [x_hi | x_lo] . [W_sc | W_sc]; behind a norm with a pair output the folded pack is ':n2')
             try:
-                if want_part and fuse:
-                    out, opart = ops.conv3x3_sc(n2, x, W[p + ".conv2.weight:sc"], rows, *sz, out=out, bias=W[p + ".conv2.bias:sc"], gn_groups=G)
-                else:
-                    out = ops.conv3x3_sc(n2, x, W[p + ".conv2.weight:sc"], rows, *sz, out=out, bias=W[p + ".conv2.bias:sc"])
+                out, opart = _produce("conv3x3_sc", a2, self._full_of(x) if pair else x, W[k2 + ":n2"] if n2_pair else W[ksc], rows, *sz,
+                                      out=out, bias=W[p + ".conv2.bias:sc"], gn=ogn)
                 done = True
             except ops.SkgError as e:      # declined (an operand >= 2 GiB): the two launches
                 if e.rc != -2:
                     raise
         if not done:
-            if (p + ".conv_shortcut.weight") in W:
-                sc = ops.gemm(x, W[p + ".conv_shortcut.weight"], bias=W[p + ".conv_shortcut.bias"])
-            else:
-                sc = x
-            if want_part and fuse:
-                out, opart = ops.conv3x3(n2, W[p + ".conv2.weight"], rows, *sz, out=out, bias=W[p + ".conv2.bias"],
-                                         residual=sc, gn_groups=G)
-            else:
-                out = ops.conv3x3(n2, W[p + ".conv2.weight"], rows, *sz, out=out, bias=W[p + ".conv2.bias"], residual=sc)
-        if stash is not None:
-            stash.res[p] = dict(x=x, st1=st1, h1=h1, st2=st2, sz=sz, half=half)
+            sc = self._shortcut(p, x, M, Cout) if sc is None else sc
+            # (behind a norm with a pair output conv2's own [W | W] taps are the leading columns of its ':n2' pack, made contiguous)
+            w2 = W[k2 + ":n2"][:, : 9 * a2.shape[1]].contiguous() if n2_pair else W[k2]
+            out, opart = _produce("conv3x3", a2, w2, rows, *sz, out=out, bias=W[p + ".conv2.bias"], residual=sc, gn=ogn)
+        if stash is not None:      # (the backward differentiates the fp16 - hi - values in either mode)
+            stash.res[p] = dict(x=_hi(x), st1=st1, h1=_hi(h1), st2=st2, sz=sz, half=half)
         return out, opart
 
     def _tr_fwd(self, p, x, rows, sz, heads, stash: Optional[Stash], out=None, xpart=None, want_part=False, shared=False,
                 x_full=None):
-        """shared: x holds the COND rows only (rows // 2 of them) of a CFG-doubled batch whose two halves are identical up
+        """x: fp16 or a Pair (the pair zone): p1, p2, p3, pin and the output have its representation, q2 / qkv are fp16.
+        shared: x holds the COND rows only (rows // 2 of them) of a CFG-doubled batch whose two halves are identical up
         to here (see forward): everything in front of the first text-dependent operation - GroupNorm, proj_in, the whole
         self-attention, LayerNorm 2, to_q - runs once; p1 and q2 are written into the cond half of full-size buffers and
         copied to the uncond half (x_full: the same for x, filled by the caller)."""
-        cfg, W = self.cfg, self.W
-        HW = sz[0] * sz[1]
-        C = x.shape[1]
+        cfg, W, pair = self.cfg, self.W, isinstance(x, ops.Pair)
+        HW, M = sz[0] * sz[1], rows * sz[0] * sz[1]
+        C = _hi(x).shape[1]
         dh = C // heads
         scale = dh ** -0.5
         t = p + ".transformer_blocks.0"
         keep = stash is not None
         r1 = rows // 2 if shared else rows                    # rows of the text-independent part
-        g, gst = ops.groupnorm(x, r1, HW, cfg.norm_groups, 1e-6, W[p + ".norm.weight"], W[p + ".norm.bias"], False,
-                               partial=xpart)
-        pin = ops.gemm(g, W[p + ".proj_in.weight"], bias=W[p + ".proj_in.bias"])
-        a1, st1 = ops.layernorm(pin, W[t + ".norm1.weight"], W[t + ".norm1.bias"], want_stats=True)
+        M1, M0 = r1 * HW, (rows // 2) * HW                    # M0: the first cond row of a stashing launch
+        ln = lambda v, k: _layernorm(v, W[f"{t}.{k}.weight"], W[f"{t}.{k}.bias"], want_stats=True)
+        g, gst = self._norm(x, r1, HW, 1e-6, p + ".norm", False, partial=xpart)
+        pin, _ = _produce("gemm", *self._operand(g, p + ".proj_in.weight", ":n2"), out=_fresh(x, M1, C), bias=W[p + ".proj_in.bias"])
+        a1, st1 = ln(pin, "norm1")
         qkv = ops.gemm(a1, W[t + ".attn1.qkv"])
         # V straight out of the fused projection (row-major; the kernel's LDS transpose read replaces the V^T copy)
         o1, lse1 = ops.attn_fwd(qkv[:, :C], qkv[:, C:2 * C], qkv[:, 2 * C:], r1, heads, HW, HW, HW, dh, scale,
                                 want_lse=True, v_rows=True)
-        M1 = r1 * HW
-        p1_full = torch.empty(rows * HW, C, device=x.device, dtype=torch.float16) if shared else None
-        p1 = ops.gemm(o1, W[t + ".attn1.to_out.0.weight"], p1_full[M1:] if shared else None,
-                      bias=W[t + ".attn1.to_out.0.bias"], residual=pin)
+        p1_full = _fresh(x, M, C) if shared else None
+        p1, _ = _produce("gemm", o1, W[t + ".attn1.to_out.0.weight"], out=_rows_of(p1_full, M1, M) if shared else _fresh(x, M, C),
+                         bias=W[t + ".attn1.to_out.0.bias"], residual=pin)
         x_c, p1_c = x, p1                                     # what the backward of the cond rows reads
         if self.inject is not None:
             if shared and getattr(self.inject, "halves_equal", False):
                 # the injected K / V are the same for both halves too (checked by the injector): stay shared through it
-                p1_full2 = torch.empty(rows * HW, C, device=x.device, dtype=torch.float16)
-                p1 = self.inject(t, p1, rows, HW, heads, cond_only=True, out=p1_full2[M1:])
-                p1_full = p1_full2
+                p1_full = _fresh(x, M, C)
+                p1 = self.inject(t, p1, rows, HW, heads, cond_only=True, out=_rows_of(p1_full, M1, M))
             else:
                 if shared:                                    # the injected K / V differ between the halves: diverge here
-                    ops.batch_copy(p1, M1, p1_full, M1, 1, M1)
+                    _copy_up(p1, p1_full, M1)
                     x, p1, shared = x_full, p1_full, False
                 p1 = self.inject(t, p1, rows, HW, heads)
             p1_c = p1
         cb = self.ctx["blocks"][t + ".attn2"]
-        xab = (_XATTN_BLOCK and (not keep or (_XATTN_KEEP and rows % 2 == 0)) and "kvpack" in cb and heads in _XATTN_HEADS and HW % 128 == 0)
+        xab = (_XATTN_BLOCK and (not keep or ((_XATTN_KEEP_HP if pair else _XATTN_KEEP) and rows % 2 == 0)) and "kvpack" in cb
+               and heads in _XATTN_HEADS and HW % 128 == 0)
         xk_half = ()
         if xab:
-            # norm2 -> to_q -> attention over the text keys -> to_out + residual in ONE row-local launch (skg_xattn_block_f16); the
-            # text-dependent part needs both halves, so a shared front ends here
+            # norm2 -> to_q -> attention over the text keys -> to_out + residual in ONE row-local launch (skg_xattn_block_f16[_hilo]);
+            # the text-dependent part needs both halves, so a shared front ends here
             if shared:
-                ops.batch_copy(p1, M1, p1_full, M1, 1, M1)
+                _copy_up(p1, p1_full, M1)
                 x, p1, shared = x_full, p1_full, False
             xargs = (HW, heads, self.ctx["L"], W[t + ".norm2.weight"], W[t + ".norm2.bias"], 1e-5, W[t + ".attn2.xpack"], cb["kvpack"],
                      W[t + ".attn2.to_out.0.bias"], scale)
             if keep:
                 # guided step: the same launch also stores what the backward of the cond rows (second half) reads - norm2's
-                # statistics, q, the attention output and its lse (skg_xattn_block_f16_keep), for those rows only
-                p2, st2, q2_c, o2, lse2 = ops.xattn_block(p1, *xargs, keep_from=(rows // 2) * HW)
-                q2 = q2_c
+                # statistics, q, the attention output and its lse (skg_xattn_block_f16[_hilo]_keep), for those rows only
+                p2, st2, q2_c, o2, lse2 = ops.xattn_block(p1, *xargs, keep_from=M0)
                 xk_half = ("st2", "q2", "o2", "lse2")
             else:
                 p2 = ops.xattn_block(p1, *xargs)
-                st2 = q2 = q2_c = o2 = lse2 = None            # (only a stash would read them, and there is none)
+                st2 = q2_c = o2 = lse2 = None                 # (only a stash would read them, and there is none)
         else:
-            a2, st2 = ops.layernorm(p1, W[t + ".norm2.weight"], W[t + ".norm2.bias"], want_stats=True)
-            q2_full = torch.empty(rows * HW, C, device=x.device, dtype=torch.float16) if shared else None
-            q2 = ops.gemm(a2, W[t + ".attn2.to_q.weight"], q2_full[M1:] if shared else None)
-            q2_c = q2
+            a2, st2 = ln(p1, "norm2")
+            q2_full = torch.empty(M, C, device=self.dev, dtype=torch.float16) if shared else None
+            q2 = q2_c = ops.gemm(a2, W[t + ".attn2.to_q.weight"], q2_full[M1:] if shared else None)
             if shared:      # the text-dependent part needs both halves: one copy each into the uncond half
-                ops.batch_copy(p1, M1, p1_full, M1, 1, M1)
+                _copy_up(p1, p1_full, M1)
                 ops.batch_copy(q2, M1, q2_full, M1, 1, M1)
                 x, p1, q2 = x_full, p1_full, q2_full
             o2, lse2 = ops.attn_fwd(q2, cb["K"], cb["V"], rows, heads, HW, self.ctx["L"], self.ctx["Lp"], dh, scale,
                                     want_lse=True, v_rows=True)
-            p2 = ops.gemm(o2, W[t + ".attn2.to_out.0.weight"], bias=W[t + ".attn2.to_out.0.bias"], residual=p1)
-        ffb = _FF_BLOCK and (t + ".ff.pack") in W and (not keep or rows % 2 == 0)
-        st3_half = False
-        ffp = ffb and _FF_PROJ and (t + ".ff.packp") in W and (not keep or _FF_KEEP) and HW % 128 == 0
-        opart = None
-        if ffp:
-            # ... and proj_out + the outer residual behind it in the same launch (skg_ff_block_proj_f16): the block output p3 never
-            # reaches memory (no backward reads it); GroupNorm partial sums of the result when the consumer folds them
-            gn = (HW, cfg.norm_groups) if want_part and self._gn_from_producer(rows, HW, C) else None
-            if out is None:
-                out = torch.empty(rows * HW, C, device=x.device, dtype=torch.float16)
-            _, st3, f, opart = ops.ff_block_proj(p2, W[t + ".norm3.weight"], W[t + ".norm3.bias"], 1e-5, W[t + ".ff.packp"], W[t + ".ff.bias1"],
-                                                 W[t + ".ff.net.2.bias"], W[p + ".proj_out.bias"], x, out=out, want_stats=keep,
-                                                 keep_from=(rows // 2) * HW if keep else None, gn=gn)
-        elif ffb:
-            # C = 320: norm3 -> FF1 -> gate -> FF2 + residual in ONE row-local launch (skg_ff_block_f16: the row panel and the
-            # output accumulators stay in registers, only weights stream).  In a guided step the same launch also stores what
-            # the backward of the cond rows reads: the FF1 output (interleaved pack) and norm3's statistics
-            M0 = (rows // 2) * HW
-            p3 = torch.empty(rows * HW, C, device=x.device, dtype=torch.float16)
-            ffargs = (W[t + ".norm3.weight"], W[t + ".norm3.bias"], 1e-5, W[t + ".ff.pack"], W[t + ".ff.bias1"], W[t + ".ff.net.2.bias"])
-            f, st3 = None, None
-            if not keep:
-                ops.ff_block(p2, *ffargs, out=p3)
-            elif _FF_KEEP:
-                _, st3, f = ops.ff_block(p2, *ffargs, out=p3, want_stats=True, keep_from=M0)
-            else:       # (A/B switch: the uncond half fused, the cond half on the launches that stash)
-                ops.ff_block(p2[:M0], *ffargs, out=p3[:M0])
-                a3, st3 = ops.layernorm(p2[M0:], W[t + ".norm3.weight"], W[t + ".norm3.bias"], want_stats=True)
-                st3_half = True
-                if _GEGLU_KEEP:
-                    ggc, f = ops.gemm_geglu_keep(a3, W[t + ".ff.net.0.proj.weight"], W[t + ".ff.net.0.proj.bias"])
-                else:
-                    f = ops.gemm(a3, W[t + ".ff.net.0.proj.weight"], bias=W[t + ".ff.net.0.proj.bias"])
-                    ggc = ops.geglu(f, interleaved=True)
-                ops.gemm(ggc, W[t + ".ff.net.2.weight"], p3[M0:], bias=W[t + ".ff.net.2.bias"], residual=p2[M0:])
+            p2, _ = _produce("gemm", o2, W[t + ".attn2.to_out.0.weight"], out=_fresh(x, M, C), bias=W[t + ".attn2.to_out.0.bias"], residual=p1)
+        # C = 320: norm3 -> FF1 -> gate -> FF2 + residual in ONE row-local launch (skg_ff_block_f16[_hilo]: the row panel and the output
+        # accumulators stay in registers, only weights stream).  In a guided step the same launch also stores what the backward of
+        # the cond rows reads: the FF1 output (interleaved pack) and norm3's statistics
+        ffb = _FF_BLOCK and (t + ".ff.pack") in W and (not keep or (rows % 2 == 0 and _FF_KEEP))
+        ffp = ffb and _FF_PROJ and (not pair or _FF_PROJ_HP) and (t + ".ff.packp") in W and HW % 128 == 0
+        gn = (HW, cfg.norm_groups) if want_part and self._gn_from_producer(rows, HW, C) else None
+        out = _fresh(x, M, C) if out is None else out
+        f = st3 = opart = None
+        if ffb:
+            ffargs = (W[t + ".norm3.weight"], W[t + ".norm3.bias"], 1e-5, W[t + (".ff.packp" if ffp else ".ff.pack")], W[t + ".ff.bias1"],
+                      W[t + ".ff.net.2.bias"])
+            if ffp:
+                # ... and proj_out + the outer residual behind it in the same launch (skg_ff_block_proj_f16[_hilo]): the block output
+                # p3 never reaches memory (no backward reads it); GroupNorm partial sums of the result when the consumer folds them
+                _, st3, f, opart = ops.ff_block_proj(p2, *ffargs, W[p + ".proj_out.bias"], x, out=out, want_stats=keep,
+                                                     keep_from=M0 if keep else None, gn=gn)
+            elif keep:
+                p3, st3, f = ops.ff_block(p2, *ffargs, want_stats=True, keep_from=M0)
+            else:
+                p3 = ops.ff_block(p2, *ffargs)
         else:
-            a3, st3 = ops.layernorm(p2, W[t + ".norm3.weight"], W[t + ".norm3.bias"], want_stats=True)
+            a3, st3 = ln(p2, "norm3")
+            w1, b1 = W[t + ".ff.net.0.proj.weight"], W[t + ".ff.net.0.proj.bias"]
             if not keep and C % 64 == 0:        # no backward will follow: gate inside the GEMM epilogue (half the bytes)
-                f = None
-                gg = ops.gemm(a3, W[t + ".ff.net.0.proj.weight"], bias=W[t + ".ff.net.0.proj.bias"], geglu=True)
+                gg = ops.gemm(a3, w1, bias=b1, geglu=True)
             elif C % 64 == 0 and rows % 2 == 0:
-                # guided step: only the cond half (second half of the rows) is differentiated, so only it needs the
-                # pre-activation f; the uncond half takes the fused-GEGLU GEMM (a fifth of the bytes of GEMM + gate kernel)
-                M0 = (rows // 2) * HW
-                gg = torch.empty(rows * HW, 4 * C, device=x.device, dtype=torch.float16)
-                ops.gemm(a3[:M0], W[t + ".ff.net.0.proj.weight"], bias=W[t + ".ff.net.0.proj.bias"], geglu=True, out=gg[:M0])
-                # cond rows: the same fused epilogue also stores the pre-activation the gate's backward needs
-                if _GEGLU_KEEP:
-                    _, f = ops.gemm_geglu_keep(a3[M0:], W[t + ".ff.net.0.proj.weight"], W[t + ".ff.net.0.proj.bias"], out=gg[M0:])
-                else:
-                    f = ops.gemm(a3[M0:], W[t + ".ff.net.0.proj.weight"], bias=W[t + ".ff.net.0.proj.bias"])
-                    ops.geglu(f, out=gg[M0:], interleaved=True)
+                # guided step: only the cond half (second half of the rows) is differentiated, so only it needs the pre-activation
+                # f: the uncond half takes the fused-GEGLU GEMM (a fifth of the bytes of GEMM + gate kernel), the cond half the
+                # same fused epilogue that also stores the pre-activation the gate's backward needs
+                gg = torch.empty(M, 4 * C, device=self.dev, dtype=torch.float16)
+                ops.gemm(a3[:M0], w1, bias=b1, geglu=True, out=gg[:M0])
+                _, f = ops.gemm_geglu_keep(a3[M0:], w1, b1, out=gg[M0:])
             else:
-                f = ops.gemm(a3, W[t + ".ff.net.0.proj.weight"], bias=W[t + ".ff.net.0.proj.bias"])
+                f = ops.gemm(a3, w1, bias=b1)
                 gg = ops.geglu(f, interleaved=True)
-                f = f[(rows // 2) * HW:]
-            p3 = ops.gemm(gg, W[t + ".ff.net.2.weight"], bias=W[t + ".ff.net.2.bias"], residual=p2)
+                f = f[M0:]
+            p3, _ = _produce("gemm", gg, W[t + ".ff.net.2.weight"], out=_fresh(x, M, C), bias=W[t + ".ff.net.2.bias"], residual=p2)
         if not ffp:
-            if want_part and self._gn_from_producer(rows, HW, C):
-                out, opart = ops.gemm(p3, W[p + ".proj_out.weight"], out, bias=W[p + ".proj_out.bias"], residual=x,
-                                      gn_stats=(HW, cfg.norm_groups))
-            else:
-                out = ops.gemm(p3, W[p + ".proj_out.weight"], out, bias=W[p + ".proj_out.bias"], residual=x)
+            out, opart = _produce("gemm", *self._operand(p3, p + ".proj_out.weight", ":2"), out=out, bias=W[p + ".proj_out.bias"],
+                                  residual=x, gn=gn)
         if keep:
-            # half: the tensors of the text-independent part hold the cond rows only (r1 == rows // 2)
-            # (`half` is derived from what each tensor actually holds - r1 rows or all of them - whatever the injector did, so that
-            # a backward through an injected block could never slice an M1-row tensor a second time: ADVICE r3)
-            st3h = ("st3",) if st3_half else ()      # fused FF block: norm3's statistics exist for the cond rows only
-            ent = dict(x=x_c, gst=gst, pin=pin, st1=st1, qkv=qkv, o1=o1, lse1=lse1, p1=p1_c, st2=st2, q2=q2_c)
-            half = self._stash_half(ent, r1, rows, HW)
-            if r1 != rows and "x" not in half:      # the front diverged before p1 (an injector with differing halves): x is full size
-                ent["x"] = x
-            half = tuple(k for k in half if k not in xk_half) + xk_half      # (the stashing cross-attention launch: cond rows only)
-            stash.tr[p] = dict(ent, o2=o2, lse2=lse2, p2=p2, st3=st3, f=f, sz=sz, heads=heads, half=half + st3h)
+            # the fp16 (hi) tensors the backward of the cond rows reads.  x / p1 / q2: what the text-independent part produced (after
+            # the injector, for p1) - the cond rows only under a shared front.  half: the keys whose tensors hold the cond rows only,
+            # derived from what each tensor actually holds - r1 rows or all of them - whatever the injector did, so that a backward
+            # through an injected block could never slice an M1-row tensor a second time (ADVICE r3)
+            ent = dict(x=_hi(x_c), gst=gst, pin=_hi(pin), st1=st1, qkv=qkv, o1=o1, lse1=lse1, p1=_hi(p1_c), st2=st2, q2=q2_c)
+            half = tuple(k for k in self._stash_half(ent, r1, rows, HW) if k not in xk_half) + xk_half      # (the stashing cross-attention launch: cond rows only)
+            stash.tr[p] = dict(ent, o2=o2, lse2=lse2, p2=_hi(p2), st3=st3, f=f, sz=sz, heads=heads, half=half)
         return out, opart
 
     @staticmethod
@@ -772,17 +797,13 @@ class HipUNet:
             raise NotImplementedError(f"non-square latents {sz}: both sides must be multiples of {f}")
 
     # ------------------------------------------------------------------ forward
-    def _conv_gn(self, x, wkey: str, bkey: str, rows: int, sz: Tuple[int, int], mode: int, out):
-        """A convolution whose output may leave GroupNorm partial sums behind: -> (out, the sums or None).  out: an fp16 view, a
-        Pair (the pair epilogue), or None (a fresh fp16 tensor); the sums come with it where the level of the OUTPUT takes its
-        statistics from the producers (_gn_from_producer)."""
-        W = self.W
+    def _conv_gn(self, x, w, bkey: str, rows: int, sz: Tuple[int, int], mode: int, out):
+        """A convolution (x, w: see _operand) whose output may leave GroupNorm partial sums behind: -> (out, the sums or None).  out: an
+        fp16 view, a Pair (the pair epilogue), or None (a fresh fp16 tensor); the sums come with it where the level of the OUTPUT takes
+        its statistics from the producers (_gn_from_producer)."""
         osz = _half(sz) if mode == ops.CONV_S2 else sz
-        hi, lo = (out.hi, out.lo) if isinstance(out, ops.Pair) else (out, None)
-        gn = self.cfg.norm_groups if self._gn_from_producer(rows, osz[0] * osz[1], W[wkey].shape[0]) else None
-        res = ops.conv3x3(x, W[wkey], rows, *sz, mode, out=hi, bias=W[bkey], gn_groups=gn, out_lo=lo)
-        o, part = res if gn is not None else (res, None)
-        return (o if lo is None else out), part
+        gn = (osz[0] * osz[1], self.cfg.norm_groups) if self._gn_from_producer(rows, osz[0] * osz[1], w.shape[0]) else None
+        return _produce("conv3x3", x, w, rows, *sz, mode, out=out, bias=self.W[bkey], gn=gn)
 
     def _upsample(self, p: str, h, rows: int, sz: Tuple[int, int], out):
         """The nearest-2x upsampler convolution `p` of an up block: h (fp16: the block lies in the plain zone, or a Pair) -> out (the
@@ -848,33 +869,29 @@ class HipUNet:
         boc = cfg.block_out_channels
         nb, lpb, lpb1 = len(boc), cfg.layers_per_block, cfg.layers_per_block + 1
         cats = _ConcatBuffers(self, rows, down_only)
-        blocks = lambda plain: (self._res_fwd, self._tr_fwd) if plain else (self._res_fwd_hp, self._tr_fwd_hp)
+        res, tr = self._res_fwd, self._tr_fwd      # (one body each: the representation of their input - fp16 or Pair - decides)
         # hp: GroupNorm partial sums of h left behind by the kernel that produced it, whenever the next consumer of h is a
         # GroupNorm of the 64 x 64 / 32 x 32 levels (None otherwise: concatenated inputs, small maps)
         shared = shared_input and rows % 2 == 0 and rows >= 2 and not down_only and nb > 1 and lpb >= 1
         cur = sz
-        res, tr = blocks(self._plain_down(0))
         if shared:
             S1, M1 = rows // 2, (rows // 2) * sz[0] * sz[1]
             slot = cats.skip_slot(boc[0], sz)                      # the skip of conv_in, all rows
             hc = _rows_of(slot, M1, 2 * M1)
-            _, hp1 = self._conv_gn(x32[M1:], "conv_in.weight", "conv_in.bias", S1, sz, ops.CONV_S1, hc)
+            _, hp1 = self._conv_gn(x32[M1:], W["conv_in.weight"], "conv_in.bias", S1, sz, ops.CONV_S1, hc)
             _copy_up(hc, slot, M1)
             cats.push(slot, self._dup_partial(hp1))
-            x_full = self._pair(rows * sz[0] * sz[1], boc[0]) if isinstance(slot, ops.Pair) else \
-                torch.empty(rows * sz[0] * sz[1], boc[0], device=self.dev, dtype=torch.float16)
+            x_full = _fresh(slot, 2 * M1, boc[0])
             h1, hp1 = res("down_blocks.0.resnets.0", hc, S1, cur, tb, stash, out=_rows_of(x_full, M1, 2 * M1), xpart=hp1,
                           want_part=True, half=True)
             _copy_up(h1, x_full, M1)
             h, hp = tr("down_blocks.0.attentions.0", h1, rows, cur, cfg.num_heads[0], stash, out=cats.skip_slot(boc[0], cur),
                        xpart=hp1, want_part=0 < lpb - 1, shared=True, x_full=x_full)
         else:
-            h, hp = self._conv_gn(x32, "conv_in.weight", "conv_in.bias", rows, sz, ops.CONV_S1, cats.skip_slot(boc[0], sz))
+            h, hp = self._conv_gn(x32, W["conv_in.weight"], "conv_in.bias", rows, sz, ops.CONV_S1, cats.skip_slot(boc[0], sz))
         cats.push(h, hp)
         taps_down = []
         for i in range(nb):
-            plain = self._plain_down(i)
-            res, tr = blocks(plain)
             for j in range(lpb):
                 if shared and i == 0 and j == 0:
                     continue                                      # done above, once for both halves
@@ -892,8 +909,7 @@ class HipUNet:
                 # K-doubled operand and the output fp16)
                 p = f"down_blocks.{i}.downsamplers.0.conv"
                 o = cats.skip_slot(boc[i], _half(cur))
-                x, wkey = (h, p + ".weight") if plain else (self._full_of(h), p + ".weight:2")
-                h, hp = self._conv_gn(x, wkey, p + ".bias", rows, cur, ops.CONV_S2, o)
+                h, hp = self._conv_gn(*self._operand(h, p + ".weight", ":2"), p + ".bias", rows, cur, ops.CONV_S2, o)
                 cur = _half(cur)
                 cats.push(h, hp)
             if i < 3:
@@ -910,7 +926,6 @@ class HipUNet:
                 out.append(tuple((cats.skips[k + j], sizes[j]) for j in range(n)))
                 k += n
             return out
-        res, tr = blocks(self._plain_up(0))
         h, hp = res("mid_block.resnets.0", h, rows, cur, tb, stash, xpart=hp, want_part=True)
         tap_r0 = (_hi(h), _side(cur))
         h, hp = tr("mid_block.attentions.0", h, rows, cur, cfg.num_heads[-1], stash, xpart=hp, want_part=True)
@@ -924,7 +939,6 @@ class HipUNet:
         for i in range(nb):
             if i > last_needed:
                 break
-            res, tr = blocks(self._plain_up(i))
             for j in range(lpb1):
                 u = i * lpb1 + j
                 rp, ap = f"up_blocks.{i}.resnets.{j}", f"up_blocks.{i}.attentions.{j}"
@@ -951,28 +965,19 @@ class HipUNet:
                     on_taps(taps_down + [tap_at, tap_r0, tap_r1] + taps_up)
         eps = None
         HW = cur[0] * cur[1]
-        if want_eps and isinstance(h, ops.Pair):
-            # conv_norm_out -> SiLU -> conv_out: both the normalised activation (the K-doubled operand [hi | lo] . [W | W]) and eps
-            # itself (a (hi, lo) pair in one [M, 2 * 8] buffer, combined in fp32 by the CFG / scheduler kernel) keep fp32 accuracy -
-            # their fp16 roundings would reach eps one to one (2.8e-4 relative each)
-            n = self._pair(rows * HW, boc[0])
-            ops.groupnorm_hilo(h.hi, h.lo, rows, HW, cfg.norm_groups, 1e-5, W["conv_norm_out.weight"], W["conv_norm_out.bias"], True,
-                               out=n.hi, out_lo=n.lo, partial=hp)
-            eps = self._pair(rows * HW, COUT_PAD)
-            ops.conv3x3(n.full, W["conv_out.weight:2"], rows, *cur, out=eps.hi, out_lo=eps.lo, bias=W["conv_out.bias"])
-        elif want_eps:
-            n, nst = ops.groupnorm(h, rows, HW, cfg.norm_groups, 1e-5, W["conv_norm_out.weight"], W["conv_norm_out.bias"], True,
-                                   partial=hp)
-            eps = ops.conv3x3(n, W["conv_out.weight"], rows, *cur, bias=W["conv_out.bias"])
-            if stash is not None:      # what backward_eps reads (references only: no extra launch)
+        if want_eps:
+            # conv_norm_out -> SiLU -> conv_out.  Accuracy mode: both the normalised activation (the K-doubled operand [hi | lo] . [W | W])
+            # and eps itself (a (hi, lo) pair in one [M, 2 * 8] buffer, combined in fp32 by the CFG / scheduler kernel) keep fp32
+            # accuracy - their fp16 roundings would reach eps one to one (2.8e-4 relative each)
+            n, nst = self._norm(h, rows, HW, 1e-5, "conv_norm_out", True, partial=hp, pair_out=True)
+            eps, _ = _produce("conv3x3", *self._operand(n, "conv_out.weight", ":2"), rows, *cur, out=_fresh(h, rows * HW, COUT_PAD),
+                              bias=W["conv_out.bias"])
+            if stash is not None and not isinstance(h, ops.Pair):      # what backward_eps reads (references only: no extra launch)
                 stash.misc.update(out_h=h, out_st=nst)
         taps = taps_down + [tap_at, tap_r0, tap_r1] + taps_up
         return eps, (taps if want_taps else None)
 
-    # ------------------------------------------------------------------ modules of the pair zone (accuracy mode, residual_fp32)
-    def _pair(self, M: int, C: int) -> ops.Pair:
-        return ops.Pair.empty(M, C, self.dev)
-
+    # ------------------------------------------------------------------ pairs (accuracy mode, residual_fp32)
     @staticmethod
     def _full_of(pv: ops.Pair) -> torch.Tensor:
         """[hi | lo] as ONE operand: the pair's own buffer, or a packed copy when it lives inside a concat buffer."""
@@ -983,221 +988,6 @@ class HipUNet:
         ops.axpby(pv.hi, None, out=buf[:, :C])
         ops.axpby(pv.lo, None, out=buf[:, C:])
         return buf
-
-    def _gn_hp(self, x, rows, HW, eps, name, silu, partial=None):
-        """-> (normalised fp16 tensor, statistics [rows, groups, 2]); partial: the producer's epilogue sums (see ops.groupnorm_hilo).
-        A norm listed in HP_NORM_PAIRS returns its output as a PAIR (ops.Pair with .full = the K-doubled operand [hi | lo])."""
-        if name in self.hp_norm_pairs:
-            n = self._pair(x.hi.shape[0], x.hi.shape[1])
-            _, st = ops.groupnorm_hilo(x.hi, x.lo, rows, HW, self.cfg.norm_groups, eps, self.W[name + ".weight"],
-                                       self.W[name + ".bias"], silu, out=n.hi, out_lo=n.lo, want_stats=True, partial=partial)
-            return n, st
-        return ops.groupnorm_hilo(x.hi, x.lo, rows, HW, self.cfg.norm_groups, eps, self.W[name + ".weight"],
-                                  self.W[name + ".bias"], silu, want_stats=True, partial=partial)
-
-    def _res_fwd_hp(self, p, x, rows, sz, tb, stash: Optional[Stash] = None, out=None, xpart=None, want_part=False, half=False):
-        """As _res_fwd on pairs.  Returns (out pair, GroupNorm partial sums of out or None)."""
-        W = self.W
-        G = self.cfg.norm_groups
-        HW, M = sz[0] * sz[1], rows * sz[0] * sz[1]
-        Cout = W[p + ".conv1.weight"].shape[0]
-        n1, st1 = self._gn_hp(x, rows, HW, 1e-5, p + ".norm1", True, partial=xpart)
-        h1 = self._pair(M, Cout)                                    # conv1 output feeds norm2: kept as a pair ("lin_n")
-        fuse = self._gn_from_producer(rows, HW, Cout)
-        part1 = None
-        a1, w1 = (n1.full, W[p + ".conv1.weight:n2"]) if isinstance(n1, ops.Pair) else (n1, W[p + ".conv1.weight"])
-        wino = _HP_WINO and not fuse      # (small maps only: the levels whose GroupNorm statistics do not come from the producers)
-        if wino and not isinstance(n1, ops.Pair) and self._conv_wino(p + ".conv1.weight:wino", n1, rows, sz, out=h1.hi, out_lo=h1.lo, bias=tb[p]) is not None:
-            pass
-        elif fuse:
-            _, part1 = ops.conv3x3(a1, w1, rows, *sz, out=h1.hi, out_lo=h1.lo, bias=tb[p], gn_groups=G)
-        else:
-            ops.conv3x3(a1, w1, rows, *sz, out=h1.hi, out_lo=h1.lo, bias=tb[p])
-        n2, st2 = self._gn_hp(h1, rows, HW, 1e-5, p + ".norm2", True, partial=part1)
-        n2_pair = isinstance(n2, ops.Pair)
-        w2n = W[p + ".conv2.weight:n2"] if n2_pair else None
-        if n2_pair:
-            n2 = n2.full
-        if stash is not None:      # the backward differentiates the fp16 (hi) values, as in the default mode
-            stash.res[p] = dict(x=x.hi, st1=st1, h1=h1.hi, st2=st2, sz=sz, half=half)
-        out = out or self._pair(M, Cout)
-        opart = None
-        if wino and not n2_pair and self._wino_ok(p + ".conv2.weight:wino", rows, sz):
-            # Winograd conv2, pair output; its residual is the block input pair or the K-doubled shortcut GEMM's pair output
-            if (p + ".conv_shortcut.weight") in W:
-                sc = self._pair(M, Cout)
-                xf = self._full_of(x)
-                ops.gemm(xf, W[p + ".conv_shortcut.weight:2"], out=sc.hi, out_lo=sc.lo, bias=W[p + ".conv_shortcut.bias"])
-            else:
-                sc = x
-            if self._conv_wino(p + ".conv2.weight:wino", n2, rows, sz, out=out.hi, out_lo=out.lo, bias=W[p + ".conv2.bias"],
-                               residual=sc.hi, residual_lo=sc.lo) is not None:
-                return out, None
-        if (p + ".conv2.weight:sc2") in W:
-            # conv2 + the K-doubled shortcut [x_hi | x_lo] . [W_sc | W_sc] in one launch, pair output
-            xf = self._full_of(x)
-            wsc2 = w2n if n2_pair else W[p + ".conv2.weight:sc2"]
-            try:
-                if want_part and fuse:
-                    _, opart = ops.conv3x3_sc(n2, xf, wsc2, rows, *sz, out=out.hi, out_lo=out.lo,
-                                              bias=W[p + ".conv2.bias:sc"], gn_groups=G)
-                else:
-                    ops.conv3x3_sc(n2, xf, wsc2, rows, *sz, out=out.hi, out_lo=out.lo, bias=W[p + ".conv2.bias:sc"])
-                return out, opart
-            except ops.SkgError as e:
-                if e.rc != -2:
-                    raise
-            if n2_pair:      # the two-launch fall-back takes conv2's own [W | W] taps (the leading columns of the folded pack)
-                w2n = w2n[:, : 9 * n2.shape[1]]
-        if (p + ".conv_shortcut.weight") in W:
-            sc = self._pair(M, Cout)                                 # the stream as a matmul operand: [hi | lo] . [W | W]
-            xf = self._full_of(x)
-            ops.gemm(xf, W[p + ".conv_shortcut.weight:2"], out=sc.hi, out_lo=sc.lo, bias=W[p + ".conv_shortcut.bias"])
-        else:
-            sc = x
-        w2 = w2n if n2_pair else W[p + ".conv2.weight"]
-        if not w2.is_contiguous():              # (a column slice of the folded pack: the kernel wants the 9-tap pack contiguous)
-            w2 = w2.contiguous()
-        if want_part and fuse:
-            _, opart = ops.conv3x3(n2, w2, rows, *sz, out=out.hi, out_lo=out.lo, bias=W[p + ".conv2.bias"],
-                                   residual=sc.hi, residual_lo=sc.lo, gn_groups=G)
-        else:
-            ops.conv3x3(n2, w2, rows, *sz, out=out.hi, out_lo=out.lo, bias=W[p + ".conv2.bias"],
-                        residual=sc.hi, residual_lo=sc.lo)
-        return out, opart
-
-    def _tr_fwd_hp(self, p, x, rows, sz, heads, stash: Optional[Stash] = None, out=None, xpart=None, want_part=False, shared=False,
-                   x_full=None):
-        """As _tr_fwd on pairs (shared / x_full: the shared CFG front, see _tr_fwd: x holds the cond rows only)."""
-        W = self.W
-        HW, M = sz[0] * sz[1], rows * sz[0] * sz[1]
-        C = x.hi.shape[1]
-        dh = C // heads
-        scale = dh ** -0.5
-        t = p + ".transformer_blocks.0"
-        keep = stash is not None
-        r1 = rows // 2 if shared else rows
-        M1 = r1 * HW
-        g, gst = self._gn_hp(x, r1, HW, 1e-6, p + ".norm", False, partial=xpart)
-        pin = self._pair(M1, C)
-        if isinstance(g, ops.Pair):
-            ops.gemm(g.full, W[p + ".proj_in.weight:n2"], out=pin.hi, out_lo=pin.lo, bias=W[p + ".proj_in.bias"])
-        else:
-            ops.gemm(g, W[p + ".proj_in.weight"], out=pin.hi, out_lo=pin.lo, bias=W[p + ".proj_in.bias"])
-        a1, st1 = ops.layernorm_hilo(pin.hi, pin.lo, W[t + ".norm1.weight"], W[t + ".norm1.bias"], want_stats=True)
-        qkv = ops.gemm(a1, W[t + ".attn1.qkv"])
-        o1, lse1 = ops.attn_fwd(qkv[:, :C], qkv[:, C:2 * C], qkv[:, 2 * C:], r1, heads, HW, HW, HW, dh, scale,
-                                want_lse=True, v_rows=True)
-        p1_full = self._pair(M, C) if shared else None
-        p1 = _rows_of(p1_full, M1, M) if shared else self._pair(M, C)
-        ops.gemm(o1, W[t + ".attn1.to_out.0.weight"], out=p1.hi, out_lo=p1.lo, bias=W[t + ".attn1.to_out.0.bias"],
-                 residual=pin.hi, residual_lo=pin.lo)
-        x_c, p1_c = x, p1
-        if self.inject is not None:
-            if shared and getattr(self.inject, "halves_equal", False):
-                nf = self._pair(M, C)
-                p1 = self.inject(t, p1, rows, HW, heads, cond_only=True, out=_rows_of(nf, M1, M))
-                p1_full = nf
-            else:
-                if shared:                                    # the injected K / V differ between the halves: diverge here
-                    ops.batch_copy(p1.full, M1, p1_full.full, M1, 1, M1)
-                    x, p1, shared = x_full, p1_full, False
-                p1 = self.inject(t, p1, rows, HW, heads)
-            p1_c = p1
-        cb = self.ctx["blocks"][t + ".attn2"]
-        xab = (_XATTN_BLOCK and (not keep or (_XATTN_KEEP_HP and rows % 2 == 0)) and "kvpack" in cb and heads in _XATTN_HEADS and HW % 128 == 0)
-        xk_half = ()
-        if xab:
-            # norm2 -> to_q -> text attention -> to_out + residual in ONE row-local launch on the pair; in a guided step the same
-            # launch stores what the backward of the cond rows reads (skg_xattn_block_f16_hilo_keep), as _tr_fwd does
-            if shared:
-                ops.batch_copy(p1.full, M1, p1_full.full, M1, 1, M1)
-                x, p1, shared = x_full, p1_full, False
-            xargs = (HW, heads, self.ctx["L"], W[t + ".norm2.weight"], W[t + ".norm2.bias"], 1e-5, W[t + ".attn2.xpack"], cb["kvpack"],
-                     W[t + ".attn2.to_out.0.bias"], scale)
-            if keep:
-                p2, st2, q2_c, o2, lse2 = ops.xattn_block(p1, *xargs, keep_from=(rows // 2) * HW)
-                q2 = q2_c
-                xk_half = ("st2", "q2", "o2", "lse2")
-            else:
-                p2 = ops.xattn_block(p1, *xargs)
-                st2 = q2 = q2_c = o2 = lse2 = None
-        else:
-            a2, st2 = ops.layernorm_hilo(p1.hi, p1.lo, W[t + ".norm2.weight"], W[t + ".norm2.bias"], want_stats=True)
-            q2_full = torch.empty(M, C, device=self.dev, dtype=torch.float16) if shared else None
-            q2 = ops.gemm(a2, W[t + ".attn2.to_q.weight"], q2_full[M1:] if shared else None)
-            q2_c = q2
-            if shared:      # the text-dependent part needs both halves: one copy each into the uncond half
-                ops.batch_copy(p1.full, M1, p1_full.full, M1, 1, M1)
-                ops.batch_copy(q2, M1, q2_full, M1, 1, M1)
-                x, p1, q2 = x_full, p1_full, q2_full
-            o2, lse2 = ops.attn_fwd(q2, cb["K"], cb["V"], rows, heads, HW, self.ctx["L"], self.ctx["Lp"], dh, scale,
-                                    want_lse=True, v_rows=True)
-            p2 = self._pair(M, C)
-            ops.gemm(o2, W[t + ".attn2.to_out.0.weight"], out=p2.hi, out_lo=p2.lo, bias=W[t + ".attn2.to_out.0.bias"],
-                     residual=p1.hi, residual_lo=p1.lo)
-        ffb = _FF_BLOCK and (t + ".ff.pack") in W and (not keep or (rows % 2 == 0 and _FF_KEEP))
-        f = None
-        ffp = ffb and _FF_PROJ and _FF_PROJ_HP and (t + ".ff.packp") in W and HW % 128 == 0
-
-        def keep_entry(st3, f):
-            # the stash entry of a guided step (the backward differentiates the fp16 - hi - values)
-            # half: which tensors of the text-independent part hold the cond rows only - derived from their shapes, as _tr_fwd does
-            # (with an injector the shared front ends earlier: x / p1 / q2 are full size while gst .. lse1 are not)
-            own = r1 != rows and self.inject is None
-            ent = dict(x=(x_c if own else x).hi, gst=gst, pin=pin.hi, st1=st1, qkv=qkv, o1=o1, lse1=lse1, p1=(p1_c if own else p1).hi,
-                       st2=st2, q2=q2_c if own else q2)
-            half = self._stash_half(ent, r1, rows, HW)
-            half = tuple(k for k in half if k not in xk_half) + xk_half
-            stash.tr[p] = dict(ent, o2=o2, lse2=lse2, p2=p2.hi, st3=st3, f=f, sz=sz, heads=heads, half=half)
-
-        if ffp:
-            # ... with proj_out (on the pair p3 = hi + lo: W . hi + W . lo on the same fragments) and the outer residual pair in the
-            # same launch (skg_ff_block_proj_f16_hilo): the K-doubled proj_out GEMM and the [M, 2C] round trip of p3 disappear
-            out = out or self._pair(M, C)
-            gn = (HW, self.cfg.norm_groups) if want_part and self._gn_from_producer(rows, HW, C) else None
-            _, st3, f, opart = ops.ff_block_proj(p2, W[t + ".norm3.weight"], W[t + ".norm3.bias"], 1e-5, W[t + ".ff.packp"], W[t + ".ff.bias1"],
-                                                 W[t + ".ff.net.2.bias"], W[p + ".proj_out.bias"], x, out=out, want_stats=keep,
-                                                 keep_from=(rows // 2) * HW if keep else None, gn=gn)
-            if keep:
-                keep_entry(st3, f)
-            return out, opart
-        if ffb:
-            # C = 320: norm3 -> FF1 -> gate -> FF2 + residual in ONE row-local launch on the pair (guided steps: the same launch
-            # stores the cond rows' FF1 output and norm3's statistics for the backward)
-            ffargs = (W[t + ".norm3.weight"], W[t + ".norm3.bias"], 1e-5, W[t + ".ff.pack"], W[t + ".ff.bias1"], W[t + ".ff.net.2.bias"])
-            st3 = None
-            if keep:
-                p3, st3, f = ops.ff_block(p2, *ffargs, want_stats=True, keep_from=(rows // 2) * HW)
-            else:
-                p3 = ops.ff_block(p2, *ffargs)
-        else:
-            a3, st3 = ops.layernorm_hilo(p2.hi, p2.lo, W[t + ".norm3.weight"], W[t + ".norm3.bias"], want_stats=True)
-            if keep and C % 64 == 0 and rows % 2 == 0:     # guided step: the cond half's gate also keeps its pre-activation
-                M0 = (rows // 2) * HW
-                gg = torch.empty(M, 4 * C, device=self.dev, dtype=torch.float16)
-                ops.gemm(a3[:M0], W[t + ".ff.net.0.proj.weight"], bias=W[t + ".ff.net.0.proj.bias"], geglu=True, out=gg[:M0])
-                _, f = ops.gemm_geglu_keep(a3[M0:], W[t + ".ff.net.0.proj.weight"], W[t + ".ff.net.0.proj.bias"], out=gg[M0:])
-            elif C % 64 == 0:
-                gg = ops.gemm(a3, W[t + ".ff.net.0.proj.weight"], bias=W[t + ".ff.net.0.proj.bias"], geglu=True)
-            else:
-                ff = ops.gemm(a3, W[t + ".ff.net.0.proj.weight"], bias=W[t + ".ff.net.0.proj.bias"])
-                gg = ops.geglu(ff, interleaved=True)
-                f = ff[(rows // 2) * HW:]
-            p3 = self._pair(M, C)
-            ops.gemm(gg, W[t + ".ff.net.2.weight"], out=p3.hi, out_lo=p3.lo, bias=W[t + ".ff.net.2.bias"],
-                     residual=p2.hi, residual_lo=p2.lo)
-        if keep:
-            keep_entry(st3, f)
-        out = out or self._pair(M, C)
-        opart = None
-        if want_part and self._gn_from_producer(rows, HW, C):
-            _, opart = ops.gemm(p3.full, W[p + ".proj_out.weight:2"], out=out.hi, out_lo=out.lo, bias=W[p + ".proj_out.bias"],
-                                residual=x.hi, residual_lo=x.lo, gn_stats=(HW, self.cfg.norm_groups))
-        else:
-            ops.gemm(p3.full, W[p + ".proj_out.weight:2"], out=out.hi, out_lo=out.lo, bias=W[p + ".proj_out.bias"],
-                     residual=x.hi, residual_lo=x.lo)
-        return out, opart
 
     # ------------------------------------------------------------------ modules, backward (cond rows)
     def _res_bwd(self, p, dout, S, st: dict, r0: Optional[int] = None):

@@ -582,7 +582,7 @@ def test_lgp_train_step_end_to_end_tiny(tiny):
 @pytest.mark.parametrize("residual_fp32", [False, True])
 def test_declined_conv_shortcut_fold_falls_back_to_two_launches(monkeypatch, residual_fp32):
     """skg_conv3x3_sc_f16 DECLINES (SKG_E_UNSUPPORTED, tests/test_host.py checks the return code of the C ABI on a
-    >= 2 GiB operand) and HipUNet._res_fwd / _res_fwd_hp then run conv2 and the shortcut GEMM as two launches from packs that are
+    >= 2 GiB operand) and HipUNet._res_fwd then runs conv2 and the shortcut GEMM as two launches from packs that are
     built on first use.  Forced here by making every conv3x3_sc call decline: the evaluation must equal the fused one up to the fp16
     rounding of the shortcut output that the fold removes (default mode) / to pair accuracy (accuracy mode), taps included; the
     accuracy mode's upsampler fall-back keeps the hi-only operand of the launch it replaces."""
@@ -633,3 +633,86 @@ def test_declined_conv_shortcut_fold_falls_back_to_two_launches(monkeypatch, res
     with torch.no_grad():
         C, _ = ounet.unet_forward(ocfg, W, x, 500, ehs)
     assert report("eps, declined path vs fp32 oracle", e1, C)[0] < (8e-4 if residual_fp32 else 2.5e-3)
+
+
+# ------------------------------------------------------------------- a narrow net whose first level is 320 wide: the fused C = 320 launches
+_WIDE320 = {}
+# measured on the code with two block implementations per mode x 1.5 (shared against doubled: bit-identical there, so the bound is 0)
+_WIDE320_BOUNDS = {False: dict(eps=1.2e-3, taps=2.5e-3, dx=2.3e-3, eps_sd=0.0, taps_sd=0.0, dx_sd=0.0),
+                   True: dict(eps=2.9e-4, taps=1.5e-3, dx=1.8e-3, eps_sd=0.0, taps_sd=0.0, dx_sd=0.0)}
+
+
+def _wide320_case():
+    """Inputs and the fp32 oracle's results (eps, taps, d/dx of the cond rows), computed once for both modes."""
+    if not _WIDE320:
+        import dataclasses
+        from oracle import unet as ounet
+        from sketch2img_amd.config import TINY
+        rep = dict(block_out_channels=(320, 64, 128, 128), num_heads=(8, 2, 4, 4))
+        cfg, ocfg = dataclasses.replace(TINY, **rep), dataclasses.replace(ounet.TINY, **rep)
+        W = ounet.init_weights(ocfg)
+        S, h = 2, 32
+        g = torch.Generator().manual_seed(47)
+        x = torch.randn(S, 4, h, h, generator=g)
+        xx = torch.cat([x, x]).half().float()
+        ehs = torch.randn(2 * S, 77, cfg.cross_attention_dim, generator=g).half().float()
+        xr = xx.clone().requires_grad_(True)
+        re, rt = ounet.unet_forward(ocfg, W, xr, 500, ehs)
+        tg = [torch.randn(S, r.shape[1], r.shape[2], r.shape[3], generator=g).half().float() for r in rt]
+        gr = torch.autograd.grad(sum((r[S:] * t).sum() for r, t in zip(rt, tg)), xr)[0][S:]
+        _WIDE320.update(cfg=cfg, W=W, S=S, h=h, xx=xx, ehs=ehs, tg=tg, eps=re.detach(), taps=[r.detach() for r in rt], grad=gr)
+    return _WIDE320
+
+
+@pytest.mark.parametrize("residual_fp32", [False, True])
+def test_wide320_net_fused_stashing_launches_vs_oracle(monkeypatch, residual_fp32):
+    """The fused C = 320 launches (ops.xattn_block, ops.ff_block_proj) with a stash, on fp16 tensors and on pairs, in a net small
+    enough for a test: TINY with block_out_channels (320, 64, 128, 128), heads (8, 2, 4, 4) - 38 M parameters - at 32 x 32 latents
+    (HW = 1024: the statistics-from-producer arms and ff_block_proj's gn= output too), 4 rows = 2 samples CFG-doubled, t = 500.
+    Stashing forward without and with the shared CFG front: eps and the nine taps against the fp32 oracle, shared against doubled,
+    backward(stash, tap gradients of the cond rows) for both stashes against torch.autograd.grad on the oracle.  The launch counters
+    are conditions, not measurements: without them the test could pass on the unfused arms alone.
+    Measured on the code with two block implementations per mode, the same without and with the shared front (bounds = measured
+    x 1.5; the accuracy mode's eps bound is tighter than the default mode's): default mode eps rel 8.15e-4, worst tap 1.67e-3 (tap 6),
+    d/dx 1.55e-3; accuracy mode eps 1.98e-4, worst tap 1.00e-3 (tap 6), d/dx 1.21e-3; shared against doubled: eps, all nine taps
+    and d/dx bit-identical in both modes (the half-size launches of this net run the same kernel instantiations)."""
+    from sketch2img_amd import ops
+    from sketch2img_amd.unet import CIN_PAD, HipUNet, Stash
+    c = _wide320_case()
+    S, h, rows = c["S"], c["h"], 2 * c["S"]
+    net = HipUNet(c["cfg"], c["W"], DEV, residual_fp32=residual_fp32)
+    assert not residual_fp32 or net.hp_norm_pairs
+    net.prepare_context(c["ehs"])
+    calls = {"xattn_block": [], "ff_block_proj": []}
+    for name, log in calls.items():
+        def counted(X, *a, _f=getattr(ops, name), _log=log, **k):
+            _log.append((isinstance(X, ops.Pair), k.get("keep_from")))
+            return _f(X, *a, **k)
+        monkeypatch.setattr(ops, name, counted)
+    x32 = ops.nchw_to_nhwc(c["xx"].to(DEV), CIN_PAD)
+    tgrads = [nhwc16(t) for t in c["tg"]]
+    tag = f"wide320 residual_fp32={residual_fp32}"
+    B = _WIDE320_BOUNDS[residual_fp32]
+    fig, got = {}, {}
+    for shared in (False, True):
+        stash = Stash()
+        eps, taps = net.forward(x32, 500, rows, h, stash, shared_input=shared)
+        for name, log in calls.items():
+            assert any(kf is not None for _, kf in log), f"{name}: no stashing launch (shared={shared})"
+            assert all(pr == residual_fp32 for pr, _ in log), f"{name}: representation of the first argument"
+            log.clear()
+        dx = net.backward(stash, tgrads)
+        assert dx[:, 4:].abs().max() == 0
+        e = ops.nhwc_to_nchw(eps, rows, 4, h, h).cpu()
+        tp = [from_nhwc(t, rows, s, s) for t, s in taps]
+        d = ops.nhwc_to_nchw(dx, S, 4, h, h).cpu()
+        got[shared] = (e, tp, d)
+        fig["eps", shared] = report(f"{tag} shared={shared}: eps", e, c["eps"])[0]
+        fig["taps", shared] = max(report(f"{tag} shared={shared}: tap{i}", a, r)[0] for i, (a, r) in enumerate(zip(tp, c["taps"])))
+        fig["dx", shared] = report(f"{tag} shared={shared}: d/dx", d, c["grad"])[0]
+    fig["eps", "sd"] = report(f"{tag}: eps, shared vs doubled", got[True][0], got[False][0])[0]
+    fig["taps", "sd"] = max(report(f"{tag}: tap{i}, shared vs doubled", a, b)[0] for i, (a, b) in enumerate(zip(got[True][1], got[False][1])))
+    fig["dx", "sd"] = report(f"{tag}: d/dx, shared vs doubled", got[True][2], got[False][2])[0]
+    for (what, which), v in fig.items():
+        bound = B[what + "_sd"] if which == "sd" else B[what]
+        assert v <= bound, f"{what} ({which}): {v:.3e} > {bound:.3e}"
