@@ -433,6 +433,10 @@ int skg_silu_f16(const void* X, int ldx, void* Y, int ldy, int M, int C, void* s
 /* Y = X * sigmoid(1.702 X): transformers' "quick_gelu", the MLP activation of the CLIP vision tower that
  * modules/clip_guided_inf.py:49-54,103 runs to produce the sketch tokens. */
 int skg_quick_gelu_f16(const void* X, int ldx, void* Y, int ldy, int M, int C, void* stream);
+/* Its backward: out = dY * s * (1 + 1.702 F (1 - s)) with s = sigmoid(1.702 F), F = the activation's INPUT (the fc1 output);
+ * fp32 arithmetic, fp16 [M][C] views with their own row pitches, C % 8 == 0; out may alias dY.  The MLP step of the CLIP
+ * vision tower's backward (modules/clip_guided_trainer.py:116-119 trains the tower).  Additive: same ABI version. */
+int skg_quick_gelu_bwd_f16(const void* F, int ldf, const void* dY, int lddy, void* out, int ldo, int M, int C, void* stream);
 /* Y = X/2 (1 + erf(X / sqrt 2)): exact "gelu", the MLP activation of the OpenCLIP text encoder that SD 2.x
  * checkpoints carry (transformers CLIPTextModel with hidden_act = "gelu"; modules/pipeline.py:55-57). */
 int skg_gelu_f16(const void* X, int ldx, void* Y, int ldy, int M, int C, void* stream);

@@ -130,6 +130,8 @@ SIGNATURES = {
     "skg_wgrad_f16": ("i", "pipiiiifipppp"),
     "skg_layernorm_param_scratch_floats": ("z", "i"),
     "skg_layernorm_param_grads": ("i", "pipiiipfipppp"),
+    # CLIP vision tower training (clip_vision.py forward_train / backward): additive entry point, same ABI version
+    "skg_quick_gelu_bwd_f16": ("i", "pipipiiip"),
 }
 
 _CT = {"p": ctypes.c_void_p, "i": ctypes.c_int, "f": ctypes.c_float, "u": ctypes.c_uint,

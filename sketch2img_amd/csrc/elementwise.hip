@@ -157,6 +157,28 @@ __global__ __launch_bounds__(256) void quick_gelu_kernel(const half_t* __restric
   }
 }
 
+// d quick_gelu: dF = dY * s * (1 + 1.702 f (1 - s)), s = sigmoid(1.702 f), fp32 arithmetic.  Every element is read before it
+// is written by the same thread, so dF may alias dY.
+__global__ __launch_bounds__(256) void quick_gelu_bwd_kernel(const half_t* __restrict__ Fp, int ldf, const half_t* dY, int lddy,
+                                                             half_t* dF, int ldo, int M, int C) {
+  const int C8 = C >> 3;
+  const size_t total = (size_t)M * C8;
+  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
+    const size_t m = i / C8;
+    const int c = (int)(i - m * C8) * 8;
+    const half8_t f = ld_half8(Fp + m * ldf + c);
+    const half8_t d = ld_half8(dY + m * lddy + c);
+    half8_t o;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      const float x = (float)f[j];
+      const float s = 1.f / (1.f + __expf(-1.702f * x));
+      o[j] = (half_t)((float)d[j] * (s * (1.f + 1.702f * x * (1.f - s))));
+    }
+    st_half8(dF + m * ldo + c, o);
+  }
+}
+
 // gelu(x) = x/2 (1 + erf(x / sqrt 2)): the MLP activation of the OpenCLIP text encoder SD 2.x ships (hidden_act "gelu")
 __global__ __launch_bounds__(256) void gelu_kernel(const half_t* __restrict__ X, int ldx, half_t* __restrict__ Y,
                                                    int ldy, int M, int C) {
@@ -491,6 +513,16 @@ extern "C" int skg_quick_gelu_f16(const void* X, int ldx, void* Y, int ldy, int 
   hipLaunchKernelGGL(quick_gelu_kernel, dim3(ew_grid((size_t)M * C / 8)), dim3(256), 0, (hipStream_t)stream,
                      (const half_t*)X, ldx, (half_t*)Y, ldy, M, C);
   SKG_CHECK_LAUNCH("skg_quick_gelu_f16");
+  return SKG_OK;
+}
+
+extern "C" int skg_quick_gelu_bwd_f16(const void* F, int ldf, const void* dY, int lddy, void* out, int ldo, int M, int C,
+                                      void* stream) {
+  SKG_REQUIRE(F && dY && out && M > 0 && C > 0 && C % 8 == 0 && ldf % 8 == 0 && lddy % 8 == 0 && ldo % 8 == 0);
+  SKG_REQUIRE(ldf >= C && lddy >= C && ldo >= C && skg_aligned(F, 16) && skg_aligned(dY, 16) && skg_aligned(out, 16));
+  hipLaunchKernelGGL(quick_gelu_bwd_kernel, dim3(ew_grid((size_t)M * C / 8)), dim3(256), 0, (hipStream_t)stream,
+                     (const half_t*)F, ldf, (const half_t*)dY, lddy, (half_t*)out, ldo, M, C);
+  SKG_CHECK_LAUNCH("skg_quick_gelu_bwd_f16");
   return SKG_OK;
 }
 

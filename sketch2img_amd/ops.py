@@ -737,6 +737,18 @@ def quick_gelu(X, out=None):
     return out
 
 
+def quick_gelu_bwd(F, dY, out=None):
+    """d loss / d F of Y = quick_gelu(F) from dY; out may be dY itself."""
+    _f16(F, dY, out)
+    M, C = F.shape
+    assert dY.shape == (M, C)
+    if out is None:
+        out = torch.empty(M, C, device=F.device, dtype=torch.float16)
+    check(lib.skg_quick_gelu_bwd_f16(_p(F), _ld(F), _p(dY), _ld(dY), _p(out), _ld(out), M, C, _stream()),
+          "skg_quick_gelu_bwd_f16")
+    return out
+
+
 def gelu(X, out=None):
     _f16(X)
     M, C = X.shape

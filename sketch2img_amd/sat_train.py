@@ -13,8 +13,13 @@ whole batch (skg_lgp_mse_train: the same [B*hw, >= 4] / NCHW layouts), so the se
 
 What differs from the reference, on purpose (as in lgp_train.py): accelerate's fp16 autocast + GradScaler becomes fp16 compute
 with a STATIC power-of-two loss scale and fp32 master weights; bitsandbytes' AdamW8bit becomes plain fp32 AdamW with the same
-hyper-parameters.  The CLIP vision tower, which the reference trains too, is not differentiated: loss_and_grads returns
-d loss / d sketch_state, the seam where its backward can attach.
+hyper-parameters.
+
+The CLIP vision tower, which the reference trains in the same optimizer (clip_guided_trainer.py:116-119), attaches at the seam:
+loss_and_grads returns d loss / d sketch_state, and train_step(tower=, pixel_values=) takes the sketch tokens from
+clip_vision_train.HipClipTowerTrainer.forward_train, casts d sketch_state (fp32, x LOSS_SCALE, x the tower's power-of-two seam
+scale) to fp16, runs HipCLIPVision.backward from it, all-reduces both flat gradients and steps both optimizers or - when either
+gradient is non-finite, the reference's single GradScaler - neither.  Without a tower nothing changes.
 
 Loss scale: gradients of the unscaled loss are 1e-6 ... 1e-5 and underflow fp16 (6 of the 11 parameter kinds off by 30-100 %);
 between 2^10 and 2^16 every tensor is within 5e-3 of the fp32 oracle.  LOSS_SCALE = 2^13 sits in the middle of that
@@ -206,10 +211,11 @@ class HipSatTrainer:
         return self.lr * cosine_with_restarts(self.step_count, self.warmup, self.total, self.cycles)
 
     @torch.no_grad()
-    def step(self, g: torch.Tensor) -> bool:
+    def step(self, g: torch.Tensor, checked: bool = False) -> bool:
         """AdamW on the fp32 master vector (g carries LOSS_SCALE), fp16 copy refreshed.  A non-finite gradient skips the step:
-        returns False with p, m, v and the step count untouched (the static-scale form of GradScaler's skipped step)."""
-        if not bool(torch.isfinite(g).all()):
+        returns False with p, m, v and the step count untouched (the static-scale form of GradScaler's skipped step).
+        checked=True: the caller has already found g finite (train_step with a tower decides for both optimizers at once)."""
+        if not checked and not bool(torch.isfinite(g).all()):
             return False
         lr = self.current_lr()
         self.step_count += 1
@@ -224,10 +230,38 @@ class HipSatTrainer:
 
 
 @torch.no_grad()
-def train_step(trainer: HipSatTrainer, net, latents: torch.Tensor, ehs: torch.Tensor, sketch_state: torch.Tensor,
-               timesteps: Sequence[int], noise: torch.Tensor, alphas_cumprod: torch.Tensor):
+def loss_and_grads_through_tower(trainer: HipSatTrainer, tower, net, latents, noise, timesteps, ehs, pixel_values, alphas_cumprod):
+    """HipSatTrainer.loss_and_grads fed by the tower's stashing forward, then the tower's backward from d sketch_state.
+    -> (loss, SatMixin flat gradient x LOSS_SCALE, tower flat gradient x LOSS_SCALE x tower.seam_scale, d sketch_state x LOSS_SCALE)."""
+    assert pixel_values is not None, "training through the tower needs pixel_values"
+    tokens, kept = tower.forward_train(pixel_values)
+    loss, g, dstate = trainer.loss_and_grads(net, latents, noise, timesteps, ehs, tokens, alphas_cumprod)
+    gt = tower.new_grad()
+    tower.backward(kept, tower.seam(dstate), gt)
+    return loss, g, gt, dstate
+
+
+@torch.no_grad()
+def train_step(trainer: HipSatTrainer, net, latents: torch.Tensor, ehs: torch.Tensor, sketch_state: Optional[torch.Tensor],
+               timesteps: Sequence[int], noise: torch.Tensor, alphas_cumprod: torch.Tensor, tower=None,
+               pixel_values: Optional[torch.Tensor] = None):
     """clip_guided_trainer.py:203-236 for one batch: noise the latents, UNet forward / backward per sample, gradient all-reduce
-    across ranks, AdamW.  Returns (loss (0-dim tensor), whether the optimizer stepped, d loss / d sketch_state x LOSS_SCALE)."""
-    loss, g, dstate = trainer.loss_and_grads(net, latents, noise, timesteps, ehs, sketch_state, alphas_cumprod)
+    across ranks, AdamW.  Returns (loss (0-dim tensor), whether the optimizer stepped, d loss / d sketch_state x LOSS_SCALE).
+
+    tower (a clip_vision_train.HipClipTowerTrainer) + pixel_values [B, 3, S, S]: the sketch tokens come from the tower's stashing
+    forward (sketch_state is ignored: pass None), d sketch_state goes into the tower's backward, and the two optimizers step
+    together or not at all."""
+    if tower is None:
+        loss, g, dstate = trainer.loss_and_grads(net, latents, noise, timesteps, ehs, sketch_state, alphas_cumprod)
+        trainer.all_reduce(g)
+        return loss, trainer.step(g), dstate
+    loss, g, gt, dstate = loss_and_grads_through_tower(trainer, tower, net, latents, noise, timesteps, ehs, pixel_values, alphas_cumprod)
     trainer.all_reduce(g)
-    return loss, trainer.step(g), dstate
+    tower.all_reduce(gt)
+    # one GradScaler in the reference: a non-finite gradient in either set skips both.  The verdict is taken here, once per
+    # vector (the tower's is ~3e8 floats), and handed down.
+    if not (bool(torch.isfinite(g).all()) and bool(torch.isfinite(gt).all())):
+        return loss, False, dstate
+    trainer.step(g, checked=True)
+    tower.step(gt, checked=True)
+    return loss, True, dstate
