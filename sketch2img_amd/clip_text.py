@@ -18,18 +18,13 @@ from typing import Dict, List, Optional
 
 import torch
 
-from . import ops
+from . import clip_encoder, ops
+from .clip_encoder import CLIPFacade, _round_up, encoder_layers, pack_layers, state_dict_accessors
 from .config import CLIPTextConfig, SD15_TEXT, SD21_TEXT
-from .unet import _h
-
-
-def _round_up(x: int, m: int) -> int:
-    return (x + m - 1) // m * m
 
 
 def strip_prefix(sd: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
-    """transformers 4.x prefixes the keys with ``text_model.``; 5.x does not.  Both load."""
-    return {(k[len("text_model."):] if k.startswith("text_model.") else k): v for k, v in sd.items()}
+    return clip_encoder.strip_prefix(sd, "text_model.")
 
 
 class HipCLIPText:
@@ -37,25 +32,11 @@ class HipCLIPText:
         if cfg.hidden_act not in ("quick_gelu", "gelu"):
             raise ValueError(f"CLIP text encoder: unsupported hidden_act {cfg.hidden_act!r}")
         self.cfg, self.dev = cfg, torch.device(device)
-        self.W = self._pack(strip_prefix(state_dict))
-
-    def _pack(self, sd):
-        cfg, dev = self.cfg, self.dev
-        W: Dict[str, torch.Tensor] = {}
-        W["tok"] = _h(sd["embeddings.token_embedding.weight"].detach().float(), dev)
-        W["pos"] = _h(sd["embeddings.position_embedding.weight"].detach().float(), dev)
+        h16, _ = state_dict_accessors(strip_prefix(state_dict), self.dev)
+        W = self.W = {"tok": h16("embeddings.token_embedding.weight"), "pos": h16("embeddings.position_embedding.weight")}
         for k in ("final_layer_norm.weight", "final_layer_norm.bias"):
-            W[k] = _h(sd[k].detach().float(), dev)
-        for l in range(cfg.num_hidden_layers):
-            p = f"encoder.layers.{l}"
-            W[p + ".qkv.weight"] = _h(torch.cat([sd[f"{p}.self_attn.{n}.weight"].detach().float()
-                                                 for n in ("q_proj", "k_proj", "v_proj")]), dev)
-            W[p + ".qkv.bias"] = _h(torch.cat([sd[f"{p}.self_attn.{n}.bias"].detach().float()
-                                               for n in ("q_proj", "k_proj", "v_proj")]), dev)
-            for n in ("self_attn.out_proj", "mlp.fc1", "mlp.fc2", "layer_norm1", "layer_norm2"):
-                W[f"{p}.{n}.weight"] = _h(sd[f"{p}.{n}.weight"].detach().float(), dev)
-                W[f"{p}.{n}.bias"] = _h(sd[f"{p}.{n}.bias"].detach().float(), dev)
-        return W
+            W[k] = h16(k)
+        pack_layers(W, h16, cfg.num_hidden_layers)
 
     def to(self, device):
         if torch.device(device) != self.dev:
@@ -73,26 +54,14 @@ class HipCLIPText:
         ids = input_ids.to(self.dev, torch.long)
         if int(ids.min()) < 0 or int(ids.max()) >= cfg.vocab_size:
             raise ValueError("CLIP text encoder: token id outside the vocabulary")
-        D, H = cfg.hidden_size, cfg.num_attention_heads
-        d, Lp = D // H, _round_up(L, 8)
+        D, Lp = cfg.hidden_size, _round_up(L, 8)
         tok = torch.zeros(B, Lp, D, device=self.dev, dtype=torch.float16)
         pos = torch.zeros(B, Lp, D, device=self.dev, dtype=torch.float16)
         tok[:, :L] = W["tok"].index_select(0, ids.reshape(-1)).view(B, L, D)       # row gather: data movement only
         pos[:, :L] = W["pos"][:L]
         x = ops.axpby(tok.view(B * Lp, D), pos.view(B * Lp, D))
         act = ops.quick_gelu if cfg.hidden_act == "quick_gelu" else ops.gelu
-        scale = d ** -0.5
-        for l in range(cfg.num_hidden_layers):
-            p = f"encoder.layers.{l}"
-            h = ops.layernorm(x, W[p + ".layer_norm1.weight"], W[p + ".layer_norm1.bias"], cfg.layer_norm_eps)
-            qkv = ops.gemm(h, W[p + ".qkv.weight"], bias=W[p + ".qkv.bias"])
-            vt = ops.transpose(qkv[:, 2 * D:])
-            a = ops.attn_fwd(qkv[:, :D], qkv[:, D:2 * D], vt, B, H, Lp, L, Lp, d, scale, causal=True)
-            x = ops.gemm(a, W[p + ".self_attn.out_proj.weight"], bias=W[p + ".self_attn.out_proj.bias"], residual=x)
-            h = ops.layernorm(x, W[p + ".layer_norm2.weight"], W[p + ".layer_norm2.bias"], cfg.layer_norm_eps)
-            f = ops.gemm(h, W[p + ".mlp.fc1.weight"], bias=W[p + ".mlp.fc1.bias"])
-            act(f, out=f)
-            x = ops.gemm(f, W[p + ".mlp.fc2.weight"], bias=W[p + ".mlp.fc2.bias"], residual=x)
+        x = encoder_layers(x, W, cfg, B, Lp, L, act, causal=True)
         x = ops.layernorm(x, W["final_layer_norm.weight"], W["final_layer_norm.bias"], cfg.layer_norm_eps)
         return x.view(B, Lp, D)[:, :L].contiguous()
 
@@ -117,16 +86,14 @@ def _config_from_folder(path: Optional[str]) -> CLIPTextConfig:
     return SD15_TEXT
 
 
-class CLIPTextModel:
+class CLIPTextModel(CLIPFacade):
     """Facade with the surface diffusers' _encode_prompt uses of transformers.CLIPTextModel: ``from_pretrained(path)``,
     ``load_state_dict(sd)``, ``.to(device)``, ``.device`` / ``.dtype`` / ``.config``, ``model(input_ids)[0]``."""
+    ENGINE, PREFIX, WHAT = HipCLIPText, "text_model.", "the encoder"
 
     def __init__(self, cfg: CLIPTextConfig = SD15_TEXT, state_dict: Optional[Dict[str, torch.Tensor]] = None):
         from . import synthetic
-        self.cfg = self.config = cfg
-        self._sd = strip_prefix(state_dict) if state_dict is not None else synthetic.clip_text_state_dict(cfg)
-        self._hip: Optional[HipCLIPText] = None
-        self.device, self.dtype = torch.device("cpu"), torch.float16
+        super().__init__(cfg, state_dict, synthetic.clip_text_state_dict)
 
     @classmethod
     def from_pretrained(cls, pretrained_model_name_or_path=None, config: Optional[CLIPTextConfig] = None,
@@ -134,50 +101,13 @@ class CLIPTextModel:
         path = pretrained_model_name_or_path
         if path and subfolder:
             path = os.path.join(path, subfolder)
-        sd = None
-        if path and os.path.isdir(path):
-            st, pt = os.path.join(path, "model.safetensors"), os.path.join(path, "pytorch_model.bin")
-            if os.path.exists(st):
-                from safetensors.torch import load_file
-                sd = load_file(st)
-            elif os.path.exists(pt):
-                sd = torch.load(pt, map_location="cpu")
-            if sd is not None:
-                sd = {k: v for k, v in sd.items() if "position_ids" not in k}
+        sd = cls.read_folder(path)
+        if sd is not None:
+            sd = {k: v for k, v in sd.items() if "position_ids" not in k}
         return cls(config or _config_from_folder(path), sd)
 
-    def state_dict(self):
-        return self._sd
-
-    def load_state_dict(self, sd, strict: bool = True):
-        sd = strip_prefix(sd)
-        missing = [k for k in self._sd if k not in sd and "position_ids" not in k]
-        if strict and missing:
-            raise RuntimeError(f"CLIPTextModel.load_state_dict: missing keys {missing[:4]} ...")
-        self._sd = {k: v for k, v in sd.items() if "position_ids" not in k}
-        if self._hip is not None:
-            self._hip = HipCLIPText(self.cfg, self._sd, self.device)
-        return self
-
-    def to(self, device=None, dtype=None):
-        if isinstance(device, torch.dtype):
-            device, dtype = None, device
-        if device is not None:
-            self.device = torch.device(device)
-            if self.device.type == "cuda":
-                if self._hip is None:
-                    self._hip = HipCLIPText(self.cfg, self._sd, self.device)
-                else:
-                    self._hip.to(self.device)
-        return self
-
-    def eval(self):
-        return self
-
     def __call__(self, input_ids, attention_mask=None, **kwargs):
-        if self._hip is None:
-            raise RuntimeError("CLIPTextModel: call .to('cuda') first - the encoder runs on libskg.so kernels only")
-        return _TextOutput(self._hip.last_hidden_state(input_ids))
+        return _TextOutput(self.engine().last_hidden_state(input_ids))
 
 
 class PromptEncoder:

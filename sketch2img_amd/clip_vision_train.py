@@ -1,7 +1,7 @@
 """Optimizer state of the CLIP vision tower for the SatMixin training step (reference trainer: modules/clip_guided_trainer.py:116-119
 puts ``sketch_encoder.parameters()`` into the same optimizer as the 16 injected modules; :264 saves it as sketch_encoder_model.pt).
 
-HipClipTowerTrainer owns a flat fp32 master vector, its fp16 working copy and AdamW's m / v, and drives
+HipClipTowerTrainer is a flat_adamw.FlatAdamW (flat fp32 master vector, its fp16 working copy, AdamW's m / v) that drives
 clip_vision.HipCLIPVision.forward_train / backward on views of the working copy.  Same hyper-parameters and the same
 cosine_with_restarts schedule as sat_train.HipSatTrainer (one optimizer in the reference); sat_train.train_step(tower=...) steps both
 or neither.
@@ -23,10 +23,10 @@ from typing import Dict, Optional, Tuple
 
 import torch
 
-from . import ops
 from .clip_vision import HipCLIPVision, strip_prefix
 from .config import CLIPVisionConfig
-from .sat_train import LOSS_SCALE, cosine_with_restarts
+from .flat_adamw import FlatAdamW, cosine_with_restarts
+from .sat_train import LOSS_SCALE
 from .synthetic import clip_vision_param_shapes
 
 # 2^8 on top of LOSS_SCALE = 2^13.  profiles/clip_loss_scale.txt: at the 16 x 16, B = 2 test size the tower's gradients are flat from
@@ -50,63 +50,30 @@ def flat_order(cfg: CLIPVisionConfig):
     return keys + list(_FROZEN)
 
 
-class HipClipTowerTrainer:
+class HipClipTowerTrainer(FlatAdamW):
     def __init__(self, cfg: CLIPVisionConfig, state_dict: Dict[str, torch.Tensor], device="cuda", lr: float = 2e-4,
                  betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 1e-2, warmup_steps: int = 150,
                  total_steps: int = 10000, num_cycles: int = 1, seam_scale: float = SEAM_SCALE):
-        dev = self.dev = torch.device(device)
         self.cfg = cfg
-        self.lr, self.betas, self.eps, self.wd = lr, betas, eps, weight_decay
-        self.warmup, self.total, self.cycles = warmup_steps, total_steps, num_cycles
         self.seam_scale = float(seam_scale)
         assert math.frexp(self.seam_scale)[0] == 0.5, "the seam scale must be a power of two"
-        self.step_count = 0
         D = cfg.hidden_size
         assert D % 8 == 0, "q / k / v must stay adjacent: hidden_size % 8 == 0"
-        sd = strip_prefix(state_dict)
         shapes = clip_vision_param_shapes(cfg)
-        self.layout: Dict[str, Tuple[int, torch.Size]] = {}
-        off = 0
-        for k in flat_order(cfg):
-            assert tuple(sd[k].shape) == tuple(shapes[k]), (k, tuple(sd[k].shape), shapes[k])
-            self.layout[k] = (off, torch.Size(shapes[k]))
-            if k == _FROZEN[0]:
-                self.n_opt = off                   # AdamW runs on [0, n_opt)
-            off += (math.prod(shapes[k]) + 7) // 8 * 8
-        self.n = off
+        super().__init__([(k, shapes[k]) for k in flat_order(cfg)], strip_prefix(state_dict), device, lr, betas, eps, weight_decay,
+                         lambda s: cosine_with_restarts(s, warmup_steps, total_steps, num_cycles),
+                         LOSS_SCALE * self.seam_scale, frozen=_FROZEN)
         # the fused views: q, k, v of a layer are adjacent and unpadded (D * D and D are multiples of 8)
         self.fused: Dict[str, Tuple[int, torch.Size]] = {}
         for l in range(cfg.num_hidden_layers):
             p = f"encoder.layers.{l}.self_attn"
             self.fused[p + ".qkv.weight"] = (self.layout[p + ".q_proj.weight"][0], torch.Size((3 * D, D)))
             self.fused[p + ".qkv.bias"] = (self.layout[p + ".q_proj.bias"][0], torch.Size((3 * D,)))
-        self.p = torch.zeros(off, device=dev, dtype=torch.float32)
-        for k, (o, shp) in self.layout.items():
-            self.p[o:o + shp.numel()] = sd[k].detach().to(dev, torch.float32).reshape(-1)
-        self.p16 = self.p.to(torch.float16)
-        self.m = torch.zeros_like(self.p)
-        self.v = torch.zeros_like(self.p)
         self.vision: Optional[HipCLIPVision] = None        # built (packs and all) by the first forward_train
         self._packs_stale = False
 
-    # ------------------------------------------------------------------------------------------ views
     def _at(self, key: str) -> Tuple[int, torch.Size]:
         return self.layout[key] if key in self.layout else self.fused[key]
-
-    def w16(self, key: str) -> torch.Tensor:
-        o, shp = self._at(key)
-        return self.p16[o:o + shp.numel()].view(shp)
-
-    def w32(self, key: str) -> torch.Tensor:
-        o, shp = self._at(key)
-        return self.p[o:o + shp.numel()].view(shp)
-
-    def grad_view(self, g: torch.Tensor, key: str) -> torch.Tensor:
-        o, shp = self._at(key)
-        return g[o:o + shp.numel()].view(shp)
-
-    def new_grad(self) -> torch.Tensor:
-        return torch.zeros(self.n, device=self.dev, dtype=torch.float32)
 
     # ------------------------------------------------------------------------------------------ fwd + bwd
     def forward_train(self, pixel_values: torch.Tensor):
@@ -131,33 +98,13 @@ class HipClipTowerTrainer:
         """d loss / d sketch_state fp32 (x LOSS_SCALE) -> the fp16 seed of the tower's backward (x LOSS_SCALE * seam_scale)."""
         return (dstate * self.seam_scale).to(torch.float16)
 
-    # ------------------------------------------------------------------------------------------ collective
-    def all_reduce(self, g: torch.Tensor, bucket_bytes: int = 15 << 20) -> torch.Tensor:
-        from .dist import allreduce_mean_
-        return allreduce_mean_(g, bucket_bytes)
-
     # ------------------------------------------------------------------------------------------ optimizer
-    def current_lr(self) -> float:
-        return self.lr * cosine_with_restarts(self.step_count, self.warmup, self.total, self.cycles)
-
-    @torch.no_grad()
     def step(self, g: torch.Tensor, checked: bool = False) -> bool:
-        """AdamW on the master vector (g carries LOSS_SCALE * seam_scale), fp16 copy refreshed.  A non-finite gradient skips the
-        step: False, with p, m, v and the step count untouched.  checked=True: the caller has already found g finite."""
-        if not checked and not bool(torch.isfinite(g).all()):
-            return False
-        lr = self.current_lr()
-        self.step_count += 1
-        n = self.n_opt
-        ops.adamw_step(self.p[:n], g[:n], self.m[:n], self.v[:n], self.p16[:n], lr, self.betas[0], self.betas[1], self.eps, self.wd,
-                       self.step_count, 1.0 / (LOSS_SCALE * self.seam_scale))
-        self._packs_stale = True
-        return True
+        """FlatAdamW.step (g carries LOSS_SCALE * seam_scale, AdamW runs on [0, n_opt)); a step that ran leaves the tower's packs stale."""
+        stepped = super().step(g, checked)
+        self._packs_stale = self._packs_stale or stepped
+        return stepped
 
     def state_dict(self) -> Dict[str, torch.Tensor]:
         """The reference's sketch_encoder_model.pt: fp32 masters under transformers' CLIPVisionModel keys, in its order."""
-        out: Dict[str, torch.Tensor] = {}
-        for k in clip_vision_param_shapes(self.cfg):
-            o, shp = self.layout[k]
-            out[k] = self.p[o:o + shp.numel()].view(shp).clone()
-        return out
+        return super().state_dict(clip_vision_param_shapes(self.cfg))

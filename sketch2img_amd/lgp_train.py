@@ -25,49 +25,28 @@ from typing import Dict, List, Optional, Sequence, Tuple
 import torch
 
 from . import ops
+from .flat_adamw import FlatAdamW, constant_with_warmup
 from .lgp import BNS, LIN, LOSS_SCALE, OUT_PAD, SEED_LD
 
 TRAINABLE = [f"layers.{i}.{n}" for i in (0, 2, 3, 5, 6, 8, 9, 11, 12) for n in ("weight", "bias")]
 
 
-class HipLGPTrainer:
+class HipLGPTrainer(FlatAdamW):
     def __init__(self, state_dict: Dict[str, torch.Tensor], tap_channels: Sequence[int], device="cuda",
                  lr: float = 2e-4, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 1e-2,
                  warmup_steps: int = 150):
-        dev = self.dev = torch.device(device)
+        # the master vector is in the reference's state_dict order (weights, biases of the 5 Linear and 4 BN)
+        super().__init__([(k, state_dict[k].shape) for k in TRAINABLE], state_dict, device, lr, betas, eps, weight_decay,
+                         lambda s: constant_with_warmup(s, warmup_steps), LOSS_SCALE)
+        dev = self.dev
         self.tap_channels = list(tap_channels)
         self.E = sum(tap_channels)
-        self.lr, self.betas, self.eps, self.wd, self.warmup = lr, betas, eps, weight_decay, warmup_steps
-        self.step_count = 0
-        # flat fp32 master vector in the reference's state_dict order (weights, biases of the 5 Linear and 4 BN)
-        self.layout: Dict[str, Tuple[int, torch.Size]] = {}
-        off = 0
-        for k in TRAINABLE:
-            t = state_dict[k]
-            self.layout[k] = (off, t.shape)
-            off += (t.numel() + 7) // 8 * 8                  # keep every tensor 16-byte aligned in the fp16 copy
-        self.n = off
-        self.p = torch.zeros(off, device=dev, dtype=torch.float32)
-        for k, (o, shp) in self.layout.items():
-            self.p[o:o + shp.numel()] = state_dict[k].detach().to(dev, torch.float32).reshape(-1)
-        self.p16 = self.p.to(torch.float16)
-        self.m = torch.zeros_like(self.p)
-        self.v = torch.zeros_like(self.p)
         self.running_mean = [state_dict[f"layers.{i}.running_mean"].detach().to(dev, torch.float32).clone() for i in BNS]
         self.running_var = [state_dict[f"layers.{i}.running_var"].detach().to(dev, torch.float32).clone() for i in BNS]
         self.num_batches_tracked = [int(state_dict[f"layers.{i}.num_batches_tracked"]) for i in BNS]
         self.H0 = state_dict["layers.0.weight"].shape[0]
         self.out_dim = state_dict["layers.12.weight"].shape[0]
         assert state_dict["layers.0.weight"].shape[1] == self.E + 40 and self.out_dim <= OUT_PAD
-
-    # ------------------------------------------------------------------------------------------ views
-    def w16(self, key: str) -> torch.Tensor:
-        o, shp = self.layout[key]
-        return self.p16[o:o + shp.numel()].view(shp)
-
-    def grad_view(self, g: torch.Tensor, key: str) -> torch.Tensor:
-        o, shp = self.layout[key]
-        return g[o:o + shp.numel()].view(shp)
 
     # ------------------------------------------------------------------------------------------ fwd + bwd
     @torch.no_grad()
@@ -112,7 +91,7 @@ class HipLGPTrainer:
         # ---- loss and seed
         dOut, parts = ops.lgp_mse_train(out, target, B, h, SEED_LD, LOSS_SCALE)
         loss = parts.sum()
-        g = torch.zeros(self.n, device=dev, dtype=torch.float32)
+        g = self.new_grad()
         gv = lambda k: self.grad_view(g, k)
 
         def dweight(dPre: torch.Tensor, X: torch.Tensor) -> torch.Tensor:
@@ -150,34 +129,16 @@ class HipLGPTrainer:
         gW0[:, self.E:].copy_(dweight(dZ, Ex)[:, :40])
         return loss, g
 
-    # ------------------------------------------------------------------------------------------ collective
-    def all_reduce(self, g: torch.Tensor, bucket_bytes: int = 15 << 20) -> torch.Tensor:
-        """Average the flat gradient over the ranks: sketch2img_amd.dist.allreduce_mean_ (15 MB buckets like the
-        reference's DDP).  No-op on one rank."""
-        from .dist import allreduce_mean_
-        return allreduce_mean_(g, bucket_bytes)
-
     # ------------------------------------------------------------------------------------------ optimizer
-    def current_lr(self) -> float:
-        """diffusers "constant_with_warmup": lr * min(1, step / warmup) (trainer.py:133-138)."""
-        if self.warmup <= 0:
-            return self.lr
-        return self.lr * min(1.0, float(self.step_count) / float(max(1, self.warmup)))
-
-    @torch.no_grad()
-    def step(self, g: torch.Tensor):
-        lr = self.current_lr()
-        self.step_count += 1
-        ops.adamw_step(self.p, g, self.m, self.v, self.p16, lr, self.betas[0], self.betas[1], self.eps, self.wd,
-                       self.step_count, 1.0 / LOSS_SCALE)
+    def step(self, g: torch.Tensor) -> None:
+        """AdamW, unconditionally: no finiteness test (it would add a device synchronisation and a skipped step)."""
+        super().step(g, checked=True)
 
     def state_dict(self) -> Dict[str, torch.Tensor]:
         """The reference's 30-key checkpoint (fp32 master weights + running statistics)."""
         sd: Dict[str, torch.Tensor] = {}
         for i in (0, 2, 3, 5, 6, 8, 9, 11, 12):
-            for n in ("weight", "bias"):
-                o, shp = self.layout[f"layers.{i}.{n}"]
-                sd[f"layers.{i}.{n}"] = self.p[o:o + shp.numel()].view(shp).clone()
+            sd.update(super().state_dict((f"layers.{i}.weight", f"layers.{i}.bias")))
             if i in BNS:
                 l = BNS.index(i)
                 sd[f"layers.{i}.running_mean"] = self.running_mean[l].clone()

@@ -32,13 +32,13 @@ LR schedule - diffusers "cosine_with_restarts", num_cycles = 1 (clip_guided_trai
 """
 from __future__ import annotations
 
-import math
 from typing import Dict, Optional, Sequence, Tuple
 
 import torch
 
-from . import ops
+from . import lgp_train, ops
 from .config import UNetConfig
+from .flat_adamw import FlatAdamW, cosine_with_restarts  # noqa: F401 (cosine_with_restarts is re-exported)
 from .inject import CLIP_DIM, HipClipInjectorTrain, block_dims, module_name
 
 LOSS_SCALE = 8192.0        # 2^13, see the module docstring
@@ -65,16 +65,6 @@ def param_shapes(cfg: UNetConfig) -> "Dict[str, Tuple[int, ...]]":
     return out
 
 
-def cosine_with_restarts(step: int, warmup: int, total: int, cycles: int = 1) -> float:
-    """The multiplier diffusers' get_cosine_with_hard_restarts_schedule_with_warmup applies at optimizer step `step`."""
-    if step < warmup:
-        return float(step) / float(max(1, warmup))
-    p = float(step - warmup) / float(max(1, total - warmup))
-    if p >= 1.0:
-        return 0.0
-    return max(0.0, 0.5 * (1.0 + math.cos(math.pi * ((float(cycles) * p) % 1.0))))
-
-
 def mse_seed(eps16: torch.Tensor, noise: torch.Tensor, B: int, h: int, loss_scale: float = LOSS_SCALE):
     """eps16 fp16 [B*h*h, >= 4] (the UNet's output rows of all samples), noise fp32 [B, 4, h, h] ->
     (loss = mean((eps - noise)^2) over the whole batch, d eps = loss_scale * 2 (eps - noise) / numel as fp16
@@ -88,47 +78,20 @@ def mse_seed(eps16: torch.Tensor, noise: torch.Tensor, B: int, h: int, loss_scal
 
 def add_noise(latents: torch.Tensor, noise: torch.Tensor, timesteps: Sequence[int], alphas_cumprod: torch.Tensor):
     """DDPMScheduler.add_noise with host-side fp32 scalars per sample."""
-    acp = alphas_cumprod.to(torch.float32)
-    a = torch.stack([acp[int(t)] ** 0.5 for t in timesteps]).view(-1, 1, 1, 1).to(latents.device)
-    s = torch.stack([(1 - acp[int(t)]) ** 0.5 for t in timesteps]).view(-1, 1, 1, 1).to(latents.device)
-    return a * latents + s * noise
+    return lgp_train.add_noise(latents, noise, timesteps, alphas_cumprod)[0]
 
 
-class HipSatTrainer:
+class HipSatTrainer(FlatAdamW):
     def __init__(self, cfg: UNetConfig, state_dict: Dict[str, torch.Tensor], device="cuda", lr: float = 2e-4,
                  betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 1e-2, warmup_steps: int = 150,
                  total_steps: int = 10000, num_cycles: int = 1, scale: float = 1.0):
-        dev = self.dev = torch.device(device)
+        # the master vector is in the checkpoint's key order: state_dict() is the reference's sketch_attn_model.pt
+        super().__init__(list(param_shapes(cfg).items()), state_dict, device, lr, betas, eps, weight_decay,
+                         lambda s: cosine_with_restarts(s, warmup_steps, total_steps, num_cycles), LOSS_SCALE)
         self.cfg = cfg
-        self.lr, self.betas, self.eps, self.wd = lr, betas, eps, weight_decay
-        self.warmup, self.total, self.cycles = warmup_steps, total_steps, num_cycles
-        self.step_count = 0
-        # flat fp32 master vector in the checkpoint's key order, every tensor 16-byte aligned in the fp16 copy
-        self.layout: Dict[str, Tuple[int, torch.Size]] = {}
-        off = 0
-        for k, shp in param_shapes(cfg).items():
-            assert tuple(state_dict[k].shape) == tuple(shp), (k, tuple(state_dict[k].shape), shp)
-            self.layout[k] = (off, torch.Size(shp))
-            off += (math.prod(shp) + 7) // 8 * 8
-        self.n = off
-        self.p = torch.zeros(off, device=dev, dtype=torch.float32)
-        for k, (o, shp) in self.layout.items():
-            self.p[o:o + shp.numel()] = state_dict[k].detach().to(dev, torch.float32).reshape(-1)
-        self.p16 = self.p.to(torch.float16)
-        self.m = torch.zeros_like(self.p)
-        self.v = torch.zeros_like(self.p)
-        self.injector = HipClipInjectorTrain(cfg, self.w16, self.grad_view, dev)
+        self.injector = HipClipInjectorTrain(cfg, self.w16, self.grad_view, self.dev)
         self.injector.set_scale(scale)
         self._packs_stale = True
-
-    # ------------------------------------------------------------------------------------------ views
-    def w16(self, key: str) -> torch.Tensor:
-        o, shp = self.layout[key]
-        return self.p16[o:o + shp.numel()].view(shp)
-
-    def grad_view(self, g: torch.Tensor, key: str) -> torch.Tensor:
-        o, shp = self.layout[key]
-        return g[o:o + shp.numel()].view(shp)
 
     # ------------------------------------------------------------------------------------------ fwd + bwd
     @torch.no_grad()
@@ -160,7 +123,7 @@ class HipSatTrainer:
         state16 = sketch_state.to(dev, torch.float16)
         T = state16.shape[1]
         hw = h * h
-        g = torch.zeros(self.n, device=dev, dtype=torch.float32)
+        g = self.new_grad()
         dstate = torch.zeros(B, T, CLIP_DIM, device=dev, dtype=torch.float32)
         prev = net.inject
         net.inject = self.injector
@@ -200,33 +163,12 @@ class HipSatTrainer:
             net.inject, net.ctx = prev, prev_ctx
         return fw["loss"], g, dstate
 
-    # ------------------------------------------------------------------------------------------ collective
-    def all_reduce(self, g: torch.Tensor, bucket_bytes: int = 15 << 20) -> torch.Tensor:
-        """Average the flat gradient over the ranks: dist.allreduce_mean_ (15 MB buckets like the reference's DDP)."""
-        from .dist import allreduce_mean_
-        return allreduce_mean_(g, bucket_bytes)
-
     # ------------------------------------------------------------------------------------------ optimizer
-    def current_lr(self) -> float:
-        return self.lr * cosine_with_restarts(self.step_count, self.warmup, self.total, self.cycles)
-
-    @torch.no_grad()
     def step(self, g: torch.Tensor, checked: bool = False) -> bool:
-        """AdamW on the fp32 master vector (g carries LOSS_SCALE), fp16 copy refreshed.  A non-finite gradient skips the step:
-        returns False with p, m, v and the step count untouched (the static-scale form of GradScaler's skipped step).
-        checked=True: the caller has already found g finite (train_step with a tower decides for both optimizers at once)."""
-        if not checked and not bool(torch.isfinite(g).all()):
-            return False
-        lr = self.current_lr()
-        self.step_count += 1
-        ops.adamw_step(self.p, g, self.m, self.v, self.p16, lr, self.betas[0], self.betas[1], self.eps, self.wd,
-                       self.step_count, 1.0 / LOSS_SCALE)
-        self._packs_stale = True
-        return True
-
-    def state_dict(self) -> Dict[str, torch.Tensor]:
-        """The reference's checkpoint (sketch_attn_model.pt): fp32 master weights under SatMixin's keys."""
-        return {k: self.p[o:o + shp.numel()].view(shp).clone() for k, (o, shp) in self.layout.items()}
+        """FlatAdamW.step (g carries LOSS_SCALE); a step that ran leaves the injector's packs stale."""
+        stepped = super().step(g, checked)
+        self._packs_stale = self._packs_stale or stepped
+        return stepped
 
 
 @torch.no_grad()
