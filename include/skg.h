@@ -30,7 +30,7 @@ extern "C" {
 #define SKG_E_UNSUPPORTED (-2)
 #define SKG_E_LAUNCH (-3)    /* hipGetLastError() != hipSuccess after the launch */
 
-#define SKG_ABI_VERSION 5
+#define SKG_ABI_VERSION 6
 int skg_abi_version(void);
 /* Human-readable text of the last SKG_E_LAUNCH on this thread ("" if none). */
 const char* skg_last_error(void);
@@ -49,10 +49,13 @@ const char* skg_last_error(void);
  * Replaces: every nn.Linear / 1x1 Conv2d the UNet evaluates at modules/pipeline.py:96
  * (diffusers proj_in/proj_out, to_q/k/v, to_out, ff.net, conv_shortcut -> cuBLAS/cuDNN), their
  * backward-to-input GEMMs triggered at modules/pipeline.py:159, the LGP's Linear layers at
- * modules/latent_predictor.py:45 and Conv1d(k=1) at modules/clip_guided_attn.py:124. */
-int skg_gemm_f16(const void* A, int lda, const void* B, int ldb, void* C, int ldc,
-                 int M, int N, int K, const void* bias, const void* residual, int ldr,
-                 float alpha, unsigned flags, void* stream);
+ * modules/latent_predictor.py:45 and Conv1d(k=1) at modules/clip_guided_attn.py:124.
+ * C_lo / residual_lo (either may be NULL): the lo half of an output / residual PAIR - the accuracy mode below.
+ * gn_partial != NULL: the launch also leaves the GroupNorm partial sums of its output behind (HW = rows of C per sample,
+ * `groups` groups over the N columns) - "GroupNorm whose statistics pass is done by the PRODUCER" below; else HW = groups = 0. */
+int skg_gemm_f16(const void* A, int lda, const void* B, int ldb, void* C, void* C_lo, int ldc, int M, int N, int K,
+                 const void* bias, const void* residual, const void* residual_lo, int ldr, float alpha, unsigned flags,
+                 float* gn_partial, int HW, int groups, void* stream);
 
 /* Optional split-K workspace for skg_gemm_f16 / skg_conv3x3_f16 launches on `stream` of the CURRENT device: a caller-owned
  * device buffer (>= 1 MiB, 16-byte aligned, fp32 partial slabs) that must stay valid until replaced.  With it, launches that
@@ -75,8 +78,8 @@ int skg_gemm_variant(int M, int N, int K, int Cin, int mode);
  *   mode SKG_CONV_S2A     stride 2, padding (0,1,0,1): bottom/right only (the VAE encoder's Downsample2D)  out = in / 2
  * X fp16 [rows*IH*IW][Cin] (ldx), Wp fp16 [Cout][3][3][Cin] (tap-major, Cin contiguous),
  * Y [rows*OH*OW][Cout] (ldy).  IH, IW are the INPUT sizes.  Requires Cin % 32 == 0, Cout % 8 == 0.
- * bias / residual / alpha / flags as skg_gemm_f16.  For a dgrad pass Wp is the flipped,
- * in/out-swapped pack (see sketch2img_amd/weights.py).
+ * bias / residual / alpha / flags, Y_lo / residual_lo and gn_partial / groups (HW = OH * OW) as skg_gemm_f16.  For a dgrad pass
+ * Wp is the flipped, in/out-swapped pack (see sketch2img_amd/weights.py).
  * Replaces: ResnetBlock2D conv1/conv2, Downsample2D, Upsample2D, conv_in/conv_out (cuDNN) at
  * modules/pipeline.py:96 and their dgrad at modules/pipeline.py:159. */
 #define SKG_CONV_S1 0
@@ -84,10 +87,9 @@ int skg_gemm_variant(int M, int N, int K, int Cin, int mode);
 #define SKG_CONV_UP2 2
 #define SKG_CONV_S2T 3
 #define SKG_CONV_S2A 4
-int skg_conv3x3_f16(const void* X, int ldx, const void* Wp, void* Y, int ldy,
-                    int rows, int IH, int IW, int Cin, int Cout, int mode,
-                    const void* bias, const void* residual, int ldr, float alpha,
-                    unsigned flags, void* stream);
+int skg_conv3x3_f16(const void* X, int ldx, const void* Wp, void* Y, void* Y_lo, int ldy, int rows, int IH, int IW,
+                    int Cin, int Cout, int mode, const void* bias, const void* residual, const void* residual_lo, int ldr,
+                    float alpha, unsigned flags, float* gn_partial, int groups, void* stream);
 
 /* ---- GroupNorm (+SiLU), NHWC fp16 -------------------------------------------------------------
  * stats: per (row, group) mean and rstd (float2 [rows][groups]) over HW x (C/groups) values.
@@ -100,39 +102,32 @@ size_t skg_groupnorm_scratch_floats(int rows, int groups);
 int skg_groupnorm_stats(const void* X, int ldx, int rows, int HW, int C, int groups, float eps,
                         float* stats, float* partial, void* stream);
 /* stats + apply in two launches (the apply kernel folds the chunk partials itself and publishes `stats` for a later
- * skg_groupnorm_bwd): what the UNet / VAE forward use. */
-int skg_groupnorm_fwd(const void* X, int ldx, void* Y, int ldy, int rows, int HW, int C, int groups, float eps,
-                      const void* gamma, const void* beta, int silu, float* stats, float* partial, void* stream);
-/* GroupNorm whose statistics pass is done by the PRODUCER of X.  skg_gemm_f16_gn / skg_conv3x3_f16_gn are
- * skg_gemm_f16 / skg_conv3x3_f16 that additionally leave, per (sample b, 128-row chunk c, group g), sum(y) and sum(y^2)
- * of the fp16 outputs in gn_partial[((b * (HW / 128) + c) * groups + g) * 2 + {0, 1}] (HW = rows of C per sample, a
- * multiple of 128; fp16 output, no fused GEGLU).  The sums come out of the kernel's own epilogue when the tile that runs
+ * skg_groupnorm_bwd): what the UNet / VAE forward use.  X_lo != NULL (accuracy mode, below): GroupNorm of the pair X + X_lo (one
+ * pitch; own statistics pass over the hi part; small maps: one launch on the pair's sum), and then Y_lo != NULL: the output is a
+ * pair too (pitch ldy; conv_norm_out in front of conv_out, whose operand rounding would reach eps one to one). */
+int skg_groupnorm_fwd(const void* X, const void* X_lo, int ldx, void* Y, void* Y_lo, int ldy, int rows, int HW, int C, int groups,
+                      float eps, const void* gamma, const void* beta, int silu, float* stats, float* partial, void* stream);
+/* GroupNorm whose statistics pass is done by the PRODUCER of X.  skg_gemm_f16 / skg_conv3x3_f16 with gn_partial != NULL
+ * additionally leave, per (sample b, 128-row chunk c, group g), sum(y) and sum(y^2) of the fp16 outputs (the hi part of a pair)
+ * in gn_partial[((b * (HW / 128) + c) * groups + g) * 2 + {0, 1}] (HW = rows of C per sample, a multiple of 128; fp16 output, no
+ * fused GEGLU, 16-byte aligned C, ldc % 8 == 0).  The sums come out of the kernel's own epilogue when the tile that runs
  * can produce them (256 x 320 and 128 x 160 tiles, whole tiles, groups inside a tile - every 64 x 64 / 32 x 32-level
  * layer of the UNet), otherwise from the stand-alone statistics pass: the result is the same either way, in a fixed
  * summation order.  skg_groupnorm_from_partial folds `nch` chunks per (sample, group), publishes (mean, rstd) to `stats`
  * and applies - X is read once instead of twice.  Same replaced reference calls as skg_groupnorm_fwd. */
-int skg_gemm_f16_gn(const void* A, int lda, const void* B, int ldb, void* C, int ldc, int M, int N, int K,
-                    const void* bias, const void* residual, int ldr, float alpha, unsigned flags,
-                    float* gn_partial, int HW, int groups, void* stream);
-int skg_conv3x3_f16_gn(const void* X, int ldx, const void* Wp, void* Y, int ldy, int rows, int IH, int IW,
-                       int Cin, int Cout, int mode, const void* bias, const void* residual, int ldr,
-                       float alpha, unsigned flags, float* gn_partial, int groups, void* stream);
-/* 1 when the _gn launch of this shape gets its partial sums from the kernel's own epilogue (mode as in
+/* 1 when a gn_partial launch of this shape gets its partial sums from the kernel's own epilogue (mode as in
  * skg_gemm_variant: 0 = GEMM, 1 + SKG_CONV_*), 0 when the stand-alone statistics pass follows. */
 int skg_gemm_gn_fused(int M, int N, int K, int Cin, int mode, int HW, int groups);
-int skg_groupnorm_from_partial(const void* X, int ldx, void* Y, int ldy, int rows, int HW, int C, int groups,
-                               float eps, const void* gamma, const void* beta, int silu, float* stats,
-                               const float* partial, int nch, void* stream);
-/* The same for a CONCATENATION X = [A (CA channels) | B (C - CA channels)] whose halves were written by two producers
- * (the skip connection of the UNet's up path and the layer in front of it): partialA / partialB hold groupsA / groupsB
+/* partialB != NULL: the same for a CONCATENATION X = [A (CA channels) | B (C - CA channels)] whose halves were written by two
+ * producers (the skip connection of the UNet's up path and the layer in front of it): partialA / partialB hold groupsA / groupsB
  * groups per chunk over each half's own channels; the concatenation's group width must be a multiple of both source
  * widths and CA a multiple of it (320 + 320, 640 + 640 channels: two source groups per output group), otherwise
  * SKG_E_UNSUPPORTED (nothing launched: run skg_groupnorm_fwd).  Replaces: the GroupNorm on torch.cat([h, skip]) in
- * diffusers' CrossAttnUpBlock2D / UpBlock2D resnets (modules/pipeline.py:96). */
-int skg_groupnorm_from_partial2(const void* X, int ldx, void* Y, int ldy, int rows, int HW, int C, int CA,
-                                int groups, float eps, const void* gamma, const void* beta, int silu,
-                                float* stats, const float* partialA, int groupsA, const float* partialB,
-                                int groupsB, int nch, void* stream);
+ * diffusers' CrossAttnUpBlock2D / UpBlock2D resnets (modules/pipeline.py:96).  partialB == NULL: one producer, CA and groupsB
+ * unused (pass 0) and groupsA = groups.  X_lo / Y_lo as skg_groupnorm_fwd. */
+int skg_groupnorm_from_partial(const void* X, const void* X_lo, int ldx, void* Y, void* Y_lo, int ldy, int rows, int HW, int C,
+                               int CA, int groups, float eps, const void* gamma, const void* beta, int silu, float* stats,
+                               const float* partialA, int groupsA, const float* partialB, int groupsB, int nch, void* stream);
 /* C[(m / seg_rows) * seg_stride + m % seg_rows][n] = sum_k A[m][k] * B[n][k] + bias[n]: a GEMM over all batch rows whose output rows
  * land in per-batch-row slots of a longer buffer - clip_guided_attn concatenates [N image tokens ; 257 sketch tokens] per batch
  * row (modules/clip_guided_attn.py:111-119), so the image tokens' K / V of row b belong at rows [b L, b L + N) of the K / V
@@ -144,27 +139,21 @@ int skg_gemm_f16_rows(const void* A, int lda, const void* B, int ldb, void* C, i
  * nine taps land on, with the taps that land on one pixel pre-summed - four 4-tap stride-1 convolutions over the low-res
  * input, 16 tap-products per input pixel instead of 36 (skg_conv3x3_f16 with SKG_CONV_UP2 is the 9-tap form, same result up
  * to the fp16 rounding of the summed weights).  X [rows*IH*IW, Cin] (ldx), Y [rows*2IH*2IW, Cout] (ldy), Wpp: packed
- * [4 phases 2a+b][Cout][4 taps][Cin] (sketch2img_amd.unet.pack_conv_up2).  Cin % 64 == 0. */
-int skg_conv3x3_up2_f16(const void* X, int ldx, const void* Wpp, void* Y, int ldy, int rows, int IH, int IW, int Cin,
-                        int Cout, const void* bias, void* stream);
-/* Accuracy mode: the same on a pair input - X2 = [x_hi | x_lo], 2 C channels per pixel - with (hi, lo) pre-summed weights and a
- * pair output: per tap [x_hi | x_lo | x_hi] . [W_hi | W_hi | W_lo], Wpp3 [4 phases][Cout][4 taps][3 C]
- * (sketch2img_amd.unet.pack_conv_up2_hilo).  C % 64 == 0. */
-int skg_conv3x3_up2_f16_hilo(const void* X2, int ldx, const void* Wpp3, void* Y, void* Y_lo, int ldy, int rows, int IH, int IW,
-                             int C, int Cout, const void* bias, void* stream);
-/* Accuracy mode, cheaper form (round 5): skg_conv3x3_up2_f16 on the hi part of the stream (X [rows*IH*IW][ldx >= Cin], Wpp the
- * default polyphase pack [4][Cout][4*Cin]) with the output written as the pair Y + Y_lo.  Drops the x_lo and W_lo correction
- * thirds of skg_conv3x3_up2_f16_hilo (each ~1 % of the mode's eps distance, together two thirds of its time). */
-int skg_conv3x3_up2_f16_pairout(const void* X, int ldx, const void* Wpp, void* Y, void* Y_lo, int ldy, int rows, int IH, int IW,
-                                int Cin, int Cout, const void* bias, void* stream);
-
+ * [4 phases 2a+b][Cout][4 taps][Cin] (sketch2img_amd.unet.pack_conv_up2).  Cin % 64 == 0.
+ * Accuracy mode.  Y_lo != NULL, pair_in == 0 (round 5, what the mode runs): the launch on the hi part of the stream (ldx >= Cin)
+ * with the output written as the pair Y + Y_lo - drops the x_lo and W_lo correction thirds of the pair_in form (each ~1 % of the
+ * mode's eps distance, together two thirds of its time).  pair_in != 0 (needs Y_lo): X is the pair buffer [x_hi | x_lo], 2 Cin
+ * channels per pixel, with (hi, lo) pre-summed weights: per tap [x_hi | x_lo | x_hi] . [W_hi | W_hi | W_lo], Wpp = Wpp3
+ * [4 phases][Cout][4 taps][3 Cin] (sketch2img_amd.unet.pack_conv_up2_hilo). */
+int skg_conv3x3_up2_f16(const void* X, int ldx, const void* Wpp, void* Y, void* Y_lo, int ldy, int rows, int IH, int IW, int Cin,
+                        int Cout, int pair_in, const void* bias, void* stream);
 /* conv2 + conv_shortcut of a ResnetBlock whose channel count changes, as ONE implicit GEMM (round 5; diffusers ResnetBlock2D:
  * output = conv2(.) + conv_shortcut(x), under modules/pipeline.py:96): the 1x1 shortcut is a tenth "tap" without halo -
  *   Y[m][n] = sum_{tap, c} X[pixel(m) + tap][c] * Wcat[n][tap * Cin + c] + sum_{c2 < K2} X2[m][c2] * Wcat[n][9 * Cin + c2] + bias[n]
  * X [rows*IH*IW][ldx >= Cin] the 3x3 input (stride 1), X2 [rows*IH*IW][ldx2 >= K2] the block's input x, Wcat [Cout][9*Cin + K2]
  * (conv2's tap-major pack followed by the shortcut weight; bias = conv2.bias + conv_shortcut.bias).  Y_lo != NULL (accuracy mode):
  * pair output, and X2 / K2 are the pair buffer [x_hi | x_lo] / 2 * Cin_x against [W_sc | W_sc].  gn_partial != NULL: the GroupNorm
- * partial sums of the output as skg_conv3x3_f16_gn writes them.  Removes one GEMM launch, its M x Cout output write and the
+ * partial sums of the output as skg_conv3x3_f16 writes them.  Removes one GEMM launch, its M x Cout output write and the
  * residual read of conv2's epilogue per such block (14 per SD1.5 evaluation).  Cin % 64 == 0, K2 % 64 == 0.  Returns
  * SKG_E_UNSUPPORTED (nothing launched: run conv2 and the shortcut GEMM as two launches) when X2 spans 2 GiB or more. */
 int skg_conv3x3_sc_f16(const void* X, int ldx, const void* X2, int ldx2, int K2, const void* Wcat, void* Y, void* Y_lo, int ldy,
@@ -206,55 +195,24 @@ int skg_conv4x4s2_f16(const void* X, int ldx, const void* W16, void* Y, int ldy,
  * 1.0e-3 of it from the fp16 residual stream.  HipUNet(residual_fp32=True) keeps the residual stream and the conv outputs
  * that feed a norm or the residual sum as pairs: the producer's epilogue writes hi = fp16(v) and lo = fp16(v - hi), adds a
  * residual pair in fp32; norms read hi + lo; where the stream itself is a matmul operand the pair is the operand
- * ([hi | lo] along K against [W | W]).  skg_gemm_f16 / skg_conv3x3_f16 with a second output / residual pointer (same leading
- * dimensions); C_lo / residual_lo may be NULL individually, not both.  fp16 output only, K % 64 == 0, 16-byte aligned. */
-int skg_gemm_f16_hilo(const void* A, int lda, const void* B, int ldb, void* C, void* C_lo, int ldc, int M, int N, int K,
-                      const void* bias, const void* residual, const void* residual_lo, int ldr, float alpha,
-                      unsigned flags, void* stream);
-int skg_conv3x3_f16_hilo(const void* X, int ldx, const void* Wp, void* Y, void* Y_lo, int ldy, int rows, int IH, int IW,
-                         int Cin, int Cout, int mode, const void* bias, const void* residual, const void* residual_lo,
-                         int ldr, float alpha, unsigned flags, void* stream);
-/* The same launches leaving the GroupNorm partial sums of the output's hi part behind (format of skg_gemm_f16_gn /
- * skg_conv3x3_f16_gn): from the producer's own epilogue where its tile can (256 x 320, 128 x 160), else the stand-alone pass. */
-int skg_gemm_f16_hilo_gn(const void* A, int lda, const void* B, int ldb, void* C, void* C_lo, int ldc, int M, int N, int K,
-                         const void* bias, const void* residual, const void* residual_lo, int ldr, float alpha,
-                         unsigned flags, float* gn_partial, int HW, int groups, void* stream);
-int skg_conv3x3_f16_hilo_gn(const void* X, int ldx, const void* Wp, void* Y, void* Y_lo, int ldy, int rows, int IH, int IW,
-                            int Cin, int Cout, int mode, const void* bias, const void* residual, const void* residual_lo,
-                            int ldr, float alpha, unsigned flags, float* gn_partial, int groups, void* stream);
-/* GroupNorm(+SiLU) of a pair X + X_lo (one pitch), mirrors of skg_groupnorm_fwd (own statistics pass over the hi part; small
- * maps: one launch on the pair's sum) and of skg_groupnorm_from_partial / _from_partial2 (partialB == NULL: one producer and
- * groupsA == groups; else the concatenation [A (CA channels) | B]).  The reference's GroupNorm layers (diffusers ResnetBlock2D /
- * Transformer2DModel under modules/pipeline.py:96) evaluated on the fp32-accurate stream.  Y_lo != NULL: the output is a pair too
- * (pitch ldy; conv_norm_out in front of conv_out, whose operand rounding would reach eps one to one). */
-int skg_groupnorm_fwd_hilo(const void* X, const void* X_lo, int ldx, void* Y, void* Y_lo /* or NULL */, int ldy, int rows, int HW,
-                           int C, int groups, float eps, const void* gamma, const void* beta, int silu, float* stats,
-                           float* partial, void* stream);
-int skg_groupnorm_from_partial_hilo(const void* X, const void* X_lo, int ldx, void* Y, void* Y_lo /* or NULL */, int ldy, int rows,
-                                    int HW, int C, int CA,
-                                    int groups, float eps, const void* gamma, const void* beta, int silu, float* stats,
-                                    const float* partialA, int groupsA, const float* partialB, int groupsB, int nch,
-                                    void* stream);
-/* GroupNorm(+SiLU) apply and LayerNorm of a pair (statistics [rows][groups][2] from skg_groupnorm_stats on the hi part). */
-int skg_groupnorm_apply_hilo(const void* X, const void* X_lo, int ldx, void* Y, int ldy, int rows, int HW, int C,
-                             int groups, const float* stats, const void* gamma, const void* beta, int silu,
-                             void* stream);
-int skg_layernorm_fwd_hilo(const void* X, const void* X_lo, int ldx, void* Y, int ldy, int M, int C,
-                           const void* gamma, const void* beta, float eps, float* stats /* [M][2] or NULL */, void* stream);
+ * ([hi | lo] along K against [W | W]).  skg_gemm_f16 / skg_conv3x3_f16 take the second output / residual pointer (same leading
+ * dimensions); with either of them: fp16 output only, K % 64 == 0 (Cin % 64 == 0), ldc % 8 == 0 (ldr % 8 == 0), all four 16-byte
+ * aligned.  The norms take X_lo: the reference's GroupNorm / LayerNorm layers (diffusers ResnetBlock2D / Transformer2DModel /
+ * BasicTransformerBlock under modules/pipeline.py:96) evaluated on the fp32-accurate stream. */
 
-int skg_groupnorm_apply(const void* X, int ldx, void* Y, int ldy, int rows, int HW, int C,
-                        int groups, const float* stats, const void* gamma, const void* beta,
-                        int silu, void* stream);
+/* apply alone (statistics [rows][groups][2] from skg_groupnorm_stats - on the hi part of a pair X + X_lo, X_lo != NULL) */
+int skg_groupnorm_apply(const void* X, const void* X_lo, int ldx, void* Y, int ldy, int rows, int HW, int C, int groups,
+                        const float* stats, const void* gamma, const void* beta, int silu, void* stream);
 int skg_groupnorm_bwd(const void* X, int ldx, const void* dY, int lddy, void* dX, int lddx,
                       const void* residual, int ldr, int rows, int HW, int C, int groups,
                       const float* stats, const void* gamma, const void* beta, int silu,
                       float* partial, void* stream);
 
 /* ---- LayerNorm over the last dim, fp16 [M][C] ------------------------------------------------
- * fwd also writes float2 (mean, rstd) per row to `stats` if non-NULL.
+ * fwd also writes float2 (mean, rstd) per row to `stats` if non-NULL; X_lo != NULL: LayerNorm of the pair X + X_lo.
  * bwd: dX = LN'(dY) + residual.  Requires C % 8 == 0, C <= 2048.
  * Replaces: BasicTransformerBlock.norm1/2/3 and sketch_norm (modules/clip_guided_attn.py:113). */
-int skg_layernorm_fwd(const void* X, int ldx, void* Y, int ldy, int M, int C, const void* gamma,
+int skg_layernorm_fwd(const void* X, const void* X_lo, int ldx, void* Y, int ldy, int M, int C, const void* gamma,
                       const void* beta, float eps, float* stats, void* stream);
 int skg_layernorm_bwd(const void* X, int ldx, const void* dY, int lddy, void* dX, int lddx,
                       const void* residual, int ldr, int M, int C, const void* gamma,
@@ -278,46 +236,32 @@ int skg_gemm_f16_geglu_keep(const void* A, int lda, const void* B, int ldb, void
  * Y may alias X.  Same roundings as the three-launch path (fp16 LayerNorm output, fp16 FF1 output before the gate,
  * fp16 gated value, one fp16 rounding of the residual sum).
  * Replaces: BasicTransformerBlock.norm3 / ff (GEGLU) / residual add ([diffusers] attention.py), reached from
- * modules/pipeline.py:96. */
-int skg_ff_block_f16(const void* X, int ldx, void* Y, int ldy, int M, int C, int F, const void* gamma,
-                     const void* beta, float eps, const void* Wpack, const float* bias1_pack,
-                     const void* bias2, float* stats, void* stream);
-/* The same launch, ALSO storing the FF1 output H = fp16(W1 . LayerNorm(X) + b1) of rows >= keep_from to H [M - keep_from][2F]
+ * modules/pipeline.py:96.
+ * H != NULL: ALSO store the FF1 output H = fp16(W1 . LayerNorm(X) + b1) of rows >= keep_from to H [M - keep_from][2F]
  * (row m -> H row m - keep_from) in the interleaved pack order skg_geglu_bwd takes as its saved H (what
  * skg_gemm_f16_geglu_keep writes): the cond rows of a guided step, whose gate is differentiated.  keep_from % 16 == 0,
- * ldh % 8 == 0.  H == NULL: plain skg_ff_block_f16. */
-int skg_ff_block_f16_keep(const void* X, int ldx, void* Y, int ldy, int M, int C, int F, const void* gamma,
-                          const void* beta, float eps, const void* Wpack, const float* bias1_pack,
-                          const void* bias2, float* stats, void* H, int ldh, int keep_from, void* stream);
-/* ... followed by Transformer2DModel.proj_out + the transformer's outer residual in the same launch ([diffusers] attention.py
- * Transformer2DModel.forward: `hidden_states = self.proj_out(hidden_states); output = hidden_states + residual`):
+ * ldh % 8 == 0.
+ * bias_proj != NULL: followed by Transformer2DModel.proj_out + the transformer's outer residual in the same launch ([diffusers]
+ * attention.py Transformer2DModel.forward: `hidden_states = self.proj_out(hidden_states); output = hidden_states + residual`):
  *   Y = R + bias_proj + W_proj . fp16(X + FF(LayerNorm(X)))
  * Wpack holds five more chunks behind the F / 32 feed-forward ones (sketch2img_amd.unet.pack_ff_block(..., w_proj)); the block
- * output never reaches memory (its backward does not read it).  stats / H / ldh / keep_from as skg_ff_block_f16_keep (H == NULL:
- * no stash); gn_partial != NULL: also the GroupNorm partial sums of Y, fp32 [M / HW][HW / 128][groups][2], the layout of
- * skg_gemm_f16_gn (HW % 128 == 0, groups <= 32).  Y must not alias X; it may alias R. */
-int skg_ff_block_proj_f16(const void* X, int ldx, void* Y, int ldy, int M, int C, int F, const void* gamma, const void* beta,
-                          float eps, const void* Wpack, const float* bias1_pack, const void* bias2, const void* bias_proj,
-                          const void* R, int ldr, float* stats, void* H, int ldh, int keep_from, float* gn_partial, int HW,
-                          int groups, void* stream);
-
-/* Accuracy mode (round 5): skg_ff_block_proj_f16 on pairs - X + X_lo in (pitch ldx), Y + Y_lo out (pitch ldy), outer residual
- * R + R_lo (pitch ldr).  proj_out takes the block output as the pair it is, W_proj . hi + W_proj . lo on the same weight
- * fragments (the K-doubled [p3_hi | p3_lo] . [W | W] GEMM of the unfused accuracy-mode path, without its second weight read and
- * without the [M, 2C] round trip of p3); gn_partial: the GroupNorm partial sums of Y's hi part.  Y must not alias X. */
-int skg_ff_block_proj_f16_hilo(const void* X, const void* X_lo, int ldx, void* Y, void* Y_lo, int ldy, int M, int C, int F,
-                               const void* gamma, const void* beta, float eps, const void* Wpack, const float* bias1_pack,
-                               const void* bias2, const void* bias_proj, const void* R, const void* R_lo, int ldr, float* stats,
-                               void* H, int ldh, int keep_from, float* gn_partial, int HW, int groups, void* stream);
-/* Accuracy mode: the same launch on a PAIR input X + X_lo (pitch ldx) with a PAIR output Y + Y_lo (pitch ldy): LayerNorm reads
- * the sum, the residual sum is formed in fp32 and stored as hi = fp16(v), lo = fp16(v - hi).  H / keep_from as _keep (or NULL). */
-int skg_ff_block_f16_hilo(const void* X, const void* X_lo, int ldx, void* Y, void* Y_lo, int ldy, int M, int C, int F,
-                          const void* gamma, const void* beta, float eps, const void* Wpack, const float* bias1_pack,
-                          const void* bias2, float* stats, void* H, int ldh, int keep_from, void* stream);
+ * output never reaches memory (its backward does not read it).  Then gn_partial != NULL: also the GroupNorm partial sums of Y,
+ * fp32 [M / HW][HW / 128][groups][2], the layout skg_gemm_f16 leaves (HW % 128 == 0, groups <= 32).  Y must not alias X; it may
+ * alias R.
+ * X_lo and Y_lo != NULL (accuracy mode; both or neither): PAIR input X + X_lo (pitch ldx) and PAIR output Y + Y_lo (pitch ldy) -
+ * LayerNorm reads the sum, the residual sum is formed in fp32 and stored as hi = fp16(v), lo = fp16(v - hi).  With bias_proj
+ * (round 5) the outer residual is the pair R + R_lo (pitch ldr) and proj_out takes the block output as the pair it is,
+ * W_proj . hi + W_proj . lo on the same weight fragments (the K-doubled [p3_hi | p3_lo] . [W | W] GEMM of the unfused
+ * accuracy-mode path, without its second weight read and without the [M, 2C] round trip of p3); gn_partial: the GroupNorm partial
+ * sums of Y's hi part. */
+int skg_ff_block_f16(const void* X, const void* X_lo, int ldx, void* Y, void* Y_lo, int ldy, int M, int C, int F,
+                     const void* gamma, const void* beta, float eps, const void* Wpack, const float* bias1_pack,
+                     const void* bias2, const void* bias_proj, const void* R, const void* R_lo, int ldr, float* stats,
+                     void* H, int ldh, int keep_from, float* gn_partial, int HW, int groups, void* stream);
 
 /* ---- Row-local fused cross-attention sub-block (round 3; VERDICT r2 next #2, first half) ---------------------------
  * Y [M][C] = X + bo + Wo . Attention(Q = Wq . LayerNorm(X; gamma, beta, eps), K, V) over the Nkv <= 80 text keys of the row's
- * image - ONE launch instead of skg_layernorm_fwd, skg_gemm_f16 (attn2.to_q), skg_attn_fwd_rowv (77 keys) and skg_gemm_f16 with a
+ * image - ONE launch instead of skg_layernorm_fwd, skg_gemm_f16 (attn2.to_q), skg_attn_fwd with SKG_ATTN_ROWV (77 keys) and skg_gemm_f16 with a
  * residual (attn2.to_out); q, the attention output and the normalised rows never exist in memory.
  * C == 320, heads == 8 (head width 40: the 64 x 64 level of SD1.5); rows [b * HW, (b + 1) * HW) belong to image b, HW % 128 == 0,
  * M % HW == 0; scale = head_width^-0.5.
@@ -327,29 +271,18 @@ int skg_ff_block_f16_hilo(const void* X, const void* X_lo, int ldx, void* Y, voi
  * attention output, one fp16 rounding of the residual sum).  Y may alias X.  No LSE / q / o outputs: for rows nobody
  * differentiates (unguided evaluations, the uncond half of guided ones).
  * Replaces: BasicTransformerBlock.norm2 / attn2 / residual add ([diffusers] attention.py; the op order of
- * modules/clip_guided_attn.py:127-152), reached from modules/pipeline.py:96. */
-int skg_xattn_block_f16(const void* X, int ldx, void* Y, int ldy, int M, int HW, int C, int heads, int Nkv,
-                        const void* gamma, const void* beta, float eps, const void* Wpack, const void* KVpack,
-                        const void* bias_out, float scale, void* stream);
-/* The stashing launch of a guided evaluation (as skg_ff_block_f16_keep): rows >= keep_from - a multiple of HW, i.e. whole images:
- * the cond half - ALSO store what the backward of the four replaced launches reads: stats fp32 [M - keep_from][2] = norm2's
- * (mean, rstd) per row, Q / O fp16 [M - keep_from][ldk] = the attn2.to_q output and the attention output (head h in columns
- * 40 h .. 40 h + 39), lse fp32 [(M - keep_from) / HW][heads][HW] in skg_attn_fwd's convention.  Feeds skg_attn_bwd_delta /
- * skg_attn_bwd_dq / skg_layernorm_bwd unchanged. */
-int skg_xattn_block_f16_keep(const void* X, int ldx, void* Y, int ldy, int M, int HW, int C, int heads, int Nkv,
-                             const void* gamma, const void* beta, float eps, const void* Wpack, const void* KVpack,
-                             const void* bias_out, float scale, float* stats, void* Q, void* O, int ldk, float* lse,
-                             int keep_from, void* stream);
-/* ... on pairs (accuracy mode, round 5): skg_xattn_block_f16_hilo that also stores, for the rows >= keep_from, what the backward of
- * the replaced launches reads (stats, Q, O, lse as skg_xattn_block_f16_keep). */
-int skg_xattn_block_f16_hilo_keep(const void* X, const void* X_lo, int ldx, void* Y, void* Y_lo, int ldy, int M, int HW, int C,
-                                  int heads, int Nkv, const void* gamma, const void* beta, float eps, const void* Wpack,
-                                  const void* KVpack, const void* bias_out, float scale, float* stats, void* Q, void* O, int ldk,
-                                  float* lse, int keep_from, void* stream);
-/* Accuracy mode: the same launch on a PAIR input X + X_lo (pitch ldx) with a PAIR output Y + Y_lo (pitch ldy). */
-int skg_xattn_block_f16_hilo(const void* X, const void* X_lo, int ldx, void* Y, void* Y_lo, int ldy, int M, int HW, int C,
-                             int heads, int Nkv, const void* gamma, const void* beta, float eps, const void* Wpack,
-                             const void* KVpack, const void* bias_out, float scale, void* stream);
+ * modules/clip_guided_attn.py:127-152), reached from modules/pipeline.py:96.
+ * Q != NULL: the stashing launch of a guided evaluation (as H of skg_ff_block_f16): rows >= keep_from - a multiple of HW, i.e.
+ * whole images: the cond half - ALSO store what the backward of the four replaced launches reads: stats fp32 [M - keep_from][2] =
+ * norm2's (mean, rstd) per row, Q / O fp16 [M - keep_from][ldk] = the attn2.to_q output and the attention output (head h in
+ * columns 40 h .. 40 h + 39), lse fp32 [(M - keep_from) / HW][heads][HW] in skg_attn_fwd's convention.  Feeds skg_attn_bwd_delta /
+ * skg_attn_bwd_dq / skg_layernorm_bwd unchanged.
+ * X_lo and Y_lo != NULL (accuracy mode; both or neither): PAIR input X + X_lo (pitch ldx), PAIR output Y + Y_lo (pitch ldy); with
+ * Q (round 5) the stash as above. */
+int skg_xattn_block_f16(const void* X, const void* X_lo, int ldx, void* Y, void* Y_lo, int ldy, int M, int HW, int C, int heads,
+                        int Nkv, const void* gamma, const void* beta, float eps, const void* Wpack, const void* KVpack,
+                        const void* bias_out, float scale, float* stats, void* Q, void* O, int ldk, float* lse, int keep_from,
+                        void* stream);
 
 /* ---- GEGLU: Y[m][j] = a_j * gelu(g_j),  H fp16 [M][2F] -----------------------------------------------
  * interleaved == 0: H = [a (F columns) | g (F columns)] (diffusers' chunk(2));  interleaved == 1: groups of four
@@ -365,26 +298,23 @@ int skg_geglu_bwd(const void* H, int ldh, const void* dY, int lddy, void* dH, in
  * [h*dh, (h+1)*dh).  Vt is V transposed: Vt[h*dh + d][b*kv_stride + j] (ldvt).  Only the first
  * Nkv of each batch row's kv_stride key slots are valid.  O [batch*Nq][..] (ldo).
  * lse (float [batch][heads][Nq], natural-log-sum-exp of the scaled scores) may be NULL.
- * dh in {16, 32, 40, 64, 80, 160}; kv_stride % 8 == 0 (the V^T operand; the row-major-V forms below take any kv_stride).
+ * dh in {16, 32, 40, 64, 80, 160}; kv_stride % 8 == 0 (the V^T operand; SKG_ATTN_ROWV takes any kv_stride).
  * Replaces: xformers memory_efficient_attention (enabled at app.py:43) / diffusers
  * CrossAttention baddbmm+softmax+bmm for attn1, attn2 and the injected sketch_attn
- * (modules/clip_guided_attn.py:114, modules/sketch_guided_attn.py:127). */
+ * (modules/clip_guided_attn.py:114, modules/sketch_guided_attn.py:127).
+ * flags (at most one of the two; both: SKG_E_BADARG):
+ *   SKG_ATTN_ROWV    Vt / ldvt are V handed over ROW-MAJOR: V [batch*kv_stride][ldv], head h at columns h*dh.. (e.g. the third
+ *                    column block of a fused QKV projection, ldv = 3C).  The kernel reads its V fragments through the gfx950 LDS
+ *                    transpose read (ds_read_b64_tr_b16), so no transposed copy of V is written.
+ *   SKG_ATTN_CAUSAL  key j of a batch row is visible to query i only when j <= i (self-attention, Nq rows and kv_stride key
+ *                    slots per batch row).  dh in {16, 32, 64}.  Replaces: the masked self-attention of transformers'
+ *                    CLIPTextModel, which the reference calls through StableDiffusionPipeline._encode_prompt
+ *                    (modules/pipeline.py:55-57). */
+#define SKG_ATTN_CAUSAL 1u
+#define SKG_ATTN_ROWV 2u
 int skg_attn_fwd(const void* Q, int ldq, const void* K, int ldk, const void* Vt, int ldvt,
                  void* O, int ldo, float* lse, int batch, int heads, int Nq, int Nkv,
-                 int kv_stride, int dh, float scale, void* stream);
-/* Same with V handed over ROW-MAJOR: V [batch*kv_stride][ldv], head h at columns h*dh.. (e.g. the third column block
- * of a fused QKV projection, ldv = 3C).  The kernel reads its V fragments through the gfx950 LDS transpose read
- * (ds_read_b64_tr_b16), so no transposed copy of V is written.  Same replaced reference calls as skg_attn_fwd. */
-int skg_attn_fwd_rowv(const void* Q, int ldq, const void* K, int ldk, const void* V, int ldv,
-                      void* O, int ldo, float* lse, int batch, int heads, int Nq, int Nkv,
-                      int kv_stride, int dh, float scale, void* stream);
-/* Same with a causal mask: key j of a batch row is visible to query i only when j <= i (self-attention, Nq rows
- * and kv_stride key slots per batch row).  dh in {16, 32, 64}.
- * Replaces: the masked self-attention of transformers' CLIPTextModel, which the reference calls through
- * StableDiffusionPipeline._encode_prompt (modules/pipeline.py:55-57). */
-int skg_attn_fwd_causal(const void* Q, int ldq, const void* K, int ldk, const void* Vt, int ldvt,
-                        void* O, int ldo, float* lse, int batch, int heads, int Nq, int Nkv,
-                        int kv_stride, int dh, float scale, void* stream);
+                 int kv_stride, int dh, float scale, unsigned flags, void* stream);
 /* backward.  delta[b][h][q] = sum_d dO*O (skg_attn_bwd_delta).  All operands row-major like their primals (Q, dO
  * [batch*Nq][..], K, V [batch*kv_stride][..]); the transposed fragments the dQ / dK / dV products need (K^T, Q^T, dO^T)
  * are read from the row tiles in LDS through ds_read_b64_tr_b16 - no transposed copies in HBM.  Outputs row-major.
@@ -392,27 +322,20 @@ int skg_attn_fwd_causal(const void* Q, int ldq, const void* K, int ldk, const vo
  * torch.autograd.grad at modules/pipeline.py:159. */
 int skg_attn_bwd_delta(const void* O, int ldo, const void* dO, int lddo, float* delta, int batch,
                        int heads, int Nq, int dh, void* stream);
-int skg_attn_bwd_dq(const void* Q, int ldq, const void* K, int ldk, const void* V, int ldv,
-                    const void* dO, int lddo, const float* lse,
-                    const float* delta, void* dQ, int lddq, int batch, int heads, int Nq, int Nkv,
-                    int kv_stride, int dh, float scale, void* stream);
-/* skg_attn_bwd_dq with skg_attn_bwd_delta in its prologue (round 5): O [batch*Nq][ldo] is the forward's output; delta is formed from
- * the dO fragments the launch loads anyway, used, and stored to delta_out [batch][heads][Nq] for the skg_attn_bwd_dkv launch
- * that follows (summation order differs from skg_attn_bwd_delta's: equal to fp32 rounding, not bit for bit). */
-int skg_attn_bwd_dq_delta(const void* Q, int ldq, const void* K, int ldk, const void* V, int ldv, const void* dO, int lddo,
-                          const void* O, int ldo, const float* lse, float* delta_out, void* dQ, int lddq, int batch, int heads,
-                          int Nq, int Nkv, int kv_stride, int dh, float scale, void* stream);
+/* dq.  delta given: O / ldo / delta_out are not looked at.  delta == NULL (round 5): skg_attn_bwd_delta in the prologue - O
+ * [batch*Nq][ldo] is the forward's output; delta is formed from the dO fragments the launch loads anyway, used, and stored to
+ * delta_out [batch][heads][Nq] for the skg_attn_bwd_dkv launch that follows (summation order differs from skg_attn_bwd_delta's:
+ * equal to fp32 rounding, not bit for bit). */
+int skg_attn_bwd_dq(const void* Q, int ldq, const void* K, int ldk, const void* V, int ldv, const void* dO, int lddo,
+                    const void* O, int ldo, const float* lse, const float* delta, float* delta_out, void* dQ, int lddq,
+                    int batch, int heads, int Nq, int Nkv, int kv_stride, int dh, float scale, void* stream);
+/* dK, dV.  K, V, dK, dV rows of batch row b start at b * kv_stride (kv_stride >= Nkv; dense buffers: kv_stride = Nkv; a padded
+ * K / V buffer such as the injected attention's [N image tokens ; T sketch tokens -> multiple of 8]: same kernel, same grid).
+ * Rows Nkv .. kv_stride - 1 of dK / dV are left untouched. */
 int skg_attn_bwd_dkv(const void* Q, int ldq, const void* K, int ldk,
                      const void* V, int ldv, const void* dO, int lddo,
                      const float* lse, const float* delta, void* dK, int lddk, void* dV, int lddv,
-                     int batch, int heads, int Nq, int Nkv, int dh, float scale, void* stream);
-/* ... with a key stride: K, V, dK, dV rows of batch row b start at b * kv_stride (kv_stride >= Nkv: a padded K / V buffer
- * such as the injected attention's [N image tokens ; T sketch tokens -> multiple of 8]).  Rows Nkv .. kv_stride - 1 of dK / dV
- * are left untouched.  kv_stride == Nkv is skg_attn_bwd_dkv bit for bit (same kernel, same grid). */
-int skg_attn_bwd_dkv_strided(const void* Q, int ldq, const void* K, int ldk,
-                             const void* V, int ldv, const void* dO, int lddo,
-                             const float* lse, const float* delta, void* dK, int lddk, void* dV, int lddv,
-                             int batch, int heads, int Nq, int Nkv, int kv_stride, int dh, float scale, void* stream);
+                     int batch, int heads, int Nq, int Nkv, int kv_stride, int dh, float scale, void* stream);
 
 /* ---- data movement -----------------------------------------------------------------------------*/
 /* Out[c][m] = In[m][c], fp16, In [M][C] (ldi), Out [C][M] (ldo).  C % 8 == 0, M % 8 == 0. */
@@ -451,16 +374,18 @@ int skg_nhwc_f16_to_nchw_f32(const void* X, int ldx, float* Y, int rows, int C, 
 /* ---- LGP (Latent Gradient/Edge Predictor) pieces ------------------------------------------------
  * Layer 0 is re-associated with the bilinear resize: per tap i the caller runs
  * skg_gemm_f16(F_i, W0[:, off_i:off_i+C_i]) -> P_i fp32 [rows*s_i*s_i][H0] at the tap's NATIVE
- * size; skg_lgp_layer0_gather then forms, for every output pixel of the h x h grid,
+ * size; skg_lgp_layer0_gather then forms, for every output pixel of the h x w grid,
  *   z = relu( fp16( sum_i bilinear_i(P_i) + W0[:, E:E+40] . fp16(e) + b0 ) )
  * with e = [nl(4), sin(2 pi nl 2^-l) l=0..8 (36)], nl = sigma * noise  (fp32, then fp16 cast, as
- * modules/latent_predictor.py:39-43).  Output Z fp16 [rows*h*h][H0], pixel order (y, x).
+ * modules/latent_predictor.py:39-43).  Output Z fp16 [rows*h*w][H0], pixel order (y, x), pixel = y*w + x.
+ * w == h: the square grid, any h.  w != h: h, w multiples of 8, and a tap of height s has width s*w/h (the same power-of-two scale
+ * on both axes): P [rows*s*(s*w/h)][H0], noise / target float NCHW [samples][4][h][w].
  * `taps` is a HOST array of ntaps (<= 12) SkgLgpTap; rows = 2*samples in the row layout
- * [uncond rows of all samples; cond rows of all samples]; noise float NCHW [samples][4][h][h].  Replaces F.interpolate x9 + cat + cast + layer 0 of
+ * [uncond rows of all samples; cond rows of all samples].  Replaces F.interpolate x9 + cat + cast + layer 0 of
  * modules/pipeline.py:146-153 / modules/latent_predictor.py:42-45. */
 typedef struct {
-  const float* P;   /* fp32 [rows*s*s][H0] */
-  int s;            /* native side */
+  const float* P;   /* fp32 [rows*s*(s*w/h)][H0] */
+  int s;            /* native height */
   int pad_;
 } SkgLgpTap;
 /* Wextra may be NULL (h % 8 == 0 and H0 % 128 == 0 required): the caller then supplies the product of the 40 extra
@@ -468,18 +393,10 @@ typedef struct {
  * 40-wide dot products instead of 160 cached vector loads per thread. */
 int skg_lgp_layer0_gather(const SkgLgpTap* taps, int ntaps, const void* Wextra, int ldw,
                           const void* bias0, const float* noise, float sigma, int samples,
-                          void* Z, int rows, int h, int H0, void* stream);
-/* adjoint of the bilinear part for ONE tap: dP [rows*s*s][H0] fp16 from dZ [rows*h*h][H0] fp16. */
-int skg_lgp_layer0_scatter(const void* dZ, int lddz, void* dP, int rows, int h, int s, int H0,
+                          void* Z, int rows, int h, int w, int H0, void* stream);
+/* adjoint of the bilinear part for ONE tap: dP [rows*s*(s*w/h)][H0] fp16 from dZ [rows*h*w][H0] fp16. */
+int skg_lgp_layer0_scatter(const void* dZ, int lddz, void* dP, int rows, int h, int w, int s, int H0,
                            void* stream);
-/* Rectangular forms of the layer-0 pieces on an h x w grid (h, w multiples of 8; pixel order (y, x), pixel = y*w + x).
- * A tap of height s has width s*w/h (the same power-of-two scale on both axes): P [rows*s*(s*w/h)][H0], noise / target
- * float NCHW [samples][4][h][w].  With w == h they compute what the square entry points compute, bit for bit. */
-int skg_lgp_layer0_gather_hw(const SkgLgpTap* taps, int ntaps, const void* Wextra, int ldw,
-                             const void* bias0, const float* noise, float sigma, int samples,
-                             void* Z, int rows, int h, int w, int H0, void* stream);
-int skg_lgp_layer0_scatter_hw(const void* dZ, int lddz, void* dP, int rows, int h, int w, int s, int H0,
-                              void* stream);
 /* train-mode BatchNorm1d whose "batch" is ONE sample's LGP rows (the reference only runs B = 1:
  * SURVEY Q1/Q3).  Row layout of X: row = (j*samples + s)*seg_rows + i, j = 0..segs-1 (segs = 2 CFG
  * halves, seg_rows = h*h).  X is the post-ReLU activation fp16 [samples*segs*seg_rows][C].
@@ -503,15 +420,12 @@ int skg_bn_apply(const void* X, int ldx, void* Y, int ldy, int samples, int segs
 int skg_bn_relu_bwd(const void* X, int ldx, const void* dY, int lddy, void* dX, int lddx,
                     int samples, int segs, int seg_rows, int C, const float* stats,
                     const void* gamma, int train_mode, float* scratch, void* stream);
-/* MSE seed: for the cond rows, dOut = loss_scale * 2*(out - target)/(n) with n = 4*h*h, zero for the
- * uncond rows; also writes loss (float[samples]).  out fp16 [2*samples*h*h][ldo] (uncond block then
- * cond block, (y,x) pixel order), first 4 columns valid; target float NCHW [samples][4][h][h].  dOut fp16 [..][ldd],
+/* MSE seed: for the cond rows, dOut = loss_scale * 2*(out - target)/(n) with n = 4*h*w, zero for the
+ * uncond rows; also writes loss (float[samples]).  out fp16 [2*samples*h*w][ldo] (uncond block then
+ * cond block, (y,x) pixel order), first 4 columns valid; target float NCHW [samples][4][h][w] (w != h: multiples of 8).  dOut fp16 [..][ldd],
  * columns >= 4 zeroed up to ldd.  Mirrors modules/pipeline.py:155-157. */
 int skg_lgp_mse_seed(const void* out, int ldo, const float* target, void* dOut, int ldd,
-                     float* loss, int samples, int h, float loss_scale, void* stream);
-/* the same on an h x w grid (n = 4*h*w; h, w multiples of 8) */
-int skg_lgp_mse_seed_hw(const void* out, int ldo, const float* target, void* dOut, int ldd,
-                        float* loss, int samples, int h, int w, float loss_scale, void* stream);
+                     float* loss, int samples, int h, int w, float loss_scale, void* stream);
 
 /* ---- LGP training (trainer.py:208-252: forward taps -> LGP -> MSE -> backward with weight gradients -> optimizer) --
  * The reference trains with accelerate fp16 autocast + bitsandbytes AdamW8bit; here: fp16 compute with a static loss
@@ -525,12 +439,10 @@ int skg_colsum_f16(const void* X, int ldx, int M, int C, float scale, float* out
 int skg_bn_param_grads(const void* X, int ldx, const void* dY, int lddy, int rows, int C, const float* stats,
                        float scale, float* dgamma, float* dbeta, float* scratch, void* stream);
 /* The 40 extra input channels of LGP layer 0 (noise level x4, sin(2 pi nl 2^-l) x36; modules/latent_predictor.py:39-41),
- * fp16, E [rows*h*h][ld] with columns >= 40 zeroed: the operand of the layer-0 weight gradient for those columns. */
-int skg_lgp_extra_features(const float* noise, float sigma, int samples, int rows, int h, void* E, int ld,
+ * fp16, E [rows*h*w][ld] with columns >= 40 zeroed: the operand of the layer-0 weight gradient for those columns (w != h:
+ * multiples of 8). */
+int skg_lgp_extra_features(const float* noise, float sigma, int samples, int rows, int h, int w, void* E, int ld,
                            void* stream);
-/* the same on an h x w grid (E [rows*h*w][ld]; h, w multiples of 8) */
-int skg_lgp_extra_features_hw(const float* noise, float sigma, int samples, int rows, int h, int w, void* E, int ld,
-                              void* stream);
 /* Training loss (trainer.py:240): mean((out - target)^2) over samples*4*h*h; dOut = loss_scale * d loss / d out
  * (fp16 [samples*h*h][ldd], columns >= 4 zero); loss_parts[s] = this sample's share of the mean (sum them). */
 int skg_lgp_mse_train(const void* out, int ldo, const float* target, void* dOut, int ldd, float* loss_parts,

@@ -23,66 +23,45 @@ LIB_PATH = os.environ.get("SKG_LIB") or os.path.join(_HERE, "libskg.so")
 # their transposed-operand pointers, skg_set_workspace became per stream; 3: the accuracy-mode entry points with GroupNorm
 # statistics - skg_*_hilo_gn, skg_groupnorm_fwd_hilo / _from_partial_hilo, skg_ff_block_f16_hilo - and the pair offset of
 # skg_cfg_ddim_step / skg_cfg_dpmpp2m_step; 5: skg_box_probe_mfma, skg_conv3x3_sc_f16 declines instead of failing on the 2 GiB
-# operand limit), so that a stale build selected through
+# operand limit; 6: one entry point per kernel family - the _hilo / _gn / _keep / _hw / _causal / _rowv / _pairout / _dq_delta /
+# _strided / _from_partial2 / skg_ff_block_proj_f16 twins folded into the un-suffixed names, which take the superset argument
+# list with nullable pointers selecting the arm: INTEGRATION.md has the migration table), so that a stale build selected through
 # SKG_LIB fails at load instead of receiving shifted arguments
-ABI_VERSION = 5
+ABI_VERSION = 6
 
 # spec letters: p = device/host pointer, i = int, f = float, u = unsigned, z = size_t (return only)
 SIGNATURES = {
     "skg_abi_version": ("i", ""),
     "skg_last_error": ("s", ""),
-    "skg_gemm_f16": ("i", "pipipiiiippifup"),
-    "skg_conv3x3_up2_f16": ("i", "pippiiiiiipp"),
-    "skg_conv3x3_up2_f16_hilo": ("i", "pipppiiiiiipp"),
-    "skg_conv3x3_up2_f16_pairout": ("i", "pipppiiiiiipp"),
+    "skg_gemm_f16": ("i", "pipippiiiipppifupiip"),
+    "skg_conv3x3_up2_f16": ("i", "pipppiiiiiiipp"),
     "skg_conv3x3_sc_f16": ("i", "pipiipppiiiiiipupip"),
     "skg_conv4x4s2_f16": ("i", "pippiiiiiipp"),
     "skg_conv3x3_wino_v_bytes": ("z", "iiii"),
     "skg_conv3x3_wino_f16": ("i", "pippppiiiiiipppiup"),
     "skg_groupnorm_wino_fwd": ("i", "pipiiiiifppipp"),
     "skg_gemm_f16_rows": ("i", "pipipiiiipiip"),
-    "skg_gemm_f16_hilo": ("i", "pipippiiiipppifup".replace(" ", "")),
-    "skg_conv3x3_f16_hilo": ("i", "pipppiiiiiiipppifup"),
-    "skg_gemm_f16_hilo_gn": ("i", "pipippiiiipppifupiip"),
-    "skg_conv3x3_f16_hilo_gn": ("i", "pipppiiiiiiipppifupip"),
-    "skg_groupnorm_fwd_hilo": ("i", "ppippiiiiifppippp"),
-    "skg_groupnorm_from_partial_hilo": ("i", "ppippiiiiiifppippipiip"),
-    "skg_ff_block_f16_hilo": ("i", "ppippiiiippfpppppiip"),
-    "skg_groupnorm_apply_hilo": ("i", "ppipiiiiippp ip".replace(" ", "")),
-    "skg_layernorm_fwd_hilo": ("i", "ppipiiippfpp"),
-    "skg_gemm_f16_gn": ("i", "pipipiiiippifupiip"),
     "skg_gemm_gn_fused": ("i", "iiiiiii"),
     "skg_gemm_f16_geglu_keep": ("i", "pipipipiiiipp"),
-    "skg_ff_block_f16": ("i", "pipiiiippfppppp"),
-    "skg_ff_block_f16_keep": ("i", "pipiiiippfpppppiip"),
-    "skg_ff_block_proj_f16": ("i", "pipiiiippfpppppippiipiip"),
-    "skg_ff_block_proj_f16_hilo": ("i", "ppippiiiippfppppppippiipiip"),
-    "skg_xattn_block_f16": ("i", "pipiiiiiippfpppfp"),
-    "skg_xattn_block_f16_hilo": ("i", "ppippiiiiiippfpppfp"),
-    "skg_xattn_block_f16_hilo_keep": ("i", "ppippiiiiiippfpppfpppipip"),
-    "skg_xattn_block_f16_keep": ("i", "pipiiiiiippfpppfpppipip"),
+    "skg_ff_block_f16": ("i", "ppippiiiippfppppppippiipiip"),
+    "skg_xattn_block_f16": ("i", "ppippiiiiiippfpppfpppipip"),
     "skg_gemm_variant": ("i", "iiiii"),
     "skg_set_workspace": ("i", "pzp"),
-    "skg_conv3x3_f16": ("i", "pippiiiiiiippifup"),
-    "skg_conv3x3_f16_gn": ("i", "pippiiiiiiippifupip"),
+    "skg_conv3x3_f16": ("i", "pipppiiiiiiipppifupip"),
     "skg_groupnorm_scratch_floats": ("z", "ii"),
     "skg_groupnorm_stats": ("i", "piiiiifppp"),
-    "skg_groupnorm_fwd": ("i", "pipiiiiifppippp"),
-    "skg_groupnorm_from_partial": ("i", "pipiiiiifppippip"),
-    "skg_groupnorm_from_partial2": ("i", "pipiiiiiifppippipiip"),
-    "skg_groupnorm_apply": ("i", "pipiiiiipppip"),
+    "skg_groupnorm_fwd": ("i", "ppippiiiiifppippp"),
+    "skg_groupnorm_from_partial": ("i", "ppippiiiiiifppippipiip"),
+    "skg_groupnorm_apply": ("i", "ppipiiiiipppip"),
     "skg_groupnorm_bwd": ("i", "pipipipiiiiipppipp"),
-    "skg_layernorm_fwd": ("i", "pipiiippfpp"),
+    "skg_layernorm_fwd": ("i", "ppipiiippfpp"),
     "skg_layernorm_bwd": ("i", "pipipipiiippp"),
     "skg_geglu_fwd": ("i", "pipiiiip"),
     "skg_geglu_bwd": ("i", "pipipiiiip"),
-    "skg_attn_fwd": ("i", "pipipipipiiiiiifp"),
-    "skg_attn_fwd_causal": ("i", "pipipipipiiiiiifp"),
-    "skg_attn_fwd_rowv": ("i", "pipipipipiiiiiifp"),
+    "skg_attn_fwd": ("i", "pipipipipiiiiiifup"),
     "skg_attn_bwd_delta": ("i", "pipipiiiip"),
-    "skg_attn_bwd_dq": ("i", "pipipipipppiiiiiiifp"),
-    "skg_attn_bwd_dq_delta": ("i", "pipipipipipppiiiiiiifp"),
-    "skg_attn_bwd_dkv": ("i", "pipipipipppipiiiiiifp"),
+    "skg_attn_bwd_dq": ("i", "pipipipipippppiiiiiiifp"),
+    "skg_attn_bwd_dkv": ("i", "pipipipipppipiiiiiiifp"),
     "skg_transpose_f16": ("i", "pipiiip"),
     "skg_axpby_f16": ("i", "pipipiiiffp"),
     "skg_batch_copy_f16": ("i", "piipiiiiip"),
@@ -92,10 +71,8 @@ SIGNATURES = {
     "skg_sumpool2x2_f16": ("i", "pipiiiiip"),
     "skg_nchw_f32_to_nhwc_f16": ("i", "ppiiiip"),
     "skg_nhwc_f16_to_nchw_f32": ("i", "pipiiip"),
-    "skg_lgp_layer0_gather": ("i", "pipippfipiiip"),
-    "skg_lgp_layer0_scatter": ("i", "pipiiiip"),
-    "skg_lgp_layer0_gather_hw": ("i", "pipippfipiiiip"),
-    "skg_lgp_layer0_scatter_hw": ("i", "pipiiiiip"),
+    "skg_lgp_layer0_gather": ("i", "pipippfipiiiip"),
+    "skg_lgp_layer0_scatter": ("i", "pipiiiiip"),
     "skg_bn_scratch_floats": ("z", "ii"),
     "skg_bn_stats": ("i", "piiiiifppppp"),
     "skg_bn_stats_from_running": ("i", "ppiifpp"),
@@ -104,12 +81,10 @@ SIGNATURES = {
     "skg_colsum_scratch_floats": ("z", "i"),
     "skg_colsum_f16": ("i", "piiifppp"),
     "skg_bn_param_grads": ("i", "pipiiipfpppp"),
-    "skg_lgp_extra_features": ("i", "pfiiipip"),
-    "skg_lgp_extra_features_hw": ("i", "pfiiiipip"),
+    "skg_lgp_extra_features": ("i", "pfiiiipip"),
     "skg_lgp_mse_train": ("i", "pippipiifp"),
     "skg_adamw_step": ("i", "pppppzfffffifp"),
-    "skg_lgp_mse_seed": ("i", "pippipiifp"),
-    "skg_lgp_mse_seed_hw": ("i", "pippipiiifp"),
+    "skg_lgp_mse_seed": ("i", "pippipiiifp"),
     "skg_cfg_ddim_step": ("i", "ppiipppiifffffip"),
     "skg_softmax_rows_f16": ("i", "pipiiip"),
     "skg_image_postprocess": ("i", "pipziffp"),
@@ -124,8 +99,7 @@ SIGNATURES = {
     "skg_convt4x4s2_f16": ("i", "pippiiiiiipip"),
     "skg_a2s_patch_f16": ("i", "ppiiiip"),
     "skg_a2s_tail": ("i", "pippiiip"),
-    # injected-attention training (sat_train.py): additive entry points, same ABI version
-    "skg_attn_bwd_dkv_strided": ("i", "pipipipipppipiiiiiiifp"),
+    # injected-attention training (sat_train.py)
     "skg_wgrad_scratch_floats": ("z", "iii"),
     "skg_wgrad_f16": ("i", "pipiiiifipppp"),
     "skg_layernorm_param_scratch_floats": ("z", "i"),

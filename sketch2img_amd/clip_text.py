@@ -7,7 +7,7 @@ own class in oracle/clip_text.py + tests/golden/clip_text_tiny.npz).  Runs once 
 Layout: tokens fp16 [B * Lp, D], every prompt's L (= 77) tokens padded to Lp = a multiple of 8 rows (80) so the
 transposed V panel keeps 16-byte aligned rows; pad rows are never read as keys (Nkv = L) and are dropped at the end.
 The token-embedding row gather is data movement (torch.index_select on the fp16 table); q/k/v are one GEMM with bias,
-the causal softmax(QK^T)V is the flash kernel's CAUSAL instantiation (skg_attn_fwd_causal), out-proj / fc2 carry the
+the causal softmax(QK^T)V is the flash kernel's CAUSAL instantiation (skg_attn_fwd with SKG_ATTN_CAUSAL), out-proj / fc2 carry the
 residual in the GEMM epilogue, quick_gelu (SD 1.x) or exact gelu (SD 2.x) and LayerNorm are their own kernels.
 Tokenisation (BPE) is host-side text processing and stays with transformers' CLIPTokenizer (`PromptEncoder`).
 """

@@ -10,8 +10,8 @@
 // the B operand: element i of lane (q, g) is declared to be k-slot (g, i) <-> key
 // 32 s + 16 (i >> 2) + 4 g + (i & 3); the MFMA only needs A and B to agree on the k <-> key map, so
 // the A operand (V^T rows = head-dim index) is read with the same map: two ds_read_b64_tr_b16 per fragment out of
-// the ROW-MAJOR V tile (skg_attn_fwd_rowv; tfrag_rows below), or two 8-byte reads out of a tile stored transposed
-// when the caller hands over V^T (skg_attn_fwd, _causal).  No P round trip through LDS, no cross-lane transposes.
+// the ROW-MAJOR V tile (SKG_ATTN_ROWV; tfrag_rows below), or two 8-byte reads out of a tile stored transposed
+// when the caller hands over V^T (no SKG_ATTN_ROWV).  No P round trip through LDS, no cross-lane transposes.
 // The backward kernels read K^T, Q^T and dO^T fragments the same way from the row tiles they stage anyway, so
 // nothing on the UNet path needs skg_transpose_f16 any more.
 //
@@ -30,13 +30,13 @@ struct AttnParams {
   const half_t* Q; int ldq;
   const half_t* K; int ldk;
   const half_t* V; int ldv;       // row-major V (backward)
-  const half_t* Vt; int ldvt;     // forward: V^T (skg_attn_fwd, _causal) or the row-major V and its pitch (skg_attn_fwd_rowv)
+  const half_t* Vt; int ldvt;     // forward: V^T (skg_attn_fwd, also causal) or the row-major V and its pitch (SKG_ATTN_ROWV)
   const half_t* dO; int lddo;
   half_t* O; int ldo;             // fwd: O; dq: dQ; dkv: dK
   half_t* O2; int ldo2;           // dkv: dV
   float* lse;                     // [batch][heads][Nq]
   const float* delta;             // [batch][heads][Nq]
-  const half_t* Of; int ldof;     // dq with the delta prologue (skg_attn_bwd_dq_delta): the forward's O, and where delta is also stored
+  const half_t* Of; int ldof;     // dq with the delta prologue (skg_attn_bwd_dq without delta): the forward's O, and where delta is also stored
   float* delta_out;
   int batch, heads, Nq, Nkv, kv_stride, dh;
   float scale;
@@ -1469,9 +1469,13 @@ inline bool common_ok(int batch, int heads, int Nq, int Nkv, int kv_stride, int 
 
 }  // namespace
 
-static int attn_fwd_impl(const void* Q, int ldq, const void* K, int ldk, const void* Vt, int ldvt, void* O,
-                         int ldo, float* lse, int batch, int heads, int Nq, int Nkv, int kv_stride, int dh,
-                         float scale, bool causal, void* stream, bool vrow = false) {
+// SKG_ATTN_ROWV: V handed over ROW-MAJOR ([batch * kv_stride][ldvt], e.g. the third column block of a fused QKV projection) - the
+// kernel reads its fragments through the LDS transpose read, no V^T copy is needed; SKG_ATTN_CAUSAL: key j <= query i only
+extern "C" int skg_attn_fwd(const void* Q, int ldq, const void* K, int ldk, const void* Vt, int ldvt, void* O,
+                            int ldo, float* lse, int batch, int heads, int Nq, int Nkv, int kv_stride, int dh,
+                            float scale, unsigned flags, void* stream) {
+  const bool causal = flags & SKG_ATTN_CAUSAL, vrow = flags & SKG_ATTN_ROWV;
+  SKG_REQUIRE(!(flags & ~(SKG_ATTN_CAUSAL | SKG_ATTN_ROWV)) && !(causal && vrow));
   SKG_REQUIRE(Q && K && Vt && O && common_ok(batch, heads, Nq, Nkv, kv_stride, dh, !vrow));
   SKG_REQUIRE(ldq % 8 == 0 && ldk % 8 == 0 && ldvt % 8 == 0 && ldo % 4 == 0);
   SKG_REQUIRE(skg_aligned(Q, 16) && skg_aligned(K, 16) && skg_aligned(Vt, 16) && skg_aligned(O, 8));
@@ -1549,26 +1553,6 @@ static int attn_fwd_impl(const void* Q, int ldq, const void* K, int ldk, const v
   return SKG_OK;
 }
 
-extern "C" int skg_attn_fwd(const void* Q, int ldq, const void* K, int ldk, const void* Vt, int ldvt, void* O,
-                            int ldo, float* lse, int batch, int heads, int Nq, int Nkv, int kv_stride, int dh,
-                            float scale, void* stream) {
-  return attn_fwd_impl(Q, ldq, K, ldk, Vt, ldvt, O, ldo, lse, batch, heads, Nq, Nkv, kv_stride, dh, scale, false, stream);
-}
-
-// V handed over ROW-MAJOR ([batch * kv_stride][ldv], e.g. the third column block of a fused QKV projection): the kernel
-// reads its fragments through the LDS transpose read, no V^T copy is needed
-extern "C" int skg_attn_fwd_rowv(const void* Q, int ldq, const void* K, int ldk, const void* V, int ldv, void* O,
-                                 int ldo, float* lse, int batch, int heads, int Nq, int Nkv, int kv_stride, int dh,
-                                 float scale, void* stream) {
-  return attn_fwd_impl(Q, ldq, K, ldk, V, ldv, O, ldo, lse, batch, heads, Nq, Nkv, kv_stride, dh, scale, false, stream, true);
-}
-
-extern "C" int skg_attn_fwd_causal(const void* Q, int ldq, const void* K, int ldk, const void* Vt, int ldvt, void* O,
-                                   int ldo, float* lse, int batch, int heads, int Nq, int Nkv, int kv_stride, int dh,
-                                   float scale, void* stream) {
-  return attn_fwd_impl(Q, ldq, K, ldk, Vt, ldvt, O, ldo, lse, batch, heads, Nq, Nkv, kv_stride, dh, scale, true, stream);
-}
-
 extern "C" int skg_attn_bwd_delta(const void* O, int ldo, const void* dO, int lddo, float* delta, int batch,
                                   int heads, int Nq, int dh, void* stream) {
   SKG_REQUIRE(O && dO && delta && batch > 0 && heads > 0 && Nq > 0 && dh % 8 == 0 && ldo % 8 == 0 && lddo % 8 == 0);
@@ -1580,9 +1564,13 @@ extern "C" int skg_attn_bwd_delta(const void* O, int ldo, const void* dO, int ld
   return SKG_OK;
 }
 
-static int attn_bwd_dq_impl(const void* Q, int ldq, const void* K, int ldk, const void* V, int ldv, const void* dO, int lddo,
-                            const float* lse, const float* delta, void* dQ, int lddq, int batch, int heads, int Nq, int Nkv,
-                            int kv_stride, int dh, float scale, void* stream, const void* O, int ldo, float* delta_out) {
+// delta == NULL: skg_attn_bwd_delta in the prologue (round 5) - delta[b][h][q] = sum_d dO O is formed from the dO fragments the launch
+// loads anyway and O, used, and stored to delta_out for the dK / dV launch that follows: one launch and one read of dO fewer per
+// attention.  With delta given, O / ldo / delta_out are not looked at.
+extern "C" int skg_attn_bwd_dq(const void* Q, int ldq, const void* K, int ldk, const void* V, int ldv, const void* dO, int lddo,
+                               const void* O, int ldo, const float* lse, const float* delta, float* delta_out, void* dQ, int lddq,
+                               int batch, int heads, int Nq, int Nkv, int kv_stride, int dh, float scale, void* stream) {
+  if (delta) { O = nullptr; ldo = 0; delta_out = nullptr; }
   SKG_REQUIRE(Q && K && V && dO && lse && (delta || (O && delta_out)) && dQ && common_ok(batch, heads, Nq, Nkv, kv_stride, dh, false));
   SKG_REQUIRE(!O || (ldo % 8 == 0 && skg_aligned(O, 16)));
   SKG_REQUIRE(ldq % 8 == 0 && ldk % 8 == 0 && ldv % 8 == 0 && lddo % 8 == 0 && lddq % 4 == 0);
@@ -1609,29 +1597,12 @@ static int attn_bwd_dq_impl(const void* Q, int ldq, const void* K, int ldk, cons
   return SKG_OK;
 }
 
-extern "C" int skg_attn_bwd_dq(const void* Q, int ldq, const void* K, int ldk, const void* V, int ldv,
-                               const void* dO, int lddo, const float* lse,
-                               const float* delta, void* dQ, int lddq, int batch, int heads, int Nq, int Nkv,
-                               int kv_stride, int dh, float scale, void* stream) {
-  SKG_REQUIRE(delta);
-  return attn_bwd_dq_impl(Q, ldq, K, ldk, V, ldv, dO, lddo, lse, delta, dQ, lddq, batch, heads, Nq, Nkv, kv_stride, dh, scale, stream,
-                          nullptr, 0, nullptr);
-}
-
-// ... with skg_attn_bwd_delta in its prologue (round 5): delta[b][h][q] = sum_d dO O is formed from the dO fragments the launch loads
-// anyway, used, and stored to delta_out for the dK / dV launch that follows - one launch and one read of dO fewer per attention
-extern "C" int skg_attn_bwd_dq_delta(const void* Q, int ldq, const void* K, int ldk, const void* V, int ldv, const void* dO, int lddo,
-                                     const void* O, int ldo, const float* lse, float* delta_out, void* dQ, int lddq, int batch,
-                                     int heads, int Nq, int Nkv, int kv_stride, int dh, float scale, void* stream) {
-  SKG_REQUIRE(O && delta_out);
-  return attn_bwd_dq_impl(Q, ldq, K, ldk, V, ldv, dO, lddo, lse, nullptr, dQ, lddq, batch, heads, Nq, Nkv, kv_stride, dh, scale, stream,
-                          O, ldo, delta_out);
-}
-
-static int attn_bwd_dkv_impl(const void* Q, int ldq, const void* K, int ldk,
-                             const void* V, int ldv, const void* dO, int lddo,
-                             const float* lse, const float* delta, void* dK, int lddk, void* dV, int lddv,
-                             int batch, int heads, int Nq, int Nkv, int kv_stride, int dh, float scale, void* stream) {
+// K, V, dK, dV rows of batch row b start at b * kv_stride (>= Nkv: a padded K / V buffer; dense: kv_stride = Nkv); rows
+// Nkv .. kv_stride - 1 of dK / dV are not written
+extern "C" int skg_attn_bwd_dkv(const void* Q, int ldq, const void* K, int ldk,
+                                const void* V, int ldv, const void* dO, int lddo,
+                                const float* lse, const float* delta, void* dK, int lddk, void* dV, int lddv,
+                                int batch, int heads, int Nq, int Nkv, int kv_stride, int dh, float scale, void* stream) {
   SKG_REQUIRE(Q && K && V && dO && lse && delta && dK && dV && common_ok(batch, heads, Nq, Nkv, kv_stride, dh, false));
   SKG_REQUIRE(ldq % 8 == 0 && ldk % 8 == 0 && ldv % 8 == 0 && lddo % 8 == 0 && lddk % 4 == 0 && lddv % 4 == 0);
   SKG_REQUIRE(skg_aligned(Q, 16) && skg_aligned(K, 16) && skg_aligned(V, 16) &&
@@ -1656,22 +1627,6 @@ static int attn_bwd_dkv_impl(const void* Q, int ldq, const void* K, int ldk,
   }
   SKG_CHECK_LAUNCH("skg_attn_bwd_dkv");
   return SKG_OK;
-}
-
-extern "C" int skg_attn_bwd_dkv(const void* Q, int ldq, const void* K, int ldk,
-                                const void* V, int ldv, const void* dO, int lddo,
-                                const float* lse, const float* delta, void* dK, int lddk, void* dV, int lddv,
-                                int batch, int heads, int Nq, int Nkv, int dh, float scale, void* stream) {
-  return attn_bwd_dkv_impl(Q, ldq, K, ldk, V, ldv, dO, lddo, lse, delta, dK, lddk, dV, lddv, batch, heads, Nq, Nkv, Nkv, dh, scale, stream);
-}
-
-// K, V, dK, dV rows of batch row b start at b * kv_stride (a padded K / V buffer); rows Nkv .. kv_stride - 1 of dK / dV are not written
-extern "C" int skg_attn_bwd_dkv_strided(const void* Q, int ldq, const void* K, int ldk,
-                                        const void* V, int ldv, const void* dO, int lddo,
-                                        const float* lse, const float* delta, void* dK, int lddk, void* dV, int lddv,
-                                        int batch, int heads, int Nq, int Nkv, int kv_stride, int dh, float scale, void* stream) {
-  SKG_REQUIRE(kv_stride >= Nkv);
-  return attn_bwd_dkv_impl(Q, ldq, K, ldk, V, ldv, dO, lddo, lse, delta, dK, lddk, dV, lddv, batch, heads, Nq, Nkv, kv_stride, dh, scale, stream);
 }
 
 #ifdef SKG_PHASES

@@ -43,11 +43,11 @@ struct FFParams {
   float* stats;            // optional [M][2]: LayerNorm mean / rstd (what the backward of the norm reads)
   half_t* keep; int ldkeep; int keep_from;     // optional: rows >= keep_from also store the FF1 output fp16(W1 a + b1), interleaved pack
   int nt_out;              // store Y non-temporally (the output stream then does not evict the weight chunks from L2)
-  // PROJ (skg_ff_block_proj_f16): Transformer2DModel.proj_out + the outer residual in the same launch - five more weight chunks
+  // PROJ (skg_ff_block_f16 with bias_proj): Transformer2DModel.proj_out + the outer residual in the same launch - five more weight chunks
   // behind the nch feed-forward ones (their 40 W1-slot pieces = 4 output tiles x 10 k-steps of W_proj, k order permuted to the
   // accumulator layout), Y = R + bp + W_proj . fp16(X + FF(X)); optionally the GroupNorm partial sums of Y
   const half_t* bp; const half_t* R; int ldr;
-  const half_t* Rl;        // HILO + PROJ (skg_ff_block_proj_f16_hilo): the outer residual is the pair R + Rl (pitch ldr)
+  const half_t* Rl;        // HILO + PROJ (both arms): the outer residual is the pair R + Rl (pitch ldr)
   float* gn_partial; int gn_hw, gn_groups;
   int nch_w1;              // W1-slot chunks the weight pack holds: nch, or nch + 5 with PROJ
 };
@@ -58,7 +58,7 @@ constexpr int MAXCH = 40;
 // 3 = no LDS fragment reads (a register stands in for every A operand), 4 = 1 + 3
 // SCHED (SKG_FFB_SCHED, A/B of issue orders): 0 = a gated PAIR after the MFMAs of every second k-step, 1 = the same with the
 // two waves of a SIMD in alternate k-steps, 2 = the pair's arithmetic in four stages spread over the MFMAs of two k-steps
-// HILO (accuracy mode, skg_ff_block_f16_hilo): LayerNorm reads hi + lo, the residual sum is formed in fp32 on the pair and
+// HILO (accuracy mode, skg_ff_block_f16 with X_lo): LayerNorm reads hi + lo, the residual sum is formed in fp32 on the pair and
 // stored as hi = fp16(v), lo = fp16(v - hi); everything between is the same kernel
 template <int KS, int PROBE = 0, int SCHED = 0, bool HILO = false, bool PROJ = false>
 __global__ __launch_bounds__(512, 1) void ff_block_kernel(const FFParams p) {
@@ -523,11 +523,16 @@ __global__ __launch_bounds__(512, 1) void ff_block_kernel(const FFParams p) {
 
 }  // namespace
 
-static int ff_block_impl(const void* X, const void* Xl, int ldx, void* Y, void* Yl, int ldy, int M, int C, int F, const void* gamma,
-                         const void* beta, float eps, const void* Wpack, const float* bias1_pack, const void* bias2,
-                         float* stats, void* H, int ldh, int keep_from, void* stream, const void* bias_proj = nullptr,
-                         const void* R = nullptr, int ldr = 0, float* gn_partial = nullptr, int gn_hw = 0, int gn_groups = 0,
-                         const void* Rl = nullptr) {
+// One entry point (include/skg.h): X_lo / Y_lo != NULL: pair input and output (accuracy mode); H != NULL: the FF1 stash of rows >=
+// keep_from; bias_proj != NULL: followed by Transformer2DModel.proj_out + the outer residual R (+ R_lo on pairs) in the same launch,
+//   Y = R + bias_proj + W_proj . fp16(X + FF(LayerNorm(X)))        (Y must not alias X; it may alias R)
+// with five more Wpack chunks behind the F / 32 feed-forward ones (unet.pack_ff_block(..., w_proj)) - proj_out takes a pair block
+// output as the pair it is (W . hi + W . lo on the same weight fragments); gn_partial != NULL (with bias_proj): also the GroupNorm
+// partial sums of Y's hi part, [M / HW][HW / 128][groups][2] as skg_gemm_f16 leaves them
+extern "C" int skg_ff_block_f16(const void* X, const void* Xl, int ldx, void* Y, void* Yl, int ldy, int M, int C, int F,
+                                const void* gamma, const void* beta, float eps, const void* Wpack, const float* bias1_pack,
+                                const void* bias2, const void* bias_proj, const void* R, const void* Rl, int ldr, float* stats,
+                                void* H, int ldh, int keep_from, float* gn_partial, int gn_hw, int gn_groups, void* stream) {
   SKG_REQUIRE(X && Y && gamma && beta && Wpack && bias1_pack && bias2 && M > 0 && (Xl != nullptr) == (Yl != nullptr));
   SKG_REQUIRE(!bias_proj || (R && (Rl != nullptr) == (Xl != nullptr) && ldr % 4 == 0 && ldr >= C && skg_aligned(bias_proj, 8) && skg_aligned(R, 8) &&
                              skg_aligned(Rl, 8) && X != Y));
@@ -575,48 +580,4 @@ static int ff_block_impl(const void* X, const void* Xl, int ldx, void* Y, void* 
   else hipLaunchKernelGGL((ff_block_kernel<10>), grid, dim3(512), 0, (hipStream_t)stream, p);
   SKG_CHECK_LAUNCH("skg_ff_block_f16");
   return SKG_OK;
-}
-
-extern "C" int skg_ff_block_f16_keep(const void* X, int ldx, void* Y, int ldy, int M, int C, int F, const void* gamma,
-                                     const void* beta, float eps, const void* Wpack, const float* bias1_pack,
-                                     const void* bias2, float* stats, void* H, int ldh, int keep_from, void* stream) {
-  return ff_block_impl(X, nullptr, ldx, Y, nullptr, ldy, M, C, F, gamma, beta, eps, Wpack, bias1_pack, bias2, stats, H, ldh, keep_from, stream);
-}
-
-extern "C" int skg_ff_block_f16(const void* X, int ldx, void* Y, int ldy, int M, int C, int F, const void* gamma,
-                                const void* beta, float eps, const void* Wpack, const float* bias1_pack,
-                                const void* bias2, float* stats, void* stream) {
-  return ff_block_impl(X, nullptr, ldx, Y, nullptr, ldy, M, C, F, gamma, beta, eps, Wpack, bias1_pack, bias2, stats, nullptr, 0, 0, stream);
-}
-
-// ... followed by Transformer2DModel.proj_out + the outer residual in the same launch:
-//   Y = R + bias_proj + W_proj . fp16(X + FF(LayerNorm(X)))        (Y must not alias X; it may alias R)
-// Wpack holds five more chunks behind the F / 32 feed-forward ones (unet.pack_ff_block(..., w_proj)); stats / H / keep_from as _keep
-// (H == NULL: no stash); gn_partial != NULL: also the GroupNorm partial sums of Y, [M / HW][HW / 128][groups][2] as skg_gemm_f16_gn
-extern "C" int skg_ff_block_proj_f16(const void* X, int ldx, void* Y, int ldy, int M, int C, int F, const void* gamma, const void* beta,
-                                     float eps, const void* Wpack, const float* bias1_pack, const void* bias2, const void* bias_proj,
-                                     const void* R, int ldr, float* stats, void* H, int ldh, int keep_from, float* gn_partial, int HW,
-                                     int groups, void* stream) {
-  SKG_REQUIRE(bias_proj && R);
-  return ff_block_impl(X, nullptr, ldx, Y, nullptr, ldy, M, C, F, gamma, beta, eps, Wpack, bias1_pack, bias2, stats, H, ldh, keep_from, stream,
-                       bias_proj, R, ldr, gn_partial, HW, groups);
-}
-
-// accuracy mode, round 5: skg_ff_block_proj_f16 on pairs - X + X_lo in, Y + Y_lo out, outer residual R + R_lo (pitch ldr); proj_out takes
-// the block output as the pair it is (W . hi + W . lo on the same weight fragments); gn_partial: statistics of Y's hi part
-extern "C" int skg_ff_block_proj_f16_hilo(const void* X, const void* X_lo, int ldx, void* Y, void* Y_lo, int ldy, int M, int C, int F,
-                                          const void* gamma, const void* beta, float eps, const void* Wpack, const float* bias1_pack,
-                                          const void* bias2, const void* bias_proj, const void* R, const void* R_lo, int ldr, float* stats,
-                                          void* H, int ldh, int keep_from, float* gn_partial, int HW, int groups, void* stream) {
-  SKG_REQUIRE(X_lo && Y_lo && bias_proj && R && R_lo);
-  return ff_block_impl(X, X_lo, ldx, Y, Y_lo, ldy, M, C, F, gamma, beta, eps, Wpack, bias1_pack, bias2, stats, H, ldh, keep_from, stream,
-                       bias_proj, R, ldr, gn_partial, HW, groups, R_lo);
-}
-
-// accuracy mode: the same launch on a pair input X + X_lo (pitch ldx) with a pair output Y + Y_lo (pitch ldy); H / keep_from as _keep
-extern "C" int skg_ff_block_f16_hilo(const void* X, const void* X_lo, int ldx, void* Y, void* Y_lo, int ldy, int M, int C, int F,
-                                     const void* gamma, const void* beta, float eps, const void* Wpack, const float* bias1_pack,
-                                     const void* bias2, float* stats, void* H, int ldh, int keep_from, void* stream) {
-  SKG_REQUIRE(X_lo && Y_lo);
-  return ff_block_impl(X, X_lo, ldx, Y, Y_lo, ldy, M, C, F, gamma, beta, eps, Wpack, bias1_pack, bias2, stats, H, ldh, keep_from, stream);
 }

@@ -328,13 +328,6 @@ extern "C" int skg_gemm_variant(int M, int N, int K, int Cin, int mode) {
   return v2 ? 2000 + v2 : 1000 + (use_wide(M, N) ? 128 : 64);
 }
 
-static int gemm_impl(const void* A, int lda, const void* B, int ldb, void* C, int ldc, int M, int N, int K,
-                     const void* bias, const void* residual, int ldr, float alpha, unsigned flags, float* gn_partial,
-                     int HW, int groups, void* stream, void* c_lo = nullptr, const void* res_lo = nullptr);
-static int conv_impl(const void* X, int ldx, const void* Wp, void* Y, int ldy, int rows, int IH, int IW, int Cin,
-                     int Cout, int mode, const void* bias, const void* residual, int ldr, float alpha, unsigned flags,
-                     float* gn_partial, int groups, void* stream, void* c_lo = nullptr, const void* res_lo = nullptr);
-
 extern "C" int skg_gemm_f16_geglu_keep(const void* A, int lda, const void* B, int ldb, void* Y, int ldy, void* H,
                                        int ldh, int M, int N, int K, const void* bias, void* stream) {
   SKG_REQUIRE(A && B && Y && H && M > 0 && N > 0 && K > 0 && K % 64 == 0 && N % 16 == 0);
@@ -349,7 +342,7 @@ extern "C" int skg_gemm_f16_geglu_keep(const void* A, int lda, const void* B, in
   return launch<MODE_DIRECT>(p, (hipStream_t)stream);
 }
 
-// 1 when skg_gemm_f16_gn / skg_conv3x3_f16_gn of this shape (contiguous, 16-byte aligned output) gets its partial sums
+// 1 when skg_gemm_f16 / skg_conv3x3_f16 with gn_partial of this shape (contiguous, 16-byte aligned output) gets its partial sums
 // from the kernel's own epilogue, 0 when the stand-alone statistics pass follows (bench.py spells kernel names from it)
 extern "C" int skg_gemm_gn_fused(int M, int N, int K, int Cin, int mode, int HW, int groups) {
   if (HW <= 0 || groups <= 0 || M <= 0 || N <= 0) return 0;
@@ -365,10 +358,39 @@ extern "C" int skg_gemm_gn_fused(int M, int N, int K, int Cin, int mode, int HW,
   return (skg_gemm8_eligible(q, mode) ? skg_gemm8_fuses_gn(q, mode) : skg_gemm2_fuses_gn(q, mode)) ? 1 : 0;
 }
 
-extern "C" int skg_gemm_f16(const void* A, int lda, const void* B, int ldb, void* C, int ldc, int M,
-                            int N, int K, const void* bias, const void* residual, int ldr,
-                            float alpha, unsigned flags, void* stream) {
-  return gemm_impl(A, lda, B, ldb, C, ldc, M, N, K, bias, residual, ldr, alpha, flags, nullptr, 0, 0, stream);
+static bool gn_args_ok(const float* partial, int M, int N, int HW, int groups, int ldc, unsigned flags) {
+  return partial && HW > 0 && HW % 128 == 0 && HW / 128 <= 128 && M % HW == 0 && groups > 0 && groups <= 64 &&
+         N % groups == 0 && N % 8 == 0 && (N / groups) % 2 == 0 && (N / groups) >= 4 && N <= 4096 && ldc % 8 == 0 &&
+         !(flags & (SKG_EPI_OUT_F32 | SKG_EPI_GEGLU));
+}
+
+// accuracy mode (include/skg.h): what a launch with the lo half of an output or residual pair needs on top of the plain one
+static bool pair_args_ok(const void* C, const void* C_lo, int ldc, const void* residual, const void* residual_lo, int ldr, int K,
+                         unsigned flags) {
+  return !(flags & (SKG_EPI_OUT_F32 | SKG_EPI_GEGLU)) && K % 64 == 0 && ldc % 8 == 0 && skg_aligned(C, 16) &&
+         (!C_lo || skg_aligned(C_lo, 16)) && (!residual_lo || skg_aligned(residual_lo, 16)) &&
+         (!residual || skg_aligned(residual, 16)) && ((!residual && !residual_lo) || ldr % 8 == 0);
+}
+
+extern "C" int skg_gemm_f16(const void* A, int lda, const void* B, int ldb, void* C, void* C_lo, int ldc, int M, int N, int K,
+                            const void* bias, const void* residual, const void* residual_lo, int ldr, float alpha,
+                            unsigned flags, float* gn_partial, int HW, int groups, void* stream) {
+  SKG_REQUIRE(!(C_lo || residual_lo) || pair_args_ok(C, C_lo, ldc, residual, residual_lo, ldr, K, flags));
+  SKG_REQUIRE(!gn_partial || (gn_args_ok(gn_partial, M, N, HW, groups, ldc, flags) && skg_aligned(C, 16)));
+  SKG_REQUIRE(A && B && C && M > 0 && N > 0 && K > 0);
+  SKG_REQUIRE(K % 32 == 0 && N % 8 == 0 && lda % 8 == 0 && ldb % 8 == 0 && ldc % 4 == 0);
+  SKG_REQUIRE(skg_aligned(A, 16) && skg_aligned(B, 16) && skg_aligned(C, 8));
+  SKG_REQUIRE(!bias || skg_aligned(bias, 8));
+  SKG_REQUIRE(!residual || (skg_aligned(residual, 8) && ldr % 4 == 0));
+  SKG_REQUIRE(lda >= K && ldb >= K && ldc >= ((flags & SKG_EPI_GEGLU) ? N / 2 : N));
+  GemmParams p{};
+  p.A = (const half_t*)A; p.lda = lda; p.B = (const half_t*)B; p.ldb = ldb; p.C = C; p.ldc = ldc;
+  p.bias = (const half_t*)bias; p.res = (const half_t*)residual; p.ldr = ldr;
+  p.M = M; p.N = N; p.K = K; p.alpha = alpha; p.flags = flags;
+  if (gn_partial) { p.gn_partial = gn_partial; p.gn_hw = HW; p.gn_groups = groups; }
+  p.c_lo = (half_t*)C_lo; p.res_lo = (const half_t*)residual_lo;
+  ws_attach(p, (hipStream_t)stream);
+  return launch<MODE_DIRECT>(p, (hipStream_t)stream);
 }
 
 extern "C" int skg_gemm_f16_rows(const void* A, int lda, const void* B, int ldb, void* C, int ldc, int M, int N, int K,
@@ -384,49 +406,6 @@ extern "C" int skg_gemm_f16_rows(const void* A, int lda, const void* B, int ldb,
   if (!skg_gemm2_try_launch(p, MODE_DIRECT, (hipStream_t)stream)) return SKG_E_UNSUPPORTED;
   SKG_CHECK_LAUNCH("skg_gemm_f16_rows");
   return SKG_OK;
-}
-
-static int gemm_impl(const void* A, int lda, const void* B, int ldb, void* C, int ldc, int M, int N, int K,
-                     const void* bias, const void* residual, int ldr, float alpha, unsigned flags, float* gn_partial,
-                     int HW, int groups, void* stream, void* c_lo, const void* res_lo) {
-  SKG_REQUIRE(A && B && C && M > 0 && N > 0 && K > 0);
-  SKG_REQUIRE(K % 32 == 0 && N % 8 == 0 && lda % 8 == 0 && ldb % 8 == 0 && ldc % 4 == 0);
-  SKG_REQUIRE(skg_aligned(A, 16) && skg_aligned(B, 16) && skg_aligned(C, 8));
-  SKG_REQUIRE(!bias || skg_aligned(bias, 8));
-  SKG_REQUIRE(!residual || (skg_aligned(residual, 8) && ldr % 4 == 0));
-  SKG_REQUIRE(lda >= K && ldb >= K && ldc >= ((flags & SKG_EPI_GEGLU) ? N / 2 : N));
-  GemmParams p{};
-  p.A = (const half_t*)A; p.lda = lda; p.B = (const half_t*)B; p.ldb = ldb; p.C = C; p.ldc = ldc;
-  p.bias = (const half_t*)bias; p.res = (const half_t*)residual; p.ldr = ldr;
-  p.M = M; p.N = N; p.K = K; p.alpha = alpha; p.flags = flags;
-  p.gn_partial = gn_partial; p.gn_hw = HW; p.gn_groups = groups;
-  p.c_lo = (half_t*)c_lo; p.res_lo = (const half_t*)res_lo;
-  ws_attach(p, (hipStream_t)stream);
-  return launch<MODE_DIRECT>(p, (hipStream_t)stream);
-}
-
-static bool gn_args_ok(const float* partial, int M, int N, int HW, int groups, int ldc, unsigned flags) {
-  return partial && HW > 0 && HW % 128 == 0 && HW / 128 <= 128 && M % HW == 0 && groups > 0 && groups <= 64 &&
-         N % groups == 0 && N % 8 == 0 && (N / groups) % 2 == 0 && (N / groups) >= 4 && N <= 4096 && ldc % 8 == 0 &&
-         !(flags & (SKG_EPI_OUT_F32 | SKG_EPI_GEGLU));
-}
-
-extern "C" int skg_gemm_f16_gn(const void* A, int lda, const void* B, int ldb, void* C, int ldc, int M, int N, int K,
-                               const void* bias, const void* residual, int ldr, float alpha, unsigned flags,
-                               float* gn_partial, int HW, int groups, void* stream) {
-  SKG_REQUIRE(gn_args_ok(gn_partial, M, N, HW, groups, ldc, flags) && skg_aligned(C, 16));
-  return gemm_impl(A, lda, B, ldb, C, ldc, M, N, K, bias, residual, ldr, alpha, flags, gn_partial, HW, groups, stream);
-}
-
-extern "C" int skg_conv3x3_f16_gn(const void* X, int ldx, const void* Wp, void* Y, int ldy, int rows, int IH, int IW,
-                                  int Cin, int Cout, int mode, const void* bias, const void* residual, int ldr,
-                                  float alpha, unsigned flags, float* gn_partial, int groups, void* stream) {
-  const int up = (mode == SKG_CONV_UP2 || mode == SKG_CONV_S2T), dn = (mode == SKG_CONV_S2 || mode == SKG_CONV_S2A);
-  const int OH = up ? IH * 2 : dn ? IH / 2 : IH, OW = up ? IW * 2 : dn ? IW / 2 : IW;
-  SKG_REQUIRE(rows > 0 && OH > 0 && OW > 0);
-  SKG_REQUIRE(gn_args_ok(gn_partial, rows * OH * OW, Cout, OH * OW, groups, ldy, flags) && skg_aligned(Y, 16));
-  return conv_impl(X, ldx, Wp, Y, ldy, rows, IH, IW, Cin, Cout, mode, bias, residual, ldr, alpha, flags, gn_partial,
-                   groups, stream);
 }
 
 // ---- conv2 + conv_shortcut of a ResnetBlock as ONE implicit GEMM (include/skg.h) -------------------------------------------
@@ -533,28 +512,17 @@ extern "C" int skg_conv3x3_wino_f16(const void* X, int ldx, const void* U, void*
   return SKG_OK;
 }
 
-extern "C" int skg_conv3x3_up2_f16(const void* X, int ldx, const void* Wpp, void* Y, int ldy, int rows, int IH, int IW,
-                                   int Cin, int Cout, const void* bias, void* stream) {
-  return conv_up2_impl(X, ldx, Wpp, Y, nullptr, ldy, rows, IH, IW, Cin, Cout, 0, bias, stream);
-}
-
-// Accuracy mode: the input is the pair buffer [x_hi | x_lo] (2 C channels per pixel, pitch ldx), the pre-summed polyphase weights
-// are (hi, lo) pairs too - their fp16 rounding would otherwise cost the margin of the eps bound (EXPERIMENTS.md round 3) - and a
-// tap's K axis is [x_hi | x_lo | x_hi] . [W_hi | W_hi | W_lo] (x_lo . W_lo is dropped: 2^-22): Wpp3 [4][Cout][4 taps][3 C];
-// the output is the pair Y + Y_lo.  12 tap-products of C channels per low-res pixel and phase against 18 for the 9-tap pair form.
-extern "C" int skg_conv3x3_up2_f16_hilo(const void* X2, int ldx, const void* Wpp3, void* Y, void* Y_lo, int ldy, int rows, int IH,
-                                        int IW, int C, int Cout, const void* bias, void* stream) {
-  SKG_REQUIRE(Y_lo && C % 64 == 0);
-  return conv_up2_impl(X2, ldx, Wpp3, Y, Y_lo, ldy, rows, IH, IW, 3 * C, Cout, 2 * C, bias, stream);
-}
-
-// Accuracy mode, round 5: the polyphase launch of skg_conv3x3_up2_f16 on the hi part of the stream with a PAIR output.  Of the three
-// K-thirds of the form above, x_lo W_hi and x_hi W_lo each move eps by ~1 % of the mode's distance from fp32 (tools/eps_decompose_up.py:
-// rel 5.00e-4 -> 5.18e-4 with both dropped) and cost two thirds of the upsamplers' time, the largest single item of the mode's price.
-extern "C" int skg_conv3x3_up2_f16_pairout(const void* X, int ldx, const void* Wpp, void* Y, void* Y_lo, int ldy, int rows, int IH,
-                                           int IW, int Cin, int Cout, const void* bias, void* stream) {
-  SKG_REQUIRE(Y_lo);
-  return conv_up2_impl(X, ldx, Wpp, Y, Y_lo, ldy, rows, IH, IW, Cin, Cout, 0, bias, stream);
+// pair_in (accuracy mode): the input is the pair buffer [x_hi | x_lo] (2 C channels per pixel, pitch ldx), the pre-summed polyphase
+// weights are (hi, lo) pairs too - their fp16 rounding would otherwise cost the margin of the eps bound (EXPERIMENTS.md round 3) -
+// and a tap's K axis is [x_hi | x_lo | x_hi] . [W_hi | W_hi | W_lo] (x_lo . W_lo is dropped: 2^-22): Wpp3 [4][Cout][4 taps][3 C]; the
+// output is the pair Y + Y_lo.  12 tap-products of C channels per low-res pixel and phase against 18 for the 9-tap pair form.
+// Y_lo alone (round 5): the plain launch on the hi part of the stream with a PAIR output.  Of the three K-thirds of the form above,
+// x_lo W_hi and x_hi W_lo each move eps by ~1 % of the mode's distance from fp32 (tools/eps_decompose_up.py: rel 5.00e-4 -> 5.18e-4
+// with both dropped) and cost two thirds of the upsamplers' time, the largest single item of the mode's price.
+extern "C" int skg_conv3x3_up2_f16(const void* X, int ldx, const void* Wpp, void* Y, void* Y_lo, int ldy, int rows, int IH, int IW,
+                                   int Cin, int Cout, int pair_in, const void* bias, void* stream) {
+  SKG_REQUIRE(!pair_in || (Y_lo && Cin % 64 == 0));
+  return conv_up2_impl(X, ldx, Wpp, Y, Y_lo, ldy, rows, IH, IW, pair_in ? 3 * Cin : Cin, Cout, pair_in ? 2 * Cin : 0, bias, stream);
 }
 
 // dX of the polyphase upsample + conv above = ONE 4 x 4 stride-2 convolution (padding 1) over dY at the upsampled size with
@@ -579,63 +547,21 @@ extern "C" int skg_conv4x4s2_f16(const void* X, int ldx, const void* W16, void* 
   return SKG_OK;
 }
 
-// ---- accuracy mode: outputs / residuals as (hi, lo) pairs of fp16 tensors (include/skg.h) ------------------------------
-extern "C" int skg_gemm_f16_hilo(const void* A, int lda, const void* B, int ldb, void* C, void* C_lo, int ldc, int M, int N,
-                                 int K, const void* bias, const void* residual, const void* residual_lo, int ldr,
-                                 float alpha, unsigned flags, void* stream) {
-  SKG_REQUIRE((C_lo || residual_lo) && !(flags & (SKG_EPI_OUT_F32 | SKG_EPI_GEGLU)) && K % 64 == 0 && ldc % 8 == 0);
-  SKG_REQUIRE(skg_aligned(C, 16) && (!C_lo || skg_aligned(C_lo, 16)) && (!residual_lo || skg_aligned(residual_lo, 16)) &&
-              (!residual || skg_aligned(residual, 16)) && ((!residual && !residual_lo) || ldr % 8 == 0));
-  return gemm_impl(A, lda, B, ldb, C, ldc, M, N, K, bias, residual, ldr, alpha, flags, nullptr, 0, 0, stream, C_lo, residual_lo);
-}
-
-extern "C" int skg_conv3x3_f16_hilo(const void* X, int ldx, const void* Wp, void* Y, void* Y_lo, int ldy, int rows, int IH,
-                                    int IW, int Cin, int Cout, int mode, const void* bias, const void* residual,
-                                    const void* residual_lo, int ldr, float alpha, unsigned flags, void* stream) {
-  SKG_REQUIRE((Y_lo || residual_lo) && !(flags & (SKG_EPI_OUT_F32 | SKG_EPI_GEGLU)) && Cin % 64 == 0 && ldy % 8 == 0);
-  SKG_REQUIRE(skg_aligned(Y, 16) && (!Y_lo || skg_aligned(Y_lo, 16)) && (!residual_lo || skg_aligned(residual_lo, 16)) &&
-              (!residual || skg_aligned(residual, 16)) && ((!residual && !residual_lo) || ldr % 8 == 0));
-  return conv_impl(X, ldx, Wp, Y, ldy, rows, IH, IW, Cin, Cout, mode, bias, residual, ldr, alpha, flags, nullptr, 0, stream,
-                   Y_lo, residual_lo);
-}
-
-// ... and the GroupNorm partial sums of the OUTPUT's hi part with it (what skg_groupnorm_from_partial_hilo folds): from the
-// epilogue of the kernel that runs where its tile can (256 x 320, 128 x 160), else from the stand-alone pass
-extern "C" int skg_gemm_f16_hilo_gn(const void* A, int lda, const void* B, int ldb, void* C, void* C_lo, int ldc, int M, int N,
-                                    int K, const void* bias, const void* residual, const void* residual_lo, int ldr,
-                                    float alpha, unsigned flags, float* gn_partial, int HW, int groups, void* stream) {
-  SKG_REQUIRE((C_lo || residual_lo) && !(flags & (SKG_EPI_OUT_F32 | SKG_EPI_GEGLU)) && K % 64 == 0 && ldc % 8 == 0);
-  SKG_REQUIRE(skg_aligned(C, 16) && (!C_lo || skg_aligned(C_lo, 16)) && (!residual_lo || skg_aligned(residual_lo, 16)) &&
-              (!residual || skg_aligned(residual, 16)) && ((!residual && !residual_lo) || ldr % 8 == 0));
-  SKG_REQUIRE(gn_args_ok(gn_partial, M, N, HW, groups, ldc, flags));
-  return gemm_impl(A, lda, B, ldb, C, ldc, M, N, K, bias, residual, ldr, alpha, flags, gn_partial, HW, groups, stream, C_lo,
-                   residual_lo);
-}
-
-extern "C" int skg_conv3x3_f16_hilo_gn(const void* X, int ldx, const void* Wp, void* Y, void* Y_lo, int ldy, int rows, int IH,
-                                       int IW, int Cin, int Cout, int mode, const void* bias, const void* residual,
-                                       const void* residual_lo, int ldr, float alpha, unsigned flags, float* gn_partial,
-                                       int groups, void* stream) {
-  SKG_REQUIRE((Y_lo || residual_lo) && !(flags & (SKG_EPI_OUT_F32 | SKG_EPI_GEGLU)) && Cin % 64 == 0 && ldy % 8 == 0);
-  SKG_REQUIRE(skg_aligned(Y, 16) && (!Y_lo || skg_aligned(Y_lo, 16)) && (!residual_lo || skg_aligned(residual_lo, 16)) &&
-              (!residual || skg_aligned(residual, 16)) && ((!residual && !residual_lo) || ldr % 8 == 0));
+// output map of a 3x3 convolution mode (an unknown mode is declined by the launch switch of skg_conv3x3_f16)
+static void conv_out_size(int mode, int IH, int IW, int* OH, int* OW) {
   const int up = (mode == SKG_CONV_UP2 || mode == SKG_CONV_S2T), dn = (mode == SKG_CONV_S2 || mode == SKG_CONV_S2A);
-  const int OH = up ? IH * 2 : dn ? IH / 2 : IH, OW = up ? IW * 2 : dn ? IW / 2 : IW;
-  SKG_REQUIRE(rows > 0 && OH > 0 && OW > 0 && gn_args_ok(gn_partial, rows * OH * OW, Cout, OH * OW, groups, ldy, flags));
-  return conv_impl(X, ldx, Wp, Y, ldy, rows, IH, IW, Cin, Cout, mode, bias, residual, ldr, alpha, flags, gn_partial, groups,
-                   stream, Y_lo, residual_lo);
+  *OH = up ? IH * 2 : dn ? IH / 2 : IH;
+  *OW = up ? IW * 2 : dn ? IW / 2 : IW;
 }
 
-extern "C" int skg_conv3x3_f16(const void* X, int ldx, const void* Wp, void* Y, int ldy, int rows,
-                               int IH, int IW, int Cin, int Cout, int mode, const void* bias,
-                               const void* residual, int ldr, float alpha, unsigned flags,
-                               void* stream) {
-  return conv_impl(X, ldx, Wp, Y, ldy, rows, IH, IW, Cin, Cout, mode, bias, residual, ldr, alpha, flags, nullptr, 0, stream);
-}
-
-static int conv_impl(const void* X, int ldx, const void* Wp, void* Y, int ldy, int rows, int IH, int IW, int Cin,
-                     int Cout, int mode, const void* bias, const void* residual, int ldr, float alpha, unsigned flags,
-                     float* gn_partial, int groups, void* stream, void* c_lo, const void* res_lo) {
+extern "C" int skg_conv3x3_f16(const void* X, int ldx, const void* Wp, void* Y, void* Y_lo, int ldy, int rows, int IH, int IW,
+                               int Cin, int Cout, int mode, const void* bias, const void* residual, const void* residual_lo,
+                               int ldr, float alpha, unsigned flags, float* gn_partial, int groups, void* stream) {
+  int OH, OW;
+  conv_out_size(mode, IH, IW, &OH, &OW);
+  SKG_REQUIRE(!(Y_lo || residual_lo) || pair_args_ok(Y, Y_lo, ldy, residual, residual_lo, ldr, Cin, flags));
+  SKG_REQUIRE(!gn_partial || (rows > 0 && OH > 0 && OW > 0 && skg_aligned(Y, 16) &&
+                              gn_args_ok(gn_partial, rows * OH * OW, Cout, OH * OW, groups, ldy, flags)));
   SKG_REQUIRE(X && Wp && Y && rows > 0 && IH > 0 && IW > 0);
   SKG_REQUIRE(Cin % 32 == 0 && Cout % 8 == 0 && ldx % 8 == 0 && ldx >= Cin && ldy % 4 == 0 && ldy >= Cout);
   SKG_REQUIRE(skg_aligned(X, 16) && skg_aligned(Wp, 16) && skg_aligned(Y, 8));
@@ -646,29 +572,21 @@ static int conv_impl(const void* X, int ldx, const void* Wp, void* Y, int ldy, i
   p.bias = (const half_t*)bias; p.res = (const half_t*)residual; p.ldr = ldr;
   p.N = Cout; p.K = 9 * Cin; p.alpha = alpha; p.flags = flags;
   p.IH = IH; p.IW = IW; p.Cin = Cin;
-  p.gn_partial = gn_partial; p.gn_groups = groups;
-  p.c_lo = (half_t*)c_lo; p.res_lo = (const half_t*)res_lo;
+  p.OH = OH; p.OW = OW; p.M = rows * OH * OW; p.gn_hw = OH * OW;
+  p.gn_partial = gn_partial; p.gn_groups = gn_partial ? groups : 0;
+  p.c_lo = (half_t*)Y_lo; p.res_lo = (const half_t*)residual_lo;
   hipStream_t st = (hipStream_t)stream;
   ws_attach(p, st);
   switch (mode) {
-    case SKG_CONV_S1:
-      p.OH = IH; p.OW = IW; p.M = rows * p.OH * p.OW; p.gn_hw = p.OH * p.OW;
-      return launch<MODE_S1>(p, st);
+    case SKG_CONV_S1: return launch<MODE_S1>(p, st);
     case SKG_CONV_S2:
       SKG_REQUIRE(IH % 2 == 0 && IW % 2 == 0);
-      p.OH = IH / 2; p.OW = IW / 2; p.M = rows * p.OH * p.OW; p.gn_hw = p.OH * p.OW;
       return launch<MODE_S2>(p, st);
     case SKG_CONV_S2A:
       SKG_REQUIRE(IH % 2 == 0 && IW % 2 == 0);
-      p.OH = IH / 2; p.OW = IW / 2; p.M = rows * p.OH * p.OW; p.gn_hw = p.OH * p.OW;
       return launch<MODE_S2A>(p, st);
-    case SKG_CONV_UP2:
-      p.OH = IH * 2; p.OW = IW * 2; p.M = rows * p.OH * p.OW; p.gn_hw = p.OH * p.OW;
-      return launch<MODE_UP2>(p, st);
-    case SKG_CONV_S2T:
-      p.OH = IH * 2; p.OW = IW * 2; p.M = rows * p.OH * p.OW; p.gn_hw = p.OH * p.OW;
-      return launch<MODE_S2T>(p, st);
-    default:
-      return SKG_E_UNSUPPORTED;
+    case SKG_CONV_UP2: return launch<MODE_UP2>(p, st);
+    case SKG_CONV_S2T: return launch<MODE_S2T>(p, st);
+    default: return SKG_E_UNSUPPORTED;
   }
 }

@@ -632,9 +632,13 @@ static inline bool tap_fits(int s, int h, int w) {
   return s > 0 && h % s == 0 && ((long long)s * w) % h == 0 && w % (int)((long long)s * w / h) == 0;
 }
 
-// the square entry points pass w = h (same kernels, same arithmetic); the _hw ones add the 8-multiple sides
-static int lgp_gather(const SkgLgpTap* taps, int ntaps, const void* Wextra, int ldw, const void* bias0, const float* noise,
-               float sigma, int samples, void* Z, int rows, int h, int w, int H0, void* stream) {
+// a square grid passes w = h; a rectangular one has 8-multiple sides (same kernels, same arithmetic)
+static inline bool grid_ok(int h, int w) { return h == w || (h % GT == 0 && w % GT == 0); }
+
+extern "C" int skg_lgp_layer0_gather(const SkgLgpTap* taps, int ntaps, const void* Wextra, int ldw, const void* bias0,
+                                     const float* noise, float sigma, int samples, void* Z, int rows, int h, int w, int H0,
+                                     void* stream) {
+  SKG_REQUIRE(grid_ok(h, w));
   SKG_REQUIRE(taps && ntaps > 0 && ntaps <= MAX_TAPS && bias0 && noise && Z && rows > 0 && h > 0 && w > 0);
   SKG_REQUIRE(H0 % 4 == 0 && skg_aligned(Z, 8) && samples > 0 && rows % samples == 0);
   SKG_REQUIRE(Wextra ? (ldw % 8 == 0 && skg_aligned(Wextra, 16)) : (h % GT == 0 && w % GT == 0 && H0 % GC == 0));
@@ -659,8 +663,9 @@ static int lgp_gather(const SkgLgpTap* taps, int ntaps, const void* Wextra, int 
   return SKG_OK;
 }
 
-static int lgp_scatter(const void* dZ, int lddz, void* dP, int rows, int h, int w, int s, int H0, void* stream) {
-  SKG_REQUIRE(dZ && dP && rows > 0 && h > 0 && w > 0 && tap_fits(s, h, w) && H0 % 8 == 0 && lddz % 8 == 0 &&
+extern "C" int skg_lgp_layer0_scatter(const void* dZ, int lddz, void* dP, int rows, int h, int w, int s, int H0,
+                                      void* stream) {
+  SKG_REQUIRE(grid_ok(h, w) && dZ && dP && rows > 0 && h > 0 && w > 0 && tap_fits(s, h, w) && H0 % 8 == 0 && lddz % 8 == 0 &&
               skg_aligned(dZ, 16) && skg_aligned(dP, 16));
   hipLaunchKernelGGL(lgp_scatter_kernel, dim3(rows * s * (s * w / h)), dim3(256), 0, (hipStream_t)stream,
                      (const half_t*)dZ, lddz, (half_t*)dP, rows, h, w, s, H0);
@@ -668,9 +673,9 @@ static int lgp_scatter(const void* dZ, int lddz, void* dP, int rows, int h, int 
   return SKG_OK;
 }
 
-static int lgp_mse_seed(const void* out, int ldo, const float* target, void* dOut, int ldd, float* loss, int samples, int h,
-                 int w, float loss_scale, void* stream) {
-  SKG_REQUIRE(out && target && dOut && samples > 0 && h > 0 && w > 0 && ldo >= 4 && ldd >= 4 && ldo % 4 == 0 &&
+extern "C" int skg_lgp_mse_seed(const void* out, int ldo, const float* target, void* dOut, int ldd, float* loss,
+                                int samples, int h, int w, float loss_scale, void* stream) {
+  SKG_REQUIRE(grid_ok(h, w) && out && target && dOut && samples > 0 && h > 0 && w > 0 && ldo >= 4 && ldd >= 4 && ldo % 4 == 0 &&
               ldd % 4 == 0);
   SKG_REQUIRE(skg_aligned(out, 8) && skg_aligned(dOut, 8));
   if (hipMemsetAsync(dOut, 0, (size_t)2 * samples * h * w * ldd * sizeof(half_t), (hipStream_t)stream) != hipSuccess)
@@ -681,37 +686,13 @@ static int lgp_mse_seed(const void* out, int ldo, const float* target, void* dOu
   return SKG_OK;
 }
 
-static int lgp_extra_features(const float* noise, float sigma, int samples, int rows, int h, int w, void* E, int ld,
-                       void* stream) {
-  SKG_REQUIRE(noise && E && samples > 0 && rows > 0 && rows % samples == 0 && h > 0 && w > 0 && ld >= NEXTRA);
+extern "C" int skg_lgp_extra_features(const float* noise, float sigma, int samples, int rows, int h, int w, void* E,
+                                      int ld, void* stream) {
+  SKG_REQUIRE(grid_ok(h, w) && noise && E && samples > 0 && rows > 0 && rows % samples == 0 && h > 0 && w > 0 && ld >= NEXTRA);
   hipLaunchKernelGGL(lgp_extra_kernel, dim3(ew_grid((size_t)rows * h * w * ld)), dim3(256), 0, (hipStream_t)stream,
                      noise, sigma, samples, rows, h * w, (half_t*)E, ld);
   SKG_CHECK_LAUNCH("skg_lgp_extra_features");
   return SKG_OK;
-}
-
-extern "C" int skg_lgp_layer0_gather(const SkgLgpTap* taps, int ntaps, const void* Wextra, int ldw,
-                                     const void* bias0, const float* noise, float sigma, int samples, void* Z,
-                                     int rows, int h, int H0, void* stream) {
-  return lgp_gather(taps, ntaps, Wextra, ldw, bias0, noise, sigma, samples, Z, rows, h, h, H0, stream);
-}
-
-extern "C" int skg_lgp_layer0_gather_hw(const SkgLgpTap* taps, int ntaps, const void* Wextra, int ldw,
-                                        const void* bias0, const float* noise, float sigma, int samples, void* Z,
-                                        int rows, int h, int w, int H0, void* stream) {
-  SKG_REQUIRE(h > 0 && w > 0 && h % GT == 0 && w % GT == 0);
-  return lgp_gather(taps, ntaps, Wextra, ldw, bias0, noise, sigma, samples, Z, rows, h, w, H0, stream);
-}
-
-extern "C" int skg_lgp_layer0_scatter(const void* dZ, int lddz, void* dP, int rows, int h, int s, int H0,
-                                      void* stream) {
-  return lgp_scatter(dZ, lddz, dP, rows, h, h, s, H0, stream);
-}
-
-extern "C" int skg_lgp_layer0_scatter_hw(const void* dZ, int lddz, void* dP, int rows, int h, int w, int s, int H0,
-                                         void* stream) {
-  SKG_REQUIRE(h > 0 && w > 0 && h % GT == 0 && w % GT == 0);
-  return lgp_scatter(dZ, lddz, dP, rows, h, w, s, H0, stream);
 }
 
 extern "C" size_t skg_bn_scratch_floats(int samples, int C) {
@@ -778,17 +759,6 @@ extern "C" int skg_bn_relu_bwd(const void* X, int ldx, const void* dY, int lddy,
   return SKG_OK;
 }
 
-extern "C" int skg_lgp_mse_seed(const void* out, int ldo, const float* target, void* dOut, int ldd, float* loss,
-                                int samples, int h, float loss_scale, void* stream) {
-  return lgp_mse_seed(out, ldo, target, dOut, ldd, loss, samples, h, h, loss_scale, stream);
-}
-
-extern "C" int skg_lgp_mse_seed_hw(const void* out, int ldo, const float* target, void* dOut, int ldd, float* loss,
-                                   int samples, int h, int w, float loss_scale, void* stream) {
-  SKG_REQUIRE(h > 0 && w > 0 && h % GT == 0 && w % GT == 0);
-  return lgp_mse_seed(out, ldo, target, dOut, ldd, loss, samples, h, w, loss_scale, stream);
-}
-
 // ---- training entry points ----------------------------------------------------------------------------------------
 extern "C" size_t skg_colsum_scratch_floats(int C) { return (size_t)CS_CHUNKS * C; }
 
@@ -814,17 +784,6 @@ extern "C" int skg_bn_param_grads(const void* X, int ldx, const void* dY, int ld
   hipLaunchKernelGGL(bn_param_grads_kernel, dim3(skg_cdiv(C, 128)), dim3(128), 0, st, scratch, C, scale, dgamma, dbeta);
   SKG_CHECK_LAUNCH("skg_bn_param_grads");
   return SKG_OK;
-}
-
-extern "C" int skg_lgp_extra_features(const float* noise, float sigma, int samples, int rows, int h, void* E, int ld,
-                                      void* stream) {
-  return lgp_extra_features(noise, sigma, samples, rows, h, h, E, ld, stream);
-}
-
-extern "C" int skg_lgp_extra_features_hw(const float* noise, float sigma, int samples, int rows, int h, int w, void* E,
-                                         int ld, void* stream) {
-  SKG_REQUIRE(h > 0 && w > 0 && h % GT == 0 && w % GT == 0);
-  return lgp_extra_features(noise, sigma, samples, rows, h, w, E, ld, stream);
 }
 
 extern "C" int skg_lgp_mse_train(const void* out, int ldo, const float* target, void* dOut, int ldd,

@@ -500,8 +500,9 @@ extern "C" int skg_groupnorm_stats(const void* X, int ldx, int rows, int HW, int
   return SKG_OK;
 }
 
-static int gn_apply_impl(const void* X, const void* Xl, int ldx, void* Y, int ldy, int rows, int HW, int C, int groups,
-                         const float* stats, const void* gamma, const void* beta, int silu, void* stream) {
+// X_lo != NULL here and in the other forwards below (accuracy mode): the input is the pair X + X_lo (one pitch)
+extern "C" int skg_groupnorm_apply(const void* X, const void* Xl, int ldx, void* Y, int ldy, int rows, int HW, int C, int groups,
+                                   const float* stats, const void* gamma, const void* beta, int silu, void* stream) {
   SKG_REQUIRE(X && Y && stats && gamma && beta && rows > 0 && HW > 0);
   SKG_REQUIRE(C % 8 == 0 && C % groups == 0 && ldx % 8 == 0 && ldy % 8 == 0 && ldx >= C && ldy >= C);
   SKG_REQUIRE((C / groups) >= 4 && C <= GN_MAX_C);      // an 8-channel piece spans at most two groups
@@ -514,19 +515,6 @@ static int gn_apply_impl(const void* X, const void* Xl, int ldx, void* Y, int ld
 #undef SKG_GN_APPLY
   SKG_CHECK_LAUNCH("skg_groupnorm_apply");
   return SKG_OK;
-}
-
-extern "C" int skg_groupnorm_apply(const void* X, int ldx, void* Y, int ldy, int rows, int HW, int C,
-                                   int groups, const float* stats, const void* gamma, const void* beta,
-                                   int silu, void* stream) {
-  return gn_apply_impl(X, nullptr, ldx, Y, ldy, rows, HW, C, groups, stats, gamma, beta, silu, stream);
-}
-
-extern "C" int skg_groupnorm_apply_hilo(const void* X, const void* X_lo, int ldx, void* Y, int ldy, int rows, int HW, int C,
-                                        int groups, const float* stats, const void* gamma, const void* beta, int silu,
-                                        void* stream) {
-  SKG_REQUIRE(X_lo);
-  return gn_apply_impl(X, X_lo, ldx, Y, ldy, rows, HW, C, groups, stats, gamma, beta, silu, stream);
 }
 
 // Small maps (16x16 / 8x8 levels): ONE workgroup per (row, group) keeps the group's whole slice in registers - X is
@@ -741,8 +729,12 @@ __global__ __launch_bounds__(256) void gn_bwd_small_kernel(
   }
 }
 
-static int gn_fwd_impl(const void* X, const void* Xl, int ldx, void* Y, void* Yl, int ldy, int rows, int HW, int C, int groups,
-                       float eps, const void* gamma, const void* beta, int silu, float* stats, float* partial, void* stream) {
+// GroupNorm(+SiLU) in one or two launches, statistics published; Y_lo != NULL (pair input only): the OUTPUT is a pair too (pitch
+// ldy) - the normalised activation in front of conv_out, whose rounding would reach eps 1 : 1
+extern "C" int skg_groupnorm_fwd(const void* X, const void* Xl, int ldx, void* Y, void* Yl, int ldy, int rows, int HW, int C,
+                                 int groups, float eps, const void* gamma, const void* beta, int silu, float* stats,
+                                 float* partial, void* stream) {
+  SKG_REQUIRE(Xl || !Yl);
   SKG_REQUIRE(X && Y && stats && partial && gamma && beta && rows > 0 && HW > 0 && groups > 0 && groups <= 64);
   SKG_REQUIRE(C % 8 == 0 && C % groups == 0 && (C / groups) % 2 == 0 && (C / groups) >= 4 && C <= GN_MAX_C);
   SKG_REQUIRE(ldx % 8 == 0 && ldy % 8 == 0 && ldx >= C && ldy >= C);
@@ -806,39 +798,26 @@ extern "C" int skg_groupnorm_wino_fwd(const void* X, int ldx, void* V, int rows,
   return SKG_OK;
 }
 
-extern "C" int skg_groupnorm_fwd(const void* X, int ldx, void* Y, int ldy, int rows, int HW, int C, int groups,
-                                 float eps, const void* gamma, const void* beta, int silu, float* stats,
-                                 float* partial, void* stream) {
-  return gn_fwd_impl(X, nullptr, ldx, Y, nullptr, ldy, rows, HW, C, groups, eps, gamma, beta, silu, stats, partial, stream);
-}
-
-// accuracy mode: GroupNorm(+SiLU) of the pair X + X_lo (one pitch) in one or two launches, statistics published; Y_lo != NULL:
-// the OUTPUT is a pair too (pitch ldy) - the normalised activation in front of conv_out, whose rounding would reach eps 1 : 1
-extern "C" int skg_groupnorm_fwd_hilo(const void* X, const void* X_lo, int ldx, void* Y, void* Y_lo, int ldy, int rows, int HW, int C,
-                                      int groups, float eps, const void* gamma, const void* beta, int silu, float* stats,
-                                      float* partial, void* stream) {
-  SKG_REQUIRE(X_lo);
-  return gn_fwd_impl(X, X_lo, ldx, Y, Y_lo, ldy, rows, HW, C, groups, eps, gamma, beta, silu, stats, partial, stream);
-}
-
-// the statistics pass alone, nch chunks per sample (the fallback behind skg_gemm_f16_gn / skg_conv3x3_f16_gn when the
-// producer's tile cannot write the partial sums itself)
+// the statistics pass alone, nch chunks per sample (the fallback behind skg_gemm_f16 / skg_conv3x3_f16 with gn_partial when
+// the producer's tile cannot write the partial sums itself)
 void skg_gn_partial_launch(const half_t* X, int ldx, int rows, int HW, int C, int groups, int nch, float* partial,
                            hipStream_t st) {
   hipLaunchKernelGGL((gn_partial_kernel<0>), dim3(nch, rows), dim3(256), 0, st, X, ldx, (const half_t*)nullptr, 0, HW,
                      C, groups, (const float*)nullptr, (const half_t*)nullptr, (const half_t*)nullptr, 0, partial);
 }
 
-// GroupNorm forward from partial sums somebody else produced (a producer epilogue: skg_gemm_f16_gn, skg_conv3x3_f16_gn):
+// GroupNorm forward from partial sums somebody else produced (a producer epilogue: skg_gemm_f16, skg_conv3x3_f16 with gn_partial):
 // one launch - the apply kernel folds the nch chunk partials per (row, group) itself and publishes (mean, rstd).
 // partialB != NULL: GroupNorm of a concatenation [A (CA channels) | B (C - CA channels)] whose halves were written by two
 // producers that each left partial sums behind (groupsA / groupsB groups per chunk over their own channels).  The
 // concatenation's group width must be a multiple of both source group widths and CA a multiple of it (e.g. 320 + 320 or
 // 640 + 640 channels with 32 groups each way: two source groups per output group); otherwise SKG_E_UNSUPPORTED.
-static int gn_from_partial_impl(const void* X, const void* Xl, int ldx, void* Y, void* Yl, int ldy, int rows, int HW, int C, int CA,
-                                int groups, float eps, const void* gamma, const void* beta, int silu, float* stats,
-                                const float* partialA, int groupsA, const float* partialB, int groupsB, int nch,
-                                void* stream) {
+// partialB == NULL: one producer (CA, groupsB unused; on a pair groupsA == groups).
+extern "C" int skg_groupnorm_from_partial(const void* X, const void* Xl, int ldx, void* Y, void* Yl, int ldy, int rows, int HW, int C,
+                                          int CA, int groups, float eps, const void* gamma, const void* beta, int silu,
+                                          float* stats, const float* partialA, int groupsA, const float* partialB, int groupsB,
+                                          int nch, void* stream) {
+  SKG_REQUIRE((Xl || !Yl) && (!Xl || partialB || groupsA == groups));
   SKG_REQUIRE(X && Y && stats && partialA && gamma && beta && rows > 0 && HW > 0 && groups > 0 && groups <= 64);
   SKG_REQUIRE(nch > 0 && nch <= GN_MAX_CHUNKS);
   SKG_REQUIRE(C % 8 == 0 && C % groups == 0 && (C / groups) % 2 == 0 && (C / groups) >= 4 && C <= GN_MAX_C);
@@ -862,32 +841,6 @@ static int gn_from_partial_impl(const void* X, const void* Xl, int ldx, void* Y,
 #undef SKG_GN_FOLD
   SKG_CHECK_LAUNCH("skg_groupnorm_from_partial");
   return SKG_OK;
-}
-
-extern "C" int skg_groupnorm_from_partial(const void* X, int ldx, void* Y, int ldy, int rows, int HW, int C, int groups,
-                                          float eps, const void* gamma, const void* beta, int silu, float* stats,
-                                          const float* partial, int nch, void* stream) {
-  return gn_from_partial_impl(X, nullptr, ldx, Y, nullptr, ldy, rows, HW, C, 0, groups, eps, gamma, beta, silu, stats, partial, groups,
-                              nullptr, 0, nch, stream);
-}
-
-extern "C" int skg_groupnorm_from_partial2(const void* X, int ldx, void* Y, int ldy, int rows, int HW, int C, int CA,
-                                           int groups, float eps, const void* gamma, const void* beta, int silu,
-                                           float* stats, const float* partialA, int groupsA, const float* partialB,
-                                           int groupsB, int nch, void* stream) {
-  SKG_REQUIRE(partialB);
-  return gn_from_partial_impl(X, nullptr, ldx, Y, nullptr, ldy, rows, HW, C, CA, groups, eps, gamma, beta, silu, stats, partialA, groupsA,
-                              partialB, groupsB, nch, stream);
-}
-
-// accuracy mode: the same for a pair X + X_lo (partialB == NULL: one producer; else the concatenation form)
-extern "C" int skg_groupnorm_from_partial_hilo(const void* X, const void* X_lo, int ldx, void* Y, void* Y_lo, int ldy, int rows, int HW,
-                                               int C, int CA, int groups, float eps, const void* gamma, const void* beta,
-                                               int silu, float* stats, const float* partialA, int groupsA,
-                                               const float* partialB, int groupsB, int nch, void* stream) {
-  SKG_REQUIRE(X_lo && (partialB || groupsA == groups));
-  return gn_from_partial_impl(X, X_lo, ldx, Y, Y_lo, ldy, rows, HW, C, CA, groups, eps, gamma, beta, silu, stats, partialA, groupsA,
-                              partialB, groupsB, nch, stream);
 }
 
 extern "C" int skg_groupnorm_bwd(const void* X, int ldx, const void* dY, int lddy, void* dX, int lddx,
@@ -927,8 +880,8 @@ extern "C" int skg_groupnorm_bwd(const void* X, int ldx, const void* dY, int ldd
   return SKG_OK;
 }
 
-static int ln_fwd_impl(const void* X, const void* Xl, int ldx, void* Y, int ldy, int M, int C, const void* gamma,
-                       const void* beta, float eps, float* stats, void* stream) {
+extern "C" int skg_layernorm_fwd(const void* X, const void* Xl, int ldx, void* Y, int ldy, int M, int C, const void* gamma,
+                                 const void* beta, float eps, float* stats, void* stream) {
   SKG_REQUIRE(X && Y && gamma && beta && M > 0 && C % 8 == 0 && C <= LN_MAXP * 64 * 8);
   SKG_REQUIRE(ldx % 8 == 0 && ldy % 8 == 0 && skg_aligned(X, 16) && skg_aligned(Y, 16) && skg_aligned(Xl, 16) &&
               skg_aligned(gamma, 16) && skg_aligned(beta, 16));
@@ -949,17 +902,6 @@ static int ln_fwd_impl(const void* X, const void* Xl, int ldx, void* Y, int ldy,
 #undef SKG_LN
   SKG_CHECK_LAUNCH("skg_layernorm_fwd");
   return SKG_OK;
-}
-
-extern "C" int skg_layernorm_fwd(const void* X, int ldx, void* Y, int ldy, int M, int C, const void* gamma,
-                                 const void* beta, float eps, float* stats, void* stream) {
-  return ln_fwd_impl(X, nullptr, ldx, Y, ldy, M, C, gamma, beta, eps, stats, stream);
-}
-
-extern "C" int skg_layernorm_fwd_hilo(const void* X, const void* X_lo, int ldx, void* Y, int ldy, int M, int C,
-                                      const void* gamma, const void* beta, float eps, float* stats, void* stream) {
-  SKG_REQUIRE(X_lo);
-  return ln_fwd_impl(X, X_lo, ldx, Y, ldy, M, C, gamma, beta, eps, stats, stream);
 }
 
 extern "C" int skg_layernorm_bwd(const void* X, int ldx, const void* dY, int lddy, void* dX, int lddx,

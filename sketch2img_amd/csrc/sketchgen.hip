@@ -228,7 +228,7 @@ extern "C" int skg_instnorm_act_f16(const void* X, int ldx, int rows, int HW, in
 extern "C" int skg_convt4x4s2_f16(const void* X, int ldx, const void* Wpp, void* Y, int ldy, int rows, int IH, int IW, int Cin,
                                   int Cout, const void* bias, int epilogue, void* stream) {
   SKG_REQUIRE(epilogue == SKG_CONVT_EPI_NONE || epilogue == SKG_CONVT_EPI_TANH);
-  const int rc = skg_conv3x3_up2_f16(X, ldx, Wpp, Y, ldy, rows, IH, IW, Cin, Cout, bias, stream);
+  const int rc = skg_conv3x3_up2_f16(X, ldx, Wpp, Y, nullptr, ldy, rows, IH, IW, Cin, Cout, 0, bias, stream);
   if (rc != SKG_OK || epilogue == SKG_CONVT_EPI_NONE) return rc;
   const size_t M = (size_t)rows * 4 * IH * IW, n = M * (Cout / 8);
   hipLaunchKernelGGL(tanh_rows_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (half_t*)Y, ldy, M, Cout / 8);

@@ -36,7 +36,7 @@ struct XAParams {
   int heads, nkv;
   float sc;                // dh^-0.5 * log2(e)
   unsigned wbytes, kvbytes;
-  // stashing launch (skg_xattn_block_f16_keep): rows >= keep_from (whole images) also store what the backward of the four
+  // stashing launch (skg_xattn_block_f16 with Q): rows >= keep_from (whole images) also store what the backward of the four
   // replaced launches reads - norm2's (mean, rstd), the to_q output, the attention output and the log-sum-exp, indexed from keep_from
   float* kstats; half_t* kq; half_t* ko; int ldk; float* klse; int keep_from;
 };
@@ -69,7 +69,7 @@ __device__ __forceinline__ float4_t mfma32_fresh(half8_t a, half8_t b, float4_t 
   return d;
 }
 
-// HILO (accuracy mode, skg_xattn_block_f16_hilo): LayerNorm reads hi + lo, the residual sum is formed in fp32 on the pair and stored
+// HILO (accuracy mode, skg_xattn_block_f16 with X_lo): LayerNorm reads hi + lo, the residual sum is formed in fp32 on the pair and stored
 // as hi = fp16(v), lo = fp16(v - hi); everything between is the same kernel
 // DH = 64 (round 5: the 5 x 64 heads of SD2.1's C = 320 blocks): no K = 16 tails on the head width - Q^T is 4 tiles, S^T and the
 // out-projection take two K = 32 steps over d, O^T is 4 tiles; only the key axis (80 = 2 x 32 + 16) keeps its K = 16 step.  The LDS image is
@@ -425,10 +425,15 @@ __global__ __launch_bounds__(512, 1) void xattn_block_kernel(const XAParams p) {
 
 }  // namespace
 
-static int xattn_block_impl(const void* X, const void* Xl, int ldx, void* Y, void* Yl, int ldy, int M, int HW, int C, int heads,
-                            int Nkv, const void* gamma, const void* beta, float eps, const void* Wpack, const void* KVpack,
-                            const void* bias_out, float scale, void* stream, float* kstats = nullptr, void* kq = nullptr,
-                            void* ko = nullptr, int ldk = 0, float* klse = nullptr, int keep_from = 0) {
+// One entry point (include/skg.h): X_lo / Y_lo != NULL: pair input and output (accuracy mode); Q != NULL: the stashing launch of a
+// guided step - rows >= keep_from (a multiple of HW: whole images, the cond half) also store norm2's statistics [M - keep_from][2],
+// the to_q output Q and the attention output O ([M - keep_from][ldk], head h in columns 40 h .. 40 h + 39) and lse
+// [(M - keep_from) / HW][heads][HW] (natural log, skg_attn_fwd's convention) - what skg_attn_bwd_dq / skg_layernorm_bwd of the four
+// replaced launches read
+extern "C" int skg_xattn_block_f16(const void* X, const void* Xl, int ldx, void* Y, void* Yl, int ldy, int M, int HW, int C, int heads,
+                                   int Nkv, const void* gamma, const void* beta, float eps, const void* Wpack, const void* KVpack,
+                                   const void* bias_out, float scale, float* kstats, void* kq, void* ko, int ldk, float* klse,
+                                   int keep_from, void* stream) {
   SKG_REQUIRE(X && Y && gamma && beta && Wpack && KVpack && bias_out && M > 0 && (Xl != nullptr) == (Yl != nullptr));
   SKG_REQUIRE(!kq || (kstats && ko && klse && ldk % 4 == 0 && ldk >= C && keep_from >= 0 && keep_from < M && HW > 0 &&
                       keep_from % HW == 0 && skg_aligned(kq, 8) && skg_aligned(ko, 8)));
@@ -458,41 +463,4 @@ static int xattn_block_impl(const void* X, const void* Xl, int ldx, void* Y, voi
   else hipLaunchKernelGGL(xattn_block_kernel<false>, dim3(M / 128), dim3(512), 0, (hipStream_t)stream, p);
   SKG_CHECK_LAUNCH("skg_xattn_block_f16");
   return SKG_OK;
-}
-
-extern "C" int skg_xattn_block_f16(const void* X, int ldx, void* Y, int ldy, int M, int HW, int C, int heads, int Nkv,
-                                   const void* gamma, const void* beta, float eps, const void* Wpack, const void* KVpack,
-                                   const void* bias_out, float scale, void* stream) {
-  return xattn_block_impl(X, nullptr, ldx, Y, nullptr, ldy, M, HW, C, heads, Nkv, gamma, beta, eps, Wpack, KVpack, bias_out, scale, stream);
-}
-
-// accuracy mode: pair input X + X_lo (pitch ldx), pair output Y + Y_lo (pitch ldy)
-extern "C" int skg_xattn_block_f16_hilo(const void* X, const void* X_lo, int ldx, void* Y, void* Y_lo, int ldy, int M, int HW, int C,
-                                        int heads, int Nkv, const void* gamma, const void* beta, float eps, const void* Wpack,
-                                        const void* KVpack, const void* bias_out, float scale, void* stream) {
-  SKG_REQUIRE(X_lo && Y_lo);
-  return xattn_block_impl(X, X_lo, ldx, Y, Y_lo, ldy, M, HW, C, heads, Nkv, gamma, beta, eps, Wpack, KVpack, bias_out, scale, stream);
-}
-
-// the stashing launch of a guided step: rows >= keep_from (a multiple of HW: whole images, the cond half) also store norm2's
-// statistics [M - keep_from][2], the to_q output Q and the attention output O ([M - keep_from][ldk], head h in columns
-// 40 h .. 40 h + 39) and lse [(M - keep_from) / HW][heads][HW] (natural log, skg_attn_fwd's convention) - what
-// skg_attn_bwd_dq / skg_layernorm_bwd of the four replaced launches read
-extern "C" int skg_xattn_block_f16_keep(const void* X, int ldx, void* Y, int ldy, int M, int HW, int C, int heads, int Nkv,
-                                        const void* gamma, const void* beta, float eps, const void* Wpack, const void* KVpack,
-                                        const void* bias_out, float scale, float* stats, void* Q, void* O, int ldk, float* lse,
-                                        int keep_from, void* stream) {
-  SKG_REQUIRE(stats && Q && O && lse);
-  return xattn_block_impl(X, nullptr, ldx, Y, nullptr, ldy, M, HW, C, heads, Nkv, gamma, beta, eps, Wpack, KVpack, bias_out, scale, stream,
-                          stats, Q, O, ldk, lse, keep_from);
-}
-
-// ... on pairs (accuracy mode, round 5): skg_xattn_block_f16_hilo that also stashes what the backward of the cond rows reads
-extern "C" int skg_xattn_block_f16_hilo_keep(const void* X, const void* X_lo, int ldx, void* Y, void* Y_lo, int ldy, int M, int HW, int C,
-                                             int heads, int Nkv, const void* gamma, const void* beta, float eps, const void* Wpack,
-                                             const void* KVpack, const void* bias_out, float scale, float* stats, void* Q, void* O, int ldk,
-                                             float* lse, int keep_from, void* stream) {
-  SKG_REQUIRE(X_lo && Y_lo && stats && Q && O && lse);
-  return xattn_block_impl(X, X_lo, ldx, Y, Y_lo, ldy, M, HW, C, heads, Nkv, gamma, beta, eps, Wpack, KVpack, bias_out, scale, stream,
-                          stats, Q, O, ldk, lse, keep_from);
 }

@@ -16,6 +16,7 @@ from ._lib import SkgError, SkgTap, check, lib
 
 EPI_RELU, EPI_OUT_F32, EPI_GEGLU = 1, 2, 4
 CONV_S1, CONV_S2, CONV_UP2, CONV_S2T, CONV_S2A = 0, 1, 2, 3, 4
+ATTN_CAUSAL, ATTN_ROWV = 1, 2
 
 
 _workspace = {}
@@ -120,7 +121,7 @@ def _f16(*ts):
 
 class GNPartial:
     """Per (sample, 128-row chunk, group) sum / sum of squares of a producer's output - what `groupnorm(partial=)` folds
-    instead of reading the tensor a second time (skg_gemm_f16_gn / skg_conv3x3_f16_gn)."""
+    instead of reading the tensor a second time (skg_gemm_f16 / skg_conv3x3_f16 with gn_partial)."""
     __slots__ = ("buf", "nch", "rows", "groups")
 
     def __init__(self, rows: int, HW: int, groups: int, dev):
@@ -173,33 +174,17 @@ def gemm(A: torch.Tensor, B: torch.Tensor, out: Optional[torch.Tensor] = None, *
         assert out is not None and not (out_f32 or geglu)
         assert out_lo is None or _ld(out_lo) == _ld(out)
         assert residual_lo is None or residual is None or _ld(residual_lo) == _ld(residual)
-        r_any = residual if residual is not None else residual_lo
-        if gn_stats is not None:      # the partial sums of the output's hi part come with it
-            HW, groups = gn_stats
-            part = GNPartial(M // HW, HW, groups, A.device)
-            check(lib.skg_gemm_f16_hilo_gn(_p(A), _ld(A), _p(B), _ld(B), _p(out), _p(out_lo), _ld(out), M, N, K, _p(bias),
-                                           _p(residual), _p(residual_lo), _ld(r_any) if r_any is not None else 0, alpha,
-                                           EPI_RELU if relu else 0, _p(part.buf), HW, groups, _stream()), "skg_gemm_f16_hilo_gn")
-            return out, part
-        check(lib.skg_gemm_f16_hilo(_p(A), _ld(A), _p(B), _ld(B), _p(out), _p(out_lo), _ld(out), M, N, K, _p(bias),
-                                    _p(residual), _p(residual_lo), _ld(r_any) if r_any is not None else 0, alpha,
-                                    EPI_RELU if relu else 0, _stream()), "skg_gemm_f16_hilo")
-        return out
-    if out is None:
+    elif out is None:
         out = torch.empty(M, N // 2 if geglu else N, device=A.device,
                           dtype=torch.float32 if out_f32 else torch.float16)
+    r_any = residual if residual is not None else residual_lo
     flags = (EPI_RELU if relu else 0) | (EPI_OUT_F32 if out_f32 else 0) | (EPI_GEGLU if geglu else 0)
-    if gn_stats is not None:
-        HW, groups = gn_stats
-        part = GNPartial(M // HW, HW, groups, A.device)
-        check(lib.skg_gemm_f16_gn(_p(A), _ld(A), _p(B), _ld(B), _p(out), _ld(out), M, N, K, _p(bias),
-                                  _p(residual), _ld(residual) if residual is not None else 0, alpha, flags,
-                                  _p(part.buf), HW, groups, _stream()), "skg_gemm_f16_gn")
-        return out, part
-    check(lib.skg_gemm_f16(_p(A), _ld(A), _p(B), _ld(B), _p(out), _ld(out), M, N, K, _p(bias),
-                           _p(residual), _ld(residual) if residual is not None else 0, alpha, flags,
-                           _stream()), "skg_gemm_f16")
-    return out
+    HW, groups = gn_stats or (0, 0)      # the partial sums of the output (a pair's hi part) come with it
+    part = GNPartial(M // HW, HW, groups, A.device) if gn_stats is not None else None
+    check(lib.skg_gemm_f16(_p(A), _ld(A), _p(B), _ld(B), _p(out), _p(out_lo), _ld(out), M, N, K, _p(bias),
+                           _p(residual), _p(residual_lo), _ld(r_any) if r_any is not None else 0, alpha, flags,
+                           _p(part.buf) if part is not None else None, HW, groups, _stream()), "skg_gemm_f16")
+    return out if part is None else (out, part)
 
 
 def gemm_geglu_keep(A: torch.Tensor, B: torch.Tensor, bias: Optional[torch.Tensor] = None, out=None, pre=None):
@@ -216,33 +201,39 @@ def gemm_geglu_keep(A: torch.Tensor, B: torch.Tensor, bias: Optional[torch.Tenso
     return out, pre
 
 
+def _ff_block(X, gamma, beta, eps, pack, bias1_pack, bias2, bias_proj, R, out, want_stats, keep_from, gn):
+    """The skg_ff_block_f16 launch behind ff_block / ff_block_proj -> (out, stats | None, pre | None, GNPartial | None)."""
+    pair = isinstance(X, Pair)
+    Xh, Xl = (X.hi, X.lo) if pair else (X, None)
+    Rh, Rl = (R.hi, R.lo) if pair and R is not None else (R, None)
+    _f16(Xh, Xl, gamma, beta, pack, bias2, bias_proj, Rh, Rl)
+    M, C = Xh.shape
+    assert pack.is_contiguous() and pack.dim() == 3 and pack.shape[1:] == (60, 512) and bias1_pack.dtype == torch.float32
+    F = (pack.shape[0] - (0 if bias_proj is None else 5)) * 32
+    assert bias_proj is None or bias1_pack.shape[0] * 32 == F
+    dev = Xh.device
+    if out is None:
+        out = Pair.empty(M, C, dev) if pair else torch.empty(M, C, device=dev, dtype=torch.float16)
+    Yh, Yl = (out.hi, out.lo) if pair else (out, None)
+    assert not pair or (_ld(Xl) == _ld(Xh) and _ld(Yl) == _ld(Yh) and (Rl is None or _ld(Rl) == _ld(Rh)))
+    stats = torch.empty(M, 2, device=dev, dtype=torch.float32) if want_stats else None
+    pre = None if keep_from is None else torch.empty(M - keep_from, 2 * F, device=dev, dtype=torch.float16)
+    HW, groups = gn or (0, 0)
+    part = GNPartial(M // HW, HW, groups, dev) if gn is not None else None
+    check(lib.skg_ff_block_f16(_p(Xh), _p(Xl), _ld(Xh), _p(Yh), _p(Yl), _ld(Yh), M, C, F, _p(gamma), _p(beta), eps, _p(pack),
+                               _p(bias1_pack), _p(bias2), _p(bias_proj), _p(Rh), _p(Rl), _ld(Rh) if Rh is not None else 0, _p(stats),
+                               _p(pre), _ld(pre) if pre is not None else 0, keep_from or 0,
+                               _p(part.buf) if part is not None else None, HW, groups, _stream()), "skg_ff_block_f16")
+    return out, stats, pre, part
+
+
 def ff_block(X, gamma, beta, eps: float, pack: torch.Tensor, bias1_pack: torch.Tensor, bias2: torch.Tensor,
              out=None, want_stats: bool = False, keep_from: Optional[int] = None):
     """Fused feed-forward sub-block at C = 320: out = X + b2 + W2 . geglu(W1 . LayerNorm(X) + b1) in one launch
     (skg_ff_block_f16; pack / bias1_pack from packs.pack_ff_block).  out may be X.
     keep_from=m0: rows >= m0 also store the FF1 output (interleaved pack, what geglu_bwd reads) -> returned last.
-    X (and out) may be ops.Pair objects (accuracy mode: skg_ff_block_f16_hilo)."""
-    pair = isinstance(X, Pair)
-    Xh = X.hi if pair else X
-    _f16(Xh, gamma, beta, pack, bias2)
-    M, C = Xh.shape
-    assert pack.is_contiguous() and pack.dim() == 3 and pack.shape[1:] == (60, 512) and bias1_pack.dtype == torch.float32
-    F = pack.shape[0] * 32
-    if out is None:
-        out = Pair.empty(M, C, Xh.device) if pair else torch.empty(M, C, device=Xh.device, dtype=torch.float16)
-    stats = torch.empty(M, 2, device=Xh.device, dtype=torch.float32) if want_stats else None
-    pre = None if keep_from is None else torch.empty(M - keep_from, 2 * F, device=Xh.device, dtype=torch.float16)
-    if pair:
-        assert _ld(X.lo) == _ld(X.hi) and _ld(out.lo) == _ld(out.hi)
-        check(lib.skg_ff_block_f16_hilo(_p(X.hi), _p(X.lo), _ld(X.hi), _p(out.hi), _p(out.lo), _ld(out.hi), M, C, F, _p(gamma), _p(beta),
-                                        eps, _p(pack), _p(bias1_pack), _p(bias2), _p(stats), _p(pre), _ld(pre) if pre is not None else 0,
-                                        keep_from or 0, _stream()), "skg_ff_block_f16_hilo")
-    elif keep_from is None:
-        check(lib.skg_ff_block_f16(_p(X), _ld(X), _p(out), _ld(out), M, C, F, _p(gamma), _p(beta), eps, _p(pack), _p(bias1_pack),
-                                   _p(bias2), _p(stats), _stream()), "skg_ff_block_f16")
-    else:
-        check(lib.skg_ff_block_f16_keep(_p(X), _ld(X), _p(out), _ld(out), M, C, F, _p(gamma), _p(beta), eps, _p(pack), _p(bias1_pack),
-                                        _p(bias2), _p(stats), _p(pre), _ld(pre), keep_from, _stream()), "skg_ff_block_f16_keep")
+    X (and out) may be ops.Pair objects (accuracy mode)."""
+    out, stats, pre, _ = _ff_block(X, gamma, beta, eps, pack, bias1_pack, bias2, None, None, out, want_stats, keep_from, None)
     if keep_from is None:
         return (out, stats) if want_stats else out
     return (out, stats, pre) if want_stats else (out, pre)
@@ -250,48 +241,19 @@ def ff_block(X, gamma, beta, eps: float, pack: torch.Tensor, bias1_pack: torch.T
 
 def ff_block_proj(X, gamma, beta, eps: float, pack: torch.Tensor, bias1_pack: torch.Tensor, bias2: torch.Tensor, bias_proj: torch.Tensor,
                   R: torch.Tensor, out=None, want_stats: bool = False, keep_from: Optional[int] = None, gn: Optional[Tuple[int, int]] = None):
-    """ff_block followed by Transformer2DModel.proj_out and the outer residual in the same launch (skg_ff_block_proj_f16):
+    """ff_block followed by Transformer2DModel.proj_out and the outer residual in the same launch (skg_ff_block_f16 with bias_proj):
     out = R + bias_proj + W_proj . fp16(X + FF(LayerNorm(X))); pack = packs.pack_ff_block(..., w_proj) (five chunks more).
     gn = (HW, groups): also the GroupNorm partial sums of out.  Returns (out, stats | None, pre | None, GNPartial | None);
-    out must not be X (it may be R)."""
-    pair = isinstance(X, Pair)
-    if pair:      # accuracy mode: X, R and out are pairs (skg_ff_block_proj_f16_hilo)
-        _f16(X.hi, X.lo, gamma, beta, pack, bias2, bias_proj, R.hi, R.lo)
-        M, C = X.hi.shape
-        F = (pack.shape[0] - 5) * 32
-        assert pack.is_contiguous() and pack.shape[1:] == (60, 512) and bias1_pack.shape[0] * 32 == F and out is not None
-        assert _ld(X.lo) == _ld(X.hi) and _ld(out.lo) == _ld(out.hi) and _ld(R.lo) == _ld(R.hi)
-        dev = X.hi.device
-        stats = torch.empty(M, 2, device=dev, dtype=torch.float32) if want_stats else None
-        pre = None if keep_from is None else torch.empty(M - keep_from, 2 * F, device=dev, dtype=torch.float16)
-        part = GNPartial(M // gn[0], gn[0], gn[1], dev) if gn is not None else None
-        check(lib.skg_ff_block_proj_f16_hilo(_p(X.hi), _p(X.lo), _ld(X.hi), _p(out.hi), _p(out.lo), _ld(out.hi), M, C, F, _p(gamma), _p(beta), eps,
-                                             _p(pack), _p(bias1_pack), _p(bias2), _p(bias_proj), _p(R.hi), _p(R.lo), _ld(R.hi), _p(stats), _p(pre),
-                                             _ld(pre) if pre is not None else 0, keep_from or 0, _p(part.buf) if part is not None else None,
-                                             gn[0] if gn else 0, gn[1] if gn else 0, _stream()), "skg_ff_block_proj_f16_hilo")
-        return out, stats, pre, part
-    _f16(X, gamma, beta, pack, bias2, bias_proj, R)
-    M, C = X.shape
-    assert pack.is_contiguous() and pack.dim() == 3 and pack.shape[1:] == (60, 512) and bias1_pack.dtype == torch.float32
-    F = (pack.shape[0] - 5) * 32
-    assert bias1_pack.shape[0] * 32 == F
-    if out is None:
-        out = torch.empty(M, C, device=X.device, dtype=torch.float16)
-    stats = torch.empty(M, 2, device=X.device, dtype=torch.float32) if want_stats else None
-    pre = None if keep_from is None else torch.empty(M - keep_from, 2 * F, device=X.device, dtype=torch.float16)
-    part = GNPartial(M // gn[0], gn[0], gn[1], X.device) if gn is not None else None
-    check(lib.skg_ff_block_proj_f16(_p(X), _ld(X), _p(out), _ld(out), M, C, F, _p(gamma), _p(beta), eps, _p(pack), _p(bias1_pack), _p(bias2),
-                                    _p(bias_proj), _p(R), _ld(R), _p(stats), _p(pre), _ld(pre) if pre is not None else 0, keep_from or 0,
-                                    _p(part.buf) if part is not None else None, gn[0] if gn else 0, gn[1] if gn else 0, _stream()),
-          "skg_ff_block_proj_f16")
-    return out, stats, pre, part
+    out must not be X (it may be R).  Accuracy mode: X, R and out are pairs."""
+    assert bias_proj is not None and R is not None and (out is not None or not isinstance(X, Pair))
+    return _ff_block(X, gamma, beta, eps, pack, bias1_pack, bias2, bias_proj, R, out, want_stats, keep_from, gn)
 
 
 def xattn_block(X, HW: int, heads: int, Nkv: int, gamma, beta, eps: float, wpack: torch.Tensor, kvpack: torch.Tensor,
                 bias_out: torch.Tensor, scale: float, out=None, keep_from: Optional[int] = None):
     """Fused cross-attention sub-block at C = 320, 8 heads: out = X + bo + Wo . Attention(Wq . LayerNorm(X), K, V) over the text
     keys of each row's image, in one launch (skg_xattn_block_f16; packs from packs.pack_xattn_weights / pack_xattn_kv).
-    X (and out) may be ops.Pair objects (accuracy mode: skg_xattn_block_f16_hilo)."""
+    X (and out) may be ops.Pair objects (accuracy mode)."""
     pair = isinstance(X, Pair)
     Xh = X.hi if pair else X
     _f16(Xh, gamma, beta, wpack, kvpack, bias_out)
@@ -300,37 +262,20 @@ def xattn_block(X, HW: int, heads: int, Nkv: int, gamma, beta, eps: float, wpack
     assert wpack.is_contiguous() and wpack.shape == (heads, wp, 512) and kvpack.is_contiguous() and kvpack.shape == (M // HW, heads, kp, 512)
     if out is None:
         out = Pair.empty(M, C, Xh.device) if pair else torch.empty(M, C, device=Xh.device, dtype=torch.float16)
-    if pair and keep_from is not None:      # accuracy mode, guided step: the stashing launch on pairs (skg_xattn_block_f16_hilo_keep)
-        assert _ld(X.lo) == _ld(X.hi) and _ld(out.lo) == _ld(out.hi)
+    Yh, Yl = (out.hi, out.lo) if pair else (out, None)
+    assert not pair or (_ld(X.lo) == _ld(Xh) and _ld(Yl) == _ld(Yh))
+    st = q = o = lse = None
+    if keep_from is not None:      # stashing launch: -> (out, stats, q, o, lse) of the rows >= keep_from
         Mk = M - keep_from
         dev = Xh.device
         st = torch.empty(Mk, 2, device=dev, dtype=torch.float32)
         q = torch.empty(Mk, C, device=dev, dtype=torch.float16)
         o = torch.empty(Mk, C, device=dev, dtype=torch.float16)
         lse = torch.empty(Mk // HW, heads, HW, device=dev, dtype=torch.float32)
-        check(lib.skg_xattn_block_f16_hilo_keep(_p(X.hi), _p(X.lo), _ld(X.hi), _p(out.hi), _p(out.lo), _ld(out.hi), M, HW, C, heads, Nkv,
-                                                _p(gamma), _p(beta), eps, _p(wpack), _p(kvpack), _p(bias_out), scale, _p(st), _p(q), _p(o), C,
-                                                _p(lse), keep_from, _stream()), "skg_xattn_block_f16_hilo_keep")
-        return out, st, q, o, lse
-    if pair:
-        assert _ld(X.lo) == _ld(X.hi) and _ld(out.lo) == _ld(out.hi)
-        check(lib.skg_xattn_block_f16_hilo(_p(X.hi), _p(X.lo), _ld(X.hi), _p(out.hi), _p(out.lo), _ld(out.hi), M, HW, C, heads, Nkv,
-                                           _p(gamma), _p(beta), eps, _p(wpack), _p(kvpack), _p(bias_out), scale, _stream()),
-              "skg_xattn_block_f16_hilo")
-        return out
-    if keep_from is not None:      # stashing launch: -> (out, stats, q, o, lse) of the rows >= keep_from (skg_xattn_block_f16_keep)
-        Mk = M - keep_from
-        st = torch.empty(Mk, 2, device=X.device, dtype=torch.float32)
-        q = torch.empty(Mk, C, device=X.device, dtype=torch.float16)
-        o = torch.empty(Mk, C, device=X.device, dtype=torch.float16)
-        lse = torch.empty(Mk // HW, heads, HW, device=X.device, dtype=torch.float32)
-        check(lib.skg_xattn_block_f16_keep(_p(X), _ld(X), _p(out), _ld(out), M, HW, C, heads, Nkv, _p(gamma), _p(beta), eps, _p(wpack),
-                                           _p(kvpack), _p(bias_out), scale, _p(st), _p(q), _p(o), C, _p(lse), keep_from, _stream()),
-              "skg_xattn_block_f16_keep")
-        return out, st, q, o, lse
-    check(lib.skg_xattn_block_f16(_p(X), _ld(X), _p(out), _ld(out), M, HW, C, heads, Nkv, _p(gamma), _p(beta), eps, _p(wpack),
-                                  _p(kvpack), _p(bias_out), scale, _stream()), "skg_xattn_block_f16")
-    return out
+    check(lib.skg_xattn_block_f16(_p(Xh), _p(X.lo) if pair else None, _ld(Xh), _p(Yh), _p(Yl), _ld(Yh), M, HW, C, heads, Nkv,
+                                  _p(gamma), _p(beta), eps, _p(wpack), _p(kvpack), _p(bias_out), scale, _p(st), _p(q), _p(o), C,
+                                  _p(lse), keep_from or 0, _stream()), "skg_xattn_block_f16")
+    return out if keep_from is None else (out, st, q, o, lse)
 
 
 def conv3x3(X: torch.Tensor, Wp: torch.Tensor, rows: int, IH: int, IW: int, mode: int = CONV_S1,
@@ -351,32 +296,15 @@ def conv3x3(X: torch.Tensor, Wp: torch.Tensor, rows: int, IH: int, IW: int, mode
         OH, OW = IH * 2, IW * 2
     if out is None:
         out = torch.empty(rows * OH * OW, Cout, device=X.device, dtype=torch.float16)
-    if out_lo is not None or residual_lo is not None:
-        assert out_lo is None or _ld(out_lo) == _ld(out)
-        assert residual_lo is None or residual is None or _ld(residual_lo) == _ld(residual)
-        r_any = residual if residual is not None else residual_lo
-        if gn_groups is not None:
-            part = GNPartial(rows, OH * OW, gn_groups, X.device)
-            check(lib.skg_conv3x3_f16_hilo_gn(_p(X), _ld(X), _p(Wp), _p(out), _p(out_lo), _ld(out), rows, IH, IW, Cin, Cout, mode,
-                                              _p(bias), _p(residual), _p(residual_lo), _ld(r_any) if r_any is not None else 0,
-                                              alpha, EPI_RELU if relu else 0, _p(part.buf), gn_groups, _stream()),
-                  "skg_conv3x3_f16_hilo_gn")
-            return out, part
-        check(lib.skg_conv3x3_f16_hilo(_p(X), _ld(X), _p(Wp), _p(out), _p(out_lo), _ld(out), rows, IH, IW, Cin, Cout, mode,
-                                       _p(bias), _p(residual), _p(residual_lo), _ld(r_any) if r_any is not None else 0,
-                                       alpha, EPI_RELU if relu else 0, _stream()), "skg_conv3x3_f16_hilo")
-        return out
-    if gn_groups is not None:
-        part = GNPartial(rows, OH * OW, gn_groups, X.device)
-        check(lib.skg_conv3x3_f16_gn(_p(X), _ld(X), _p(Wp), _p(out), _ld(out), rows, IH, IW, Cin, Cout, mode,
-                                     _p(bias), _p(residual), _ld(residual) if residual is not None else 0,
-                                     alpha, EPI_RELU if relu else 0, _p(part.buf), gn_groups, _stream()),
-              "skg_conv3x3_f16_gn")
-        return out, part
-    check(lib.skg_conv3x3_f16(_p(X), _ld(X), _p(Wp), _p(out), _ld(out), rows, IH, IW, Cin, Cout, mode,
-                              _p(bias), _p(residual), _ld(residual) if residual is not None else 0,
-                              alpha, EPI_RELU if relu else 0, _stream()), "skg_conv3x3_f16")
-    return out
+    assert out_lo is None or _ld(out_lo) == _ld(out)
+    assert residual_lo is None or residual is None or _ld(residual_lo) == _ld(residual)
+    r_any = residual if residual is not None else residual_lo
+    part = GNPartial(rows, OH * OW, gn_groups, X.device) if gn_groups is not None else None
+    check(lib.skg_conv3x3_f16(_p(X), _ld(X), _p(Wp), _p(out), _p(out_lo), _ld(out), rows, IH, IW, Cin, Cout, mode,
+                              _p(bias), _p(residual), _p(residual_lo), _ld(r_any) if r_any is not None else 0,
+                              alpha, EPI_RELU if relu else 0, _p(part.buf) if part is not None else None, gn_groups or 0,
+                              _stream()), "skg_conv3x3_f16")
+    return out if part is None else (out, part)
 
 
 def conv3x3_sc(X: torch.Tensor, X2: torch.Tensor, Wcat: torch.Tensor, rows: int, IH: int, IW: int, out: Optional[torch.Tensor] = None, *,
@@ -448,7 +376,7 @@ def conv_up2(X: torch.Tensor, Wpp: torch.Tensor, rows: int, IH: int, IW: int, ou
     if out is None:
         out = torch.empty(rows * 4 * IH * IW, Cout, device=X.device, dtype=torch.float16)
     try:
-        check(lib.skg_conv3x3_up2_f16(_p(X), _ld(X), _p(Wpp), _p(out), _ld(out), rows, IH, IW, Cin, Cout, _p(bias), _stream()),
+        check(lib.skg_conv3x3_up2_f16(_p(X), _ld(X), _p(Wpp), _p(out), None, _ld(out), rows, IH, IW, Cin, Cout, 0, _p(bias), _stream()),
               "skg_conv3x3_up2_f16")
     except SkgError as e:      # the LDS-DMA kernel declined the launch (an operand >= 2 GiB): the 9-tap gather form, when the caller has its pack
         if e.rc != -2 or W9 is None:
@@ -466,8 +394,8 @@ def conv_up2_hilo(X2: torch.Tensor, Wpp3: torch.Tensor, rows: int, IH: int, IW: 
     C, Cout = X2.shape[1] // 2, Wpp3.shape[1]
     assert Wpp3.shape == (4, Cout, 12 * C) and Wpp3.is_contiguous() and X2.shape[0] == rows * IH * IW and _ld(out.hi) == _ld(out.lo)
     try:
-        check(lib.skg_conv3x3_up2_f16_hilo(_p(X2), _ld(X2), _p(Wpp3), _p(out.hi), _p(out.lo), _ld(out.hi), rows, IH, IW, C, Cout, _p(bias),
-                                           _stream()), "skg_conv3x3_up2_f16_hilo")
+        check(lib.skg_conv3x3_up2_f16(_p(X2), _ld(X2), _p(Wpp3), _p(out.hi), _p(out.lo), _ld(out.hi), rows, IH, IW, C, Cout, 1, _p(bias),
+                                      _stream()), "skg_conv3x3_up2_f16 (pair input)")
     except SkgError as e:
         if e.rc != -2 or W9x2 is None:
             raise
@@ -481,8 +409,8 @@ def conv_up2_pairout(X: torch.Tensor, Wpp: torch.Tensor, rows: int, IH: int, IW:
     _f16(X, Wpp, bias, out.hi, out.lo)
     Cin, Cout = X.shape[1], Wpp.shape[1]
     assert Wpp.shape == (4, Cout, 4 * Cin) and Wpp.is_contiguous() and X.shape[0] == rows * IH * IW and _ld(out.hi) == _ld(out.lo)
-    check(lib.skg_conv3x3_up2_f16_pairout(_p(X), _ld(X), _p(Wpp), _p(out.hi), _p(out.lo), _ld(out.hi), rows, IH, IW, Cin, Cout, _p(bias),
-                                          _stream()), "skg_conv3x3_up2_f16_pairout")
+    check(lib.skg_conv3x3_up2_f16(_p(X), _ld(X), _p(Wpp), _p(out.hi), _p(out.lo), _ld(out.hi), rows, IH, IW, Cin, Cout, 0, _p(bias),
+                                  _stream()), "skg_conv3x3_up2_f16 (pair output)")
     return out
 
 
@@ -540,94 +468,77 @@ def groupnorm_stats(X, rows, HW, groups, eps, stats=None):
     return stats
 
 
-def groupnorm_apply(X, rows, HW, groups, stats, gamma, beta, silu: bool, out=None):
-    _f16(X, gamma, beta)
+def groupnorm_apply(X, rows, HW, groups, stats, gamma, beta, silu: bool, out=None, X_lo=None):
+    """X_lo (accuracy mode): the apply reads the pair X + X_lo (one pitch); stats from groupnorm_stats on the hi part."""
+    _f16(X, X_lo, gamma, beta)
+    assert X_lo is None or _ld(X_lo) == _ld(X)
     C = X.shape[1]
     if out is None:
         out = torch.empty(X.shape[0], C, device=X.device, dtype=torch.float16)
-    check(lib.skg_groupnorm_apply(_p(X), _ld(X), _p(out), _ld(out), rows, HW, C, groups, _p(stats), _p(gamma),
+    check(lib.skg_groupnorm_apply(_p(X), _p(X_lo), _ld(X), _p(out), _ld(out), rows, HW, C, groups, _p(stats), _p(gamma),
                                   _p(beta), int(silu), _stream()), "skg_groupnorm_apply")
     return out
 
 
-def groupnorm(X, rows, HW, groups, eps, gamma, beta, silu: bool, out=None, partial: Optional[GNPartial] = None):
-    """Forward GroupNorm.  partial=: the producer of X already left the chunk sums behind (gemm / conv3x3 with
-    gn_stats= / gn_groups=): ONE launch that folds them and applies, X is read once.
-    Otherwise:  Up to 32x32 maps: two launches (chunk partial sums; apply, which folds the partials itself
-    and publishes the statistics) - at 64x64 the 86 chunk partials per group make the in-kernel fold dearer than the
-    4.7 us finalize launch it replaces, so the three-launch path stays (measured: tools/ew_bench.py)."""
-    if isinstance(partial, tuple):
-        # X = [A | B], each half written by its own producer: (GNPartial of A, channels of A, GNPartial of B)
-        pa, CA, pb = partial
-        assert pa.rows == rows and pb.rows == rows and pa.nch == pb.nch == HW // 128
-        _f16(X, gamma, beta)
-        C = X.shape[1]
-        if out is None:
-            out = torch.empty(X.shape[0], C, device=X.device, dtype=torch.float16)
-        st = torch.empty(rows, groups, 2, device=X.device, dtype=torch.float32)
-        check(lib.skg_groupnorm_from_partial2(_p(X), _ld(X), _p(out), _ld(out), rows, HW, C, CA, groups, eps, _p(gamma),
-                                              _p(beta), int(silu), _p(st), _p(pa.buf), pa.groups, _p(pb.buf),
-                                              pb.groups, pa.nch, _stream()), "skg_groupnorm_from_partial2")
-        return out, st
-    if partial is not None:
-        assert partial.rows == rows and partial.groups == groups and partial.nch == HW // 128
-        _f16(X, gamma, beta)
-        C = X.shape[1]
-        if out is None:
-            out = torch.empty(X.shape[0], C, device=X.device, dtype=torch.float16)
-        st = torch.empty(rows, groups, 2, device=X.device, dtype=torch.float32)
-        check(lib.skg_groupnorm_from_partial(_p(X), _ld(X), _p(out), _ld(out), rows, HW, C, groups, eps, _p(gamma),
-                                             _p(beta), int(silu), _p(st), _p(partial.buf), partial.nch, _stream()),
-              "skg_groupnorm_from_partial")
-        return out, st
-    if HW >= 4096:
-        st = groupnorm_stats(X, rows, HW, groups, eps)
-        return groupnorm_apply(X, rows, HW, groups, st, gamma, beta, silu, out), st
-    _f16(X, gamma, beta)
+def _groupnorm(X, X_lo, rows, HW, groups, eps, gamma, beta, silu, out, out_lo, partial):
+    """The one-launch forms behind groupnorm / groupnorm_hilo -> (out, statistics): from the producers' partial sums (a
+    GNPartial, or (GNPartial of A, channels of A, GNPartial of B) for a concatenation [A | B]), else with an own pass."""
+    _f16(X, X_lo, gamma, beta, out_lo)
     C = X.shape[1]
     if out is None:
         out = torch.empty(X.shape[0], C, device=X.device, dtype=torch.float16)
     st = torch.empty(rows, groups, 2, device=X.device, dtype=torch.float32)
-    check(lib.skg_groupnorm_fwd(_p(X), _ld(X), _p(out), _ld(out), rows, HW, C, groups, eps, _p(gamma), _p(beta),
-                                int(silu), _p(st), _p(_gn_scratch(rows, groups, X.device)), _stream()),
-          "skg_groupnorm_fwd")
+    if partial is None:
+        check(lib.skg_groupnorm_fwd(_p(X), _p(X_lo), _ld(X), _p(out), _p(out_lo), _ld(out), rows, HW, C, groups, eps, _p(gamma),
+                                    _p(beta), int(silu), _p(st), _p(_gn_scratch(rows, groups, X.device)), _stream()),
+              "skg_groupnorm_fwd")
+        return out, st
+    pa, CA, pb = partial if isinstance(partial, tuple) else (partial, 0, None)
+    assert pa.rows == rows and pa.nch == HW // 128
+    assert pa.groups == groups if pb is None else (pb.rows == rows and pb.nch == pa.nch)
+    check(lib.skg_groupnorm_from_partial(_p(X), _p(X_lo), _ld(X), _p(out), _p(out_lo), _ld(out), rows, HW, C, CA, groups, eps,
+                                         _p(gamma), _p(beta), int(silu), _p(st), _p(pa.buf), pa.groups,
+                                         None if pb is None else _p(pb.buf), 0 if pb is None else pb.groups, pa.nch, _stream()),
+          "skg_groupnorm_from_partial")
     return out, st
+
+
+def groupnorm(X, rows, HW, groups, eps, gamma, beta, silu: bool, out=None, partial: Optional[GNPartial] = None):
+    """Forward GroupNorm.  partial=: the producer of X already left the chunk sums behind (gemm / conv3x3 with
+    gn_stats= / gn_groups=): ONE launch that folds them and applies, X is read once; (GNPartial of A, channels of A, GNPartial
+    of B): X = [A | B], each half written by its own producer.
+    Otherwise:  Up to 32x32 maps: two launches (chunk partial sums; apply, which folds the partials itself
+    and publishes the statistics) - at 64x64 the 86 chunk partials per group make the in-kernel fold dearer than the
+    4.7 us finalize launch it replaces, so the three-launch path stays (measured: tools/ew_bench.py)."""
+    if partial is None and HW >= 4096:
+        st = groupnorm_stats(X, rows, HW, groups, eps)
+        return groupnorm_apply(X, rows, HW, groups, st, gamma, beta, silu, out), st
+    return _groupnorm(X, None, rows, HW, groups, eps, gamma, beta, silu, out, None, partial)
 
 
 def groupnorm_hilo(X, X_lo, rows, HW, groups, eps, gamma, beta, silu: bool, out=None, want_stats=False, partial=None, out_lo=None):
     """GroupNorm(+SiLU) of the pair X + X_lo (accuracy mode): statistics from the hi part (the producer's epilogue sums when
     `partial` - a GNPartial, or (GNPartial of A, channels of A, GNPartial of B) for a concatenation - is given, else an own
     pass; small maps: one launch on the pair's sum), apply on the sum.  out_lo: the output as a pair too (pitch of `out`)."""
-    _f16(X, X_lo, gamma, beta, out_lo)
     assert _ld(X) == _ld(X_lo) and (out_lo is None or (out is not None and _ld(out_lo) == _ld(out)))
-    C = X.shape[1]
-    if out is None:
-        out = torch.empty(X.shape[0], C, device=X.device, dtype=torch.float16)
-    st = torch.empty(rows, groups, 2, device=X.device, dtype=torch.float32)
-    if partial is not None:
-        pa, CA, pb = partial if isinstance(partial, tuple) else (partial, 0, None)
-        assert pa.rows == rows and pa.nch == HW // 128 and (pb is not None or pa.groups == groups)
-        check(lib.skg_groupnorm_from_partial_hilo(_p(X), _p(X_lo), _ld(X), _p(out), _p(out_lo), _ld(out), rows, HW, C, CA, groups, eps,
-                                                  _p(gamma), _p(beta), int(silu), _p(st), _p(pa.buf), pa.groups,
-                                                  None if pb is None else _p(pb.buf), 0 if pb is None else pb.groups, pa.nch,
-                                                  _stream()), "skg_groupnorm_from_partial_hilo")
-    else:
-        check(lib.skg_groupnorm_fwd_hilo(_p(X), _p(X_lo), _ld(X), _p(out), _p(out_lo), _ld(out), rows, HW, C, groups, eps, _p(gamma),
-                                         _p(beta), int(silu), _p(st), _p(_gn_scratch(rows, groups, X.device)), _stream()),
-              "skg_groupnorm_fwd_hilo")
+    out, st = _groupnorm(X, X_lo, rows, HW, groups, eps, gamma, beta, silu, out, out_lo, partial)
     return (out, st) if want_stats else out
 
 
-def layernorm_hilo(X, X_lo, gamma, beta, eps=1e-5, out=None, want_stats=False):
+def _layernorm(X, X_lo, gamma, beta, eps, out, want_stats):
     _f16(X, X_lo, gamma, beta)
-    assert _ld(X) == _ld(X_lo)
     M, C = X.shape
     if out is None:
         out = torch.empty(M, C, device=X.device, dtype=torch.float16)
     stats = torch.empty(M, 2, device=X.device, dtype=torch.float32) if want_stats else None
-    check(lib.skg_layernorm_fwd_hilo(_p(X), _p(X_lo), _ld(X), _p(out), _ld(out), M, C, _p(gamma), _p(beta), eps, _p(stats),
-                                     _stream()), "skg_layernorm_fwd_hilo")
+    check(lib.skg_layernorm_fwd(_p(X), _p(X_lo), _ld(X), _p(out), _ld(out), M, C, _p(gamma), _p(beta), eps, _p(stats),
+                                _stream()), "skg_layernorm_fwd")
     return (out, stats) if want_stats else out
+
+
+def layernorm_hilo(X, X_lo, gamma, beta, eps=1e-5, out=None, want_stats=False):
+    assert _ld(X) == _ld(X_lo)
+    return _layernorm(X, X_lo, gamma, beta, eps, out, want_stats)
 
 
 def groupnorm_bwd(X, dY, rows, HW, groups, stats, gamma, beta, silu: bool, residual=None, out=None):
@@ -643,14 +554,7 @@ def groupnorm_bwd(X, dY, rows, HW, groups, stats, gamma, beta, silu: bool, resid
 
 
 def layernorm(X, gamma, beta, eps=1e-5, out=None, want_stats=False):
-    _f16(X, gamma, beta)
-    M, C = X.shape
-    if out is None:
-        out = torch.empty(M, C, device=X.device, dtype=torch.float16)
-    stats = torch.empty(M, 2, device=X.device, dtype=torch.float32) if want_stats else None
-    check(lib.skg_layernorm_fwd(_p(X), _ld(X), _p(out), _ld(out), M, C, _p(gamma), _p(beta), eps, _p(stats),
-                                _stream()), "skg_layernorm_fwd")
-    return (out, stats) if want_stats else out
+    return _layernorm(X, None, gamma, beta, eps, out, want_stats)
 
 
 def layernorm_bwd(X, dY, gamma, stats, residual=None, out=None):
@@ -798,9 +702,9 @@ def attn_fwd(Q, K, Vt, batch, heads, Nq, Nkv, kv_stride, dh, scale, out=None, wa
     if out is None:
         out = torch.empty(batch * Nq, heads * dh, device=Q.device, dtype=torch.float16)
     lse = torch.empty(batch, heads, Nq, device=Q.device, dtype=torch.float32) if want_lse else None
-    fn = lib.skg_attn_fwd_causal if causal else lib.skg_attn_fwd_rowv if v_rows else lib.skg_attn_fwd
-    check(fn(_p(Q), _ld(Q), _p(K), _ld(K), _p(Vt), _ld(Vt), _p(out), _ld(out), _p(lse), batch,
-             heads, Nq, Nkv, kv_stride, dh, scale, _stream()), "skg_attn_fwd")
+    check(lib.skg_attn_fwd(_p(Q), _ld(Q), _p(K), _ld(K), _p(Vt), _ld(Vt), _p(out), _ld(out), _p(lse), batch,
+                           heads, Nq, Nkv, kv_stride, dh, scale, (ATTN_CAUSAL if causal else 0) | (ATTN_ROWV if v_rows else 0),
+                           _stream()), "skg_attn_fwd")
     return (out, lse) if want_lse else out
 
 
@@ -816,20 +720,20 @@ def attn_bwd_dq(Q, K, V, dO, lse, delta, batch, heads, Nq, Nkv, kv_stride, dh, s
     _f16(Q, K, V, dO)
     if out is None:
         out = torch.empty(batch * Nq, heads * dh, device=Q.device, dtype=torch.float16)
-    check(lib.skg_attn_bwd_dq(_p(Q), _ld(Q), _p(K), _ld(K), _p(V), _ld(V), _p(dO), _ld(dO),
-                              _p(lse), _p(delta), _p(out), _ld(out), batch, heads, Nq, Nkv, kv_stride, dh,
+    check(lib.skg_attn_bwd_dq(_p(Q), _ld(Q), _p(K), _ld(K), _p(V), _ld(V), _p(dO), _ld(dO), None, 0,
+                              _p(lse), _p(delta), None, _p(out), _ld(out), batch, heads, Nq, Nkv, kv_stride, dh,
                               scale, _stream()), "skg_attn_bwd_dq")
     return out
 
 
 def attn_bwd_dq_delta(Q, K, V, dO, O, lse, batch, heads, Nq, Nkv, kv_stride, dh, scale, out=None):
-    """attn_bwd_delta + attn_bwd_dq in one launch (skg_attn_bwd_dq_delta) -> (dQ, delta)."""
+    """attn_bwd_delta + attn_bwd_dq in one launch (skg_attn_bwd_dq without delta) -> (dQ, delta)."""
     _f16(Q, K, V, dO, O)
     if out is None:
         out = torch.empty(batch * Nq, heads * dh, device=Q.device, dtype=torch.float16)
     delta = torch.empty(batch, heads, Nq, device=Q.device, dtype=torch.float32)
-    check(lib.skg_attn_bwd_dq_delta(_p(Q), _ld(Q), _p(K), _ld(K), _p(V), _ld(V), _p(dO), _ld(dO), _p(O), _ld(O), _p(lse), _p(delta),
-                                    _p(out), _ld(out), batch, heads, Nq, Nkv, kv_stride, dh, scale, _stream()), "skg_attn_bwd_dq_delta")
+    check(lib.skg_attn_bwd_dq(_p(Q), _ld(Q), _p(K), _ld(K), _p(V), _ld(V), _p(dO), _ld(dO), _p(O), _ld(O), _p(lse), None, _p(delta),
+                              _p(out), _ld(out), batch, heads, Nq, Nkv, kv_stride, dh, scale, _stream()), "skg_attn_bwd_dq (delta prologue)")
     return out, delta
 
 
@@ -841,7 +745,7 @@ def attn_bwd_dkv(Q, K, V, dO, lse, delta, batch, heads, Nq, Nkv, dh, scale, dK=N
         dV = torch.empty(batch * Nkv, heads * dh, device=Q.device, dtype=torch.float16)
     check(lib.skg_attn_bwd_dkv(_p(Q), _ld(Q), _p(K), _ld(K), _p(V), _ld(V), _p(dO), _ld(dO),
                                _p(lse), _p(delta), _p(dK), _ld(dK), _p(dV), _ld(dV), batch,
-                               heads, Nq, Nkv, dh, scale, _stream()), "skg_attn_bwd_dkv")
+                               heads, Nq, Nkv, Nkv, dh, scale, _stream()), "skg_attn_bwd_dkv")
     return dK, dV
 
 
@@ -851,9 +755,9 @@ def attn_bwd_dkv_strided(Q, K, V, dO, lse, delta, batch, heads, Nq, Nkv, kv_stri
     _f16(Q, K, V, dO, dK, dV)
     assert kv_stride >= Nkv and dK.shape[0] >= (batch - 1) * kv_stride + Nkv and dV.shape[0] >= (batch - 1) * kv_stride + Nkv
     assert K.shape[0] >= (batch - 1) * kv_stride + Nkv and V.shape[0] >= (batch - 1) * kv_stride + Nkv
-    check(lib.skg_attn_bwd_dkv_strided(_p(Q), _ld(Q), _p(K), _ld(K), _p(V), _ld(V), _p(dO), _ld(dO),
-                                       _p(lse), _p(delta), _p(dK), _ld(dK), _p(dV), _ld(dV), batch,
-                                       heads, Nq, Nkv, kv_stride, dh, scale, _stream()), "skg_attn_bwd_dkv_strided")
+    check(lib.skg_attn_bwd_dkv(_p(Q), _ld(Q), _p(K), _ld(K), _p(V), _ld(V), _p(dO), _ld(dO),
+                               _p(lse), _p(delta), _p(dK), _ld(dK), _p(dV), _ld(dV), batch,
+                               heads, Nq, Nkv, kv_stride, dh, scale, _stream()), "skg_attn_bwd_dkv (strided)")
     return dK, dV
 
 
@@ -861,8 +765,7 @@ def attn_bwd_dkv_strided(Q, K, V, dO, lse, delta, batch, heads, Nq, Nkv, kv_stri
 def lgp_layer0_gather(P: Sequence[torch.Tensor], sizes: Sequence[int], Wextra, bias0, noise, sigma: float,
                       samples: int, h: int, H0: int, out=None, rows: Optional[int] = None, w: Optional[int] = None):
     """rows defaults to 2*samples ([uncond ; cond] blocks of the sampler); the trainer passes rows = samples.
-    w: the grid's width when it is not square (skg_lgp_layer0_gather_hw; sizes are the taps' heights, a tap of height s is
-    s * w // h wide)."""
+    w: the grid's width when it is not square (sizes are the taps' heights, a tap of height s is s * w // h wide)."""
     rows = 2 * samples if rows is None else rows
     wd = h if w is None else w
     arr = (SkgTap * len(P))()
@@ -871,11 +774,8 @@ def lgp_layer0_gather(P: Sequence[torch.Tensor], sizes: Sequence[int], Wextra, b
         arr[i].P, arr[i].s = t.data_ptr(), s
     if out is None:
         out = torch.empty(rows * h * wd, H0, device=noise.device, dtype=torch.float16)
-    wx = (_p(Wextra), _ld(Wextra) if Wextra is not None else 0, _p(bias0), _p(noise), sigma, samples, _p(out), rows, h)
-    if w is None:
-        check(lib.skg_lgp_layer0_gather(ctypes.addressof(arr), len(P), *wx, H0, _stream()), "skg_lgp_layer0_gather")
-    else:
-        check(lib.skg_lgp_layer0_gather_hw(ctypes.addressof(arr), len(P), *wx, w, H0, _stream()), "skg_lgp_layer0_gather_hw")
+    check(lib.skg_lgp_layer0_gather(ctypes.addressof(arr), len(P), _p(Wextra), _ld(Wextra) if Wextra is not None else 0, _p(bias0),
+                                    _p(noise), sigma, samples, _p(out), rows, h, wd, H0, _stream()), "skg_lgp_layer0_gather")
     return out
 
 
@@ -886,10 +786,7 @@ def lgp_layer0_scatter(dZ, rows, h, s, H0, w: Optional[int] = None):
         return dZ
     wd = h if w is None else w
     out = torch.empty(rows * s * (s * wd // h), H0, device=dZ.device, dtype=torch.float16)
-    if w is None:
-        check(lib.skg_lgp_layer0_scatter(_p(dZ), _ld(dZ), _p(out), rows, h, s, H0, _stream()), "skg_lgp_layer0_scatter")
-    else:
-        check(lib.skg_lgp_layer0_scatter_hw(_p(dZ), _ld(dZ), _p(out), rows, h, w, s, H0, _stream()), "skg_lgp_layer0_scatter_hw")
+    check(lib.skg_lgp_layer0_scatter(_p(dZ), _ld(dZ), _p(out), rows, h, wd, s, H0, _stream()), "skg_lgp_layer0_scatter")
     return out
 
 
@@ -939,14 +836,11 @@ def bn_relu_bwd(X, dY, samples, segs, seg_rows, stats, gamma, train: bool, out=N
 
 def lgp_mse_seed(out16, target, samples, h, ldd, loss_scale, w: Optional[int] = None):
     _f16(out16)
-    dOut = torch.empty(2 * samples * h * (h if w is None else w), ldd, device=out16.device, dtype=torch.float16)
+    wd = h if w is None else w
+    dOut = torch.empty(2 * samples * h * wd, ldd, device=out16.device, dtype=torch.float16)
     loss = torch.empty(samples, device=out16.device, dtype=torch.float32)
-    if w is None:
-        check(lib.skg_lgp_mse_seed(_p(out16), _ld(out16), _p(target), _p(dOut), ldd, _p(loss), samples, h,
-                                   loss_scale, _stream()), "skg_lgp_mse_seed")
-    else:
-        check(lib.skg_lgp_mse_seed_hw(_p(out16), _ld(out16), _p(target), _p(dOut), ldd, _p(loss), samples, h, w,
-                                      loss_scale, _stream()), "skg_lgp_mse_seed_hw")
+    check(lib.skg_lgp_mse_seed(_p(out16), _ld(out16), _p(target), _p(dOut), ldd, _p(loss), samples, h, wd,
+                               loss_scale, _stream()), "skg_lgp_mse_seed")
     return dOut, loss
 
 
@@ -972,13 +866,10 @@ def bn_param_grads(X, dY, stats, scale: float = 1.0):
 
 
 def lgp_extra_features(noise, sigma: float, samples: int, rows: int, h: int, ld: int = 64, w: Optional[int] = None):
-    out = torch.empty(rows * h * (h if w is None else w), ld, device=noise.device, dtype=torch.float16)
-    if w is None:
-        check(lib.skg_lgp_extra_features(_p(noise), sigma, samples, rows, h, _p(out), ld, _stream()),
-              "skg_lgp_extra_features")
-    else:
-        check(lib.skg_lgp_extra_features_hw(_p(noise), sigma, samples, rows, h, w, _p(out), ld, _stream()),
-              "skg_lgp_extra_features_hw")
+    wd = h if w is None else w
+    out = torch.empty(rows * h * wd, ld, device=noise.device, dtype=torch.float16)
+    check(lib.skg_lgp_extra_features(_p(noise), sigma, samples, rows, h, wd, _p(out), ld, _stream()),
+          "skg_lgp_extra_features")
     return out
 
 

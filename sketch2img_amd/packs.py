@@ -119,7 +119,7 @@ def pack_ff_block(w1: torch.Tensor, b1: torch.Tensor, w2: torch.Tensor, dev, w_p
       40 W1 pieces (t, ks): t = value 0-15, value 16-31, gate 0-15, gate 16-31; [lane = 16 g + l][i] = W1[row(t, l)][32 ks + 8 g + i]
       20 W2 pieces u:       [lane = 16 g + l][i] = W2[16 u + l][32 c + 16 (i >> 2) + 4 g + (i & 3)]
     (the hidden-unit order of the second product is the accumulator layout of the first).
-    w_proj [C, C] (Transformer2DModel.proj_out, skg_ff_block_proj_f16): five more chunks j behind them whose first 40 pieces are
+    w_proj [C, C] (Transformer2DModel.proj_out, skg_ff_block_f16 with bias_proj): five more chunks j behind them whose first 40 pieces are
       (t, ks): [lane = 16 g + l][i] = Wp[16 (4 j + t) + l][32 ks + 16 (i >> 2) + 4 g + (i & 3)]   (the block output's accumulator order)
     and whose last 20 pieces are zeros.
     Returns (pack fp16 [F/32 (+ 5), 60, 512], bias1 fp32 [F/32, 4, 16])."""

@@ -40,7 +40,7 @@ _XATTN_HEADS = (8,) if os.environ.get("SKG_XATTN_D64", "1") == "0" else (8, 5)  
 _XATTN_KEEP = os.environ.get("SKG_XATTN_KEEP", "1") != "0"          # the fused cross-attention launch also in guided steps (stashing launch)
 _XATTN_KEEP_HP = os.environ.get("SKG_XATTN_KEEP_HP", "1") != "0"    # ... and in the accuracy mode's guided steps (pairs)
 _FF_PROJ = os.environ.get("SKG_FF_PROJ", "1") != "0"                # proj_out + outer residual inside the fused feed-forward launch
-_FF_PROJ_HP = os.environ.get("SKG_FF_PROJ_HP", "1") != "0"          # ... in the accuracy mode too (skg_ff_block_proj_f16_hilo, round 5)
+_FF_PROJ_HP = os.environ.get("SKG_FF_PROJ_HP", "1") != "0"          # ... in the accuracy mode too (skg_ff_block_f16 with bias_proj on pairs, round 5)
 _ATTN_DQ_DELTA = os.environ.get("SKG_ATTN_DQ_DELTA", "1") != "0"    # attention backward: delta inside the dQ launch (round 5)
 _RES_SC = os.environ.get("SKG_RES_SC", "1") != "0"                  # conv2 + conv_shortcut of a ResnetBlock as one implicit GEMM (round 5)
 # round 6: the ResnetBlock convolutions of the two deepest levels (16 x 16 / 8 x 8 at 64 x 64 latents) by Winograd F(2x2, 3x3) (csrc/wino.hip):
@@ -387,7 +387,7 @@ class HipUNet:
         for k in list(sd.keys()):
             if k.endswith(".ff.net.0.proj.weight") and sd[k].shape[1] == 320 and sd[k].shape[0] // 2 <= 1280:
                 t = k[: -len(".ff.net.0.proj.weight")]
-                # (with Transformer2DModel.proj_out behind it when the block has one of the same width: skg_ff_block_proj_f16;
+                # (with Transformer2DModel.proj_out behind it when the block has one of the same width: skg_ff_block_f16 with bias_proj;
                 # the plain launch reads the leading chunks of the same tensor)
                 tp = t[: -len(".transformer_blocks.0")] if t.endswith(".transformer_blocks.0") else None
                 wpj = sd.get(tp + ".proj_out.weight") if tp else None
@@ -729,7 +729,7 @@ class HipUNet:
             ffargs = (W[t + ".norm3.weight"], W[t + ".norm3.bias"], 1e-5, W[t + (".ff.packp" if ffp else ".ff.pack")], W[t + ".ff.bias1"],
                       W[t + ".ff.net.2.bias"])
             if ffp:
-                # ... and proj_out + the outer residual behind it in the same launch (skg_ff_block_proj_f16[_hilo]): the block output
+                # ... and proj_out + the outer residual behind it in the same launch (skg_ff_block_f16 with bias_proj): the block output
                 # p3 never reaches memory (no backward reads it); GroupNorm partial sums of the result when the consumer folds them
                 _, st3, f, opart = ops.ff_block_proj(p2, *ffargs, W[p + ".proj_out.bias"], x, out=out, want_stats=keep,
                                                      keep_from=M0 if keep else None, gn=gn)

@@ -775,6 +775,41 @@ def test_groupnorm_of_a_concatenation_from_two_producers(ops, rows, H, CA, CB):
         ops.groupnorm(bad, rows, HW, G, 1e-5, ga[:960].contiguous(), be[:960].contiguous(), True, partial=(pa, 640, pb))
 
 
+def test_groupnorm_pair_arms_apply_alone_and_two_producers(ops):
+    """The two pair arms of the GroupNorm entry points that no other test calls through ops: skg_groupnorm_apply with X_lo (the
+    apply alone on a pair, statistics from groupnorm_stats on the hi part) and skg_groupnorm_from_partial with X_lo and a second
+    partial (the concatenation [A | B] on a pair; the partial sums are those of the hi part of each half in the layout the
+    producers leave: [sample][128-row chunk][group][sum, sum of squares], two source groups per output group as in the UNet's up
+    path).  Smallest shape the kernels take: one image, HW = 128 (one chunk), C = 32, 8 groups.  Against torch's fp32 GroupNorm
+    of hi + lo with the bounds of the sibling arms' tests (test_hilo_*: 4e-4 relative, statistics 2e-4)."""
+    d = dev()
+    rows, HW, C, G, CA, GA = 1, 128, 32, 8, 16, 8
+    pr = _as_pair(ops, (3 * torch.randn(rows * HW, C, generator=torch.Generator().manual_seed(11)) + 1.5).to(d))
+    vs = pr.hi.float() + pr.lo.float()
+    ga, be = (1 + 0.1 * rnd(C, seed=12).float()).half().to(d), (0.1 * rnd(C, seed=13).float()).half().to(d)
+    ref = F.silu(F.group_norm(vs.reshape(rows, HW, C).permute(0, 2, 1), G, ga.float(), be.float(), 1e-5)).permute(0, 2, 1).reshape(-1, C)
+    st = ops.groupnorm_stats(pr.hi, rows, HW, G, 1e-5)
+    y = ops.groupnorm_apply(pr.hi, rows, HW, G, st, ga, be, True, X_lo=pr.lo)
+    y16 = ops.groupnorm_apply(pr.hi, rows, HW, G, st, ga, be, True)
+    e, e16 = rel_err(y, ref), rel_err(y16, ref)
+    print(f"groupnorm_apply on a pair: rel {e:.2e} (hi alone: {e16:.2e})")
+    assert e < 4e-4 and e <= e16 * 1.05
+
+    def sums(x, g):
+        xf = x.float().reshape(rows, HW // 128, 128, g, x.shape[1] // g)
+        return torch.stack([xf.sum(dim=(2, 4)), (xf * xf).sum(dim=(2, 4))], dim=-1).reshape(-1)
+    pa, pb = ops.GNPartial(rows, HW, GA, d), ops.GNPartial(rows, HW, GA, d)
+    pa.buf.copy_(sums(pr.hi[:, :CA], GA))
+    pb.buf.copy_(sums(pr.hi[:, CA:], GA))
+    assert ops.gn_concat_ok(CA, C - CA, G, GA, GA)
+    n1, st1 = ops.groupnorm_hilo(pr.hi, pr.lo, rows, HW, G, 1e-5, ga, be, True, want_stats=True, partial=(pa, CA, pb))
+    n0, st0 = ops.groupnorm_hilo(pr.hi, pr.lo, rows, HW, G, 1e-5, ga, be, True, want_stats=True)
+    e1 = rel_err(n1, ref)
+    print(f"groupnorm of a pair from two producers' sums: rel {e1:.2e}, statistics max diff {(st1 - st0).abs().max().item():.2e}")
+    assert e1 < 4e-4
+    assert (st1 - st0).abs().max().item() < 2e-4 * (1 + st0.abs().max().item())
+
+
 @pytest.mark.parametrize("M,C", [(77, 320), (1024, 1280), (5, 32), (4096, 640)])
 def test_layernorm_fwd_bwd(ops, M, C):
     x = rnd(M, C, seed=1) * 2 + 0.5

@@ -160,16 +160,15 @@ def test_lgp_rectangular_entry_points_at_w_equal_h_are_bit_identical():
         b = torch.empty_like(a)
         args = (ctypes.addressof(arr), 3, 0 if Wx is None else Wx.data_ptr(), 0 if Wx is None else Wx.stride(0), b0.data_ptr(),
                 noise.data_ptr(), 0.7, S)
-        assert lib.skg_lgp_layer0_gather(*args, a.data_ptr(), 2 * S, h, H0, None) == 0
-        assert lib.skg_lgp_layer0_gather_hw(*args, b.data_ptr(), 2 * S, h, h, H0, None) == 0
+        ops.lgp_layer0_gather(P, (8, 2, 16), Wx, b0, noise, 0.7, S, h, H0, out=a)      # (w=None: the square grid)
+        assert lib.skg_lgp_layer0_gather(*args, b.data_ptr(), 2 * S, h, h, H0, None) == 0
         torch.cuda.synchronize()
         assert torch.equal(a, b)
     dZ = torch.randn(S * h * h, H0, generator=g).half().to(DEV)
     for s in (8, 2):
-        a = torch.empty(S * s * s, H0, device=DEV, dtype=torch.float16)
+        a = ops.lgp_layer0_scatter(dZ, S, h, s, H0)
         b = torch.empty_like(a)
-        assert lib.skg_lgp_layer0_scatter(dZ.data_ptr(), H0, a.data_ptr(), S, h, s, H0, None) == 0
-        assert lib.skg_lgp_layer0_scatter_hw(dZ.data_ptr(), H0, b.data_ptr(), S, h, h, s, H0, None) == 0
+        assert lib.skg_lgp_layer0_scatter(dZ.data_ptr(), H0, b.data_ptr(), S, h, h, s, H0, None) == 0
         torch.cuda.synchronize()
         assert torch.equal(a, b)
     out = torch.randn(2 * S * h * h, 8, generator=g).half().to(DEV)

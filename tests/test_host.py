@@ -51,7 +51,7 @@ def test_library_exports_every_declared_symbol_with_matching_signature():
     for name, sig in decl.items():
         assert _lib.SIGNATURES[name] == sig, (name, _lib.SIGNATURES[name], sig)
         assert hasattr(_lib.lib, name)
-    assert _lib.lib.skg_abi_version() == _lib.ABI_VERSION == 5
+    assert _lib.lib.skg_abi_version() == _lib.ABI_VERSION == 6
     nm = subprocess.run(["nm", "-D", "--defined-only", _lib.LIB_PATH], capture_output=True, text=True).stdout
     exported = set(re.findall(r" T (skg_\w+)", nm))
     assert set(decl) <= exported
@@ -60,14 +60,18 @@ def test_library_exports_every_declared_symbol_with_matching_signature():
 def test_host_side_argument_checks_do_not_need_a_gpu():
     """Precondition failures return SKG_E_BADARG before any HIP call."""
     from sketch2img_amd._lib import lib
-    assert lib.skg_gemm_f16(None, 0, None, 0, None, 0, 1, 8, 32, None, None, 0, 1.0, 0, None) == -1
-    assert lib.skg_gemm_f16(16, 24, 16, 24, 16, 8, 4, 8, 24, None, None, 0, 1.0, 0, None) == -1      # K % 32
-    assert lib.skg_attn_fwd(16, 8, 16, 8, 16, 8, 16, 8, None, 1, 1, 8, 8, 8, 24, 1.0, None) == -2      # dh = 24
-    assert lib.skg_conv3x3_f16(16, 32, 16, 16, 8, 1, 4, 4, 32, 8, 9, None, None, 0, 1.0, 0, None) == -2  # mode 9
-    assert lib.skg_ff_block_f16(16, 320, 16, 320, 128, 640, 1280, 16, 16, 1e-5, 16, 16, 16, None, None) == -1   # C = 320 only
-    assert lib.skg_ff_block_f16(16, 320, 16, 320, 128, 320, 1296, 16, 16, 1e-5, 16, 16, 16, None, None) == -1   # F % 32
-    assert lib.skg_xattn_block_f16(16, 320, 16, 320, 4096, 4096, 320, 8, 81, 16, 16, 1e-5, 16, 16, 16, 0.158, None) == -1   # Nkv <= 80
-    assert lib.skg_xattn_block_f16(16, 320, 16, 320, 4096, 1000, 320, 8, 77, 16, 16, 1e-5, 16, 16, 16, 0.158, None) == -1  # HW % 128
+    assert lib.skg_gemm_f16(None, 0, None, 0, None, None, 0, 1, 8, 32, None, None, None, 0, 1.0, 0, None, 0, 0, None) == -1
+    assert lib.skg_gemm_f16(16, 24, 16, 24, 16, None, 8, 4, 8, 24, None, None, None, 0, 1.0, 0, None, 0, 0, None) == -1      # K % 32
+    assert lib.skg_attn_fwd(16, 8, 16, 8, 16, 8, 16, 8, None, 1, 1, 8, 8, 8, 24, 1.0, 0, None) == -2      # dh = 24
+    assert lib.skg_conv3x3_f16(16, 32, 16, 16, None, 8, 1, 4, 4, 32, 8, 9, None, None, None, 0, 1.0, 0, None, 0, None) == -2  # mode 9
+    ffb = lambda C, F: lib.skg_ff_block_f16(16, None, 320, 16, None, 320, 128, C, F, 16, 16, 1e-5, 16, 16, 16, None, None, None, 0,
+                                            None, None, 0, 0, None, 0, 0, None)
+    assert ffb(640, 1280) == -1   # C = 320 only
+    assert ffb(320, 1296) == -1   # F % 32
+    xab = lambda HW, Nkv: lib.skg_xattn_block_f16(16, None, 320, 16, None, 320, 4096, HW, 320, 8, Nkv, 16, 16, 1e-5, 16, 16, 16, 0.158,
+                                                  None, None, None, 0, None, 0, None)
+    assert xab(4096, 81) == -1   # Nkv <= 80
+    assert xab(1000, 77) == -1  # HW % 128
     # conv2 + folded shortcut: an X2 operand of 2 GiB or more is DECLINED (-2: the caller runs the two launches), not a bad argument (ADVICE r5)
     sc_args = lambda rows, k2: (16, 320, 16, k2, k2, 16, 16, None, 320, rows, 64, 64, 320, 320, None, 0, None, 0, None)
     assert lib.skg_conv3x3_sc_f16(*sc_args(140, 1920)) == -2 and lib.skg_conv3x3_sc_f16(*sc_args(16, 1920 + 8)) == -1      # K2 % 64
@@ -80,11 +84,71 @@ def test_host_side_argument_checks_do_not_need_a_gpu():
     assert lib.skg_gemm_gn_fused(65536, 320, 288, 32, 1, 4096, 32) == 0         # conv_in: Cin = 32 -> generic kernel
     assert lib.skg_gemm_gn_fused(65536, 960, 2880, 320, 1, 4096, 32) == 0       # 30-wide groups straddle the 160-column tile
     assert lib.skg_gemm_gn_fused(65536, 320, 2880, 320, 1, 4000, 32) == 0       # chunks must be whole 128-row blocks
-    assert lib.skg_gemm_f16_gn(16, 32, 16, 32, 16, 320, 256, 320, 32, None, None, 0, 1.0, 0, None, 128, 32, None) == -1  # no buffer
+    # statistics asked for (a partial-sum buffer) at a shape that cannot have them; a NULL buffer now selects the plain launch
+    assert lib.skg_gemm_f16(16, 32, 16, 32, 16, None, 320, 256, 320, 32, None, None, None, 0, 1.0, 0, 16, 100, 32, None) == -1
     from sketch2img_amd import ops
     assert ops.gn_fusable(65536, 320, 4096, 32) and not ops.gn_fusable(65536, 320, 4000, 32)
     assert ops.gn_concat_ok(320, 320, 32, 32, 32) and ops.gn_concat_ok(640, 640, 32, 32, 32)
     assert not ops.gn_concat_ok(640, 320, 32, 32, 32) and not ops.gn_concat_ok(1280, 640, 32, 32, 32)
+
+
+def test_folded_entry_points_keep_their_twins_preconditions():
+    """One entry point per kernel family (ABI 6): what a removed twin required on top of the plain call is required exactly when
+    the argument that selects its arm is there.  Each pair of rows is the call with the arm selected and the condition violated
+    (-1, what the twin returned), then the call without the arm, which is not refused for that reason: it comes back declined (-2)
+    before anything is launched - an unknown convolution mode or head width, an operand of 2 GiB, and for the GEMM the fused
+    GEGLU at K % 64 != 0 (the only exit of skg_gemm_f16 in front of a launch; the pair arm excludes that flag, so the selected
+    row does without it).  Pointers are small aligned integers that are never dereferenced."""
+    from sketch2img_amd._lib import lib
+    GEGLU = 4
+
+    def gemm(C=16, C_lo=None, ldc=16, K=64, res=None, res_lo=None, ldr=0, flags=0, part=None, HW=0, groups=0, M=256, N=16):
+        return lib.skg_gemm_f16(16, K, 16, K, C, C_lo, ldc, M, N, K, None, res, res_lo, ldr, 1.0, flags, part, HW, groups, None)
+
+    def conv(Y=16, Y_lo=None, ldy=16, Cin=64, res=None, res_lo=None, ldr=0, part=None, groups=0, IH=16, IW=8, Cout=16):
+        return lib.skg_conv3x3_f16(16, Cin, 16, Y, Y_lo, ldy, 2, IH, IW, Cin, Cout, 9, None, res, res_lo, ldr, 1.0, 0, part, groups, None)
+
+    # -- with a lo output or lo residual: K % 64 (Cin % 64), ldc % 8, 16-byte C / C_lo / residual / residual_lo, ldr % 8
+    assert gemm(C_lo=32, K=32) == -1 and gemm(K=32, flags=GEGLU) == -2
+    assert gemm(res_lo=32, ldr=16, K=32) == -1 and gemm(ldr=16, K=32, flags=GEGLU) == -2
+    assert gemm(C_lo=32, ldc=12, N=8) == -1 and gemm(ldc=12, N=16, K=32, flags=GEGLU) == -2
+    assert gemm(C=24, C_lo=32) == -1 and gemm(C=24, K=32, flags=GEGLU) == -2
+    assert gemm(C_lo=24) == -1 and gemm(C_lo=None, K=32, flags=GEGLU) == -2
+    assert gemm(C_lo=32, res=24, ldr=16) == -1 and gemm(res=24, ldr=16, K=32, flags=GEGLU) == -2
+    assert gemm(res=32, res_lo=48, ldr=12) == -1 and gemm(res=32, ldr=12, K=32, flags=GEGLU) == -2
+    assert conv(Y_lo=32, Cin=32) == -1 and conv(Cin=32) == -2
+    assert conv(res_lo=32, ldr=16, Cin=32) == -1 and conv(ldr=16, Cin=32) == -2
+    assert conv(Y_lo=32, ldy=20) == -1 and conv(ldy=20) == -2
+    assert conv(Y=24, Y_lo=32) == -1 and conv(Y=24) == -2
+    assert conv(Y_lo=32, res=24, ldr=16) == -1 and conv(res=24, ldr=16) == -2
+    assert conv(res=32, res_lo=48, ldr=12) == -1 and conv(res=32, ldr=12) == -2
+    assert conv(Y_lo=32) == -2 and conv(res=32, res_lo=48, ldr=16) == -2                              # the arm itself is fine
+    # -- with gn_partial: the shape rule of the statistics (whole 128-row chunks, even groups, ldc % 8, fp16 out) and a 16-byte C
+    assert gemm(part=16, HW=100, groups=4) == -1 and gemm(HW=100, groups=4, K=32, flags=GEGLU) == -2
+    assert gemm(part=16, HW=128, groups=3) == -1 and gemm(HW=128, groups=3, K=32, flags=GEGLU) == -2   # N % groups
+    assert gemm(part=16, HW=128, groups=4, flags=2) == -1                                             # fp32 out
+    assert gemm(C=24, part=16, HW=128, groups=4) == -1 and gemm(C=24, HW=128, groups=4, K=32, flags=GEGLU) == -2
+    assert conv(part=16, groups=4, IH=10, IW=10) == -1 and conv(groups=4, IH=10, IW=10) == -2        # HW = 100
+    assert conv(part=16, groups=3) == -1 and conv(groups=3) == -2
+    assert conv(Y=24, part=16, groups=4) == -1 and conv(Y=24, groups=4) == -2
+    assert conv(part=16, groups=4) == -2                                                              # the arm itself is fine
+    # -- polyphase upsampler with a pair input: Y_lo and C % 64 (rows chosen so that the plain launch is declined: X spans 2 GiB)
+    up2 = lambda Y_lo, C, pair_in, ldx: lib.skg_conv3x3_up2_f16(16, ldx, 16, 16, Y_lo, 320, 140, 64, 64, C, 320, pair_in, None, None)
+    assert up2(None, 960, 1, 1920) == -1 and up2(None, 960, 0, 1920) == -2
+    assert up2(32, 32, 1, 1920) == -1 and up2(32, 960, 1, 1920) == -2
+    # -- attention backward dK / dV: kv_stride >= Nkv (dh = 24 has no kernel: declined once the arguments pass)
+    dkv = lambda kv_stride: lib.skg_attn_bwd_dkv(16, 24, 16, 24, 16, 24, 16, 24, 16, 16, 16, 24, 16, 24, 1, 1, 64, 77, kv_stride,
+                                                 24, 1.0, None)
+    assert dkv(72) == -1 and dkv(77) == -2 and dkv(80) == -2
+    # -- both attention-forward flags, or an unknown one, stay a refusal
+    fwd = lambda flags: lib.skg_attn_fwd(16, 8, 16, 8, 16, 8, 16, 8, None, 1, 1, 8, 8, 8, 24, 1.0, flags, None)
+    assert fwd(3) == -1 and fwd(4) == -1 and fwd(1) == -2 and fwd(2) == -2
+    # -- dQ: delta, or O and delta_out
+    dq = lambda O, delta, dout: lib.skg_attn_bwd_dq(16, 24, 16, 24, 16, 24, 16, 24, O, 24, 16, delta, dout, 16, 24, 1, 1, 64, 77, 80,
+                                                    24, 1.0, None)
+    assert dq(None, None, None) == -1 and dq(16, None, None) == -1 and dq(None, None, 16) == -1
+    assert dq(None, 16, None) == -2 and dq(16, None, 16) == -2
+    # -- the non-square LGP calls (h != w: sides that are multiples of 8) are in tests/test_host_nonsquare.py
 
 
 def test_ddim_tables_bit_exact_vs_oracle():

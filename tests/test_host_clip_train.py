@@ -92,11 +92,11 @@ def test_schedule_and_hyperparameters_are_the_sat_trainers():
 def test_new_symbols_are_declared_and_bound():
     from sketch2img_amd import _lib, ops
     src = open(os.path.join(ROOT, "include", "skg.h")).read()
-    assert re.search(r"#define\s+SKG_ABI_VERSION\s+5\b", src)
+    assert re.search(r"#define\s+SKG_ABI_VERSION\s+6\b", src)
     src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
     assert re.search(r"\bskg_quick_gelu_bwd_f16\s*\(", src)
     assert _lib.SIGNATURES["skg_quick_gelu_bwd_f16"] == ("i", "pipipiiip") and hasattr(_lib.lib, "skg_quick_gelu_bwd_f16")
-    assert _lib.ABI_VERSION == 5 and _lib.lib.skg_abi_version() == 5              # additive: the ABI version is unchanged
+    assert _lib.ABI_VERSION == 6 and _lib.lib.skg_abi_version() == 6
     assert callable(ops.quick_gelu_bwd)
     # the embedding fold runs on skg_colsum_f16 over the [B, Lp * D] view: its scratch is sized per column
     assert _lib.lib.skg_colsum_scratch_floats(264 * 1024) >= 264 * 1024

@@ -18,12 +18,12 @@ def _taps(*sides):
 
 def _gather(arr, h, w, Z=P, Wextra=None, H0=128):
     from sketch2img_amd._lib import lib
-    return lib.skg_lgp_layer0_gather_hw(ctypes.addressof(arr), len(arr), Wextra, 0, P, P, 1.0, 1, Z, 2, h, w, H0, None)
+    return lib.skg_lgp_layer0_gather(ctypes.addressof(arr), len(arr), Wextra, 0, P, P, 1.0, 1, Z, 2, h, w, H0, None)
 
 
 def test_rectangular_lgp_entry_points_are_exported():
     from sketch2img_amd import _lib
-    for name in ("skg_lgp_layer0_gather_hw", "skg_lgp_layer0_scatter_hw", "skg_lgp_mse_seed_hw", "skg_lgp_extra_features_hw"):
+    for name in ("skg_lgp_layer0_gather", "skg_lgp_layer0_scatter", "skg_lgp_mse_seed", "skg_lgp_extra_features"):
         assert name in _lib.SIGNATURES and hasattr(_lib.lib, name)
 
 
@@ -37,18 +37,18 @@ def test_rectangular_lgp_entry_points_reject_bad_arguments_without_a_gpu():
     assert _gather(_taps(8), 16, 24, Z=None) == E_BADARG
     assert _gather(_taps(8), 0, 24) == E_BADARG
     # scatter
-    assert lib.skg_lgp_layer0_scatter_hw(P, 128, P, 2, 16, 20, 8, 128, None) == E_BADARG
-    assert lib.skg_lgp_layer0_scatter_hw(P, 128, P, 2, 24, 16, 8, 128, None) == E_BADARG
-    assert lib.skg_lgp_layer0_scatter_hw(None, 128, P, 2, 16, 24, 8, 128, None) == E_BADARG
-    assert lib.skg_lgp_layer0_scatter_hw(P, 128, None, 2, 16, 24, 8, 128, None) == E_BADARG
+    assert lib.skg_lgp_layer0_scatter(P, 128, P, 2, 16, 20, 8, 128, None) == E_BADARG
+    assert lib.skg_lgp_layer0_scatter(P, 128, P, 2, 24, 16, 8, 128, None) == E_BADARG
+    assert lib.skg_lgp_layer0_scatter(None, 128, P, 2, 16, 24, 8, 128, None) == E_BADARG
+    assert lib.skg_lgp_layer0_scatter(P, 128, None, 2, 16, 24, 8, 128, None) == E_BADARG
     # MSE seed
-    assert lib.skg_lgp_mse_seed_hw(P, 8, P, P, 32, P, 1, 16, 12, 1.0, None) == E_BADARG
-    assert lib.skg_lgp_mse_seed_hw(None, 8, P, P, 32, P, 1, 16, 24, 1.0, None) == E_BADARG
-    assert lib.skg_lgp_mse_seed_hw(P, 8, None, P, 32, P, 1, 16, 24, 1.0, None) == E_BADARG
+    assert lib.skg_lgp_mse_seed(P, 8, P, P, 32, P, 1, 16, 12, 1.0, None) == E_BADARG
+    assert lib.skg_lgp_mse_seed(None, 8, P, P, 32, P, 1, 16, 24, 1.0, None) == E_BADARG
+    assert lib.skg_lgp_mse_seed(P, 8, None, P, 32, P, 1, 16, 24, 1.0, None) == E_BADARG
     # extra features
-    assert lib.skg_lgp_extra_features_hw(P, 1.0, 1, 2, 20, 16, P, 64, None) == E_BADARG
-    assert lib.skg_lgp_extra_features_hw(None, 1.0, 1, 2, 16, 24, P, 64, None) == E_BADARG
-    assert lib.skg_lgp_extra_features_hw(P, 1.0, 1, 2, 16, 24, None, 64, None) == E_BADARG
+    assert lib.skg_lgp_extra_features(P, 1.0, 1, 2, 20, 16, P, 64, None) == E_BADARG
+    assert lib.skg_lgp_extra_features(None, 1.0, 1, 2, 16, 24, P, 64, None) == E_BADARG
+    assert lib.skg_lgp_extra_features(P, 1.0, 1, 2, 16, 24, None, 64, None) == E_BADARG
 
 
 def test_image_size_rule():

@@ -39,7 +39,7 @@ for B, H, N, d in ((16, 8, 4096, 40), (16, 8, 1024, 80), (8, 5, 9216, 64)):
     from sketch2img_amd._lib import lib, check
     def run(Q, K, with_lse):
         check(lib.skg_attn_fwd(Q.data_ptr(), Q.stride(0), K.data_ptr(), K.stride(0), vt.data_ptr(), vt.stride(0), out.data_ptr(),
-                               out.stride(0), lse.data_ptr() if with_lse else None, B, H, N, N, N, d, sc,
+                               out.stride(0), lse.data_ptr() if with_lse else None, B, H, N, N, N, d, sc, 0,
                                torch.cuda.current_stream().cuda_stream), "attn")
     for name, Q, K, wl in (("q,k slices of qkv (ld 3C), lse", q, k, True), ("q,k slices of qkv (ld 3C)", q, k, False),
                            ("q slice, k contiguous", q, kc, False), ("q,k contiguous (ld C)", qc, kc, False),

@@ -52,7 +52,7 @@ def gn_fused(x, rows, hw, G, eps, g, b, silu, y):
     """skg_groupnorm_fwd (partial + apply that folds the partials) regardless of the HW threshold in ops.groupnorm"""
     from sketch2img_amd._lib import lib, check
     st = torch.empty(rows, G, 2, device=x.device, dtype=torch.float32)
-    check(lib.skg_groupnorm_fwd(x.data_ptr(), x.stride(0), y.data_ptr(), y.stride(0), rows, hw, x.shape[1], G, eps,
+    check(lib.skg_groupnorm_fwd(x.data_ptr(), None, x.stride(0), y.data_ptr(), None, y.stride(0), rows, hw, x.shape[1], G, eps,
                                 g.data_ptr(), b.data_ptr(), int(silu), st.data_ptr(),
                                 ops._gn_scratch(rows, G, x.device).data_ptr(), torch.cuda.current_stream().cuda_stream), "gn")
     return st

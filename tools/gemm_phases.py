@@ -14,9 +14,9 @@ import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 L = ctypes.CDLL(os.path.join(ROOT, "sketch2img_amd", "libskg_phases.so"))
-L.skg_gemm_f16.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_int,
-                           ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int,
-                           ctypes.c_float, ctypes.c_uint, ctypes.c_void_p]
+L.skg_gemm_f16.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int,
+                           ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int,
+                           ctypes.c_float, ctypes.c_uint, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p]
 READ = L.skg_debug_phases
 READ.argtypes = [ctypes.c_void_p, ctypes.c_int]
 
@@ -31,13 +31,13 @@ def run(M, N, K, flags=0, res=False):
     rp, rld = (r.data_ptr(), N) if res else (None, 0)
     st = torch.cuda.current_stream().cuda_stream
     for _ in range(3):
-        rc = L.skg_gemm_f16(a.data_ptr(), K, w.data_ptr(), K, out.data_ptr(), N, M, N, K, b.data_ptr(), rp, rld, 1.0,
-                            flags, st)
+        rc = L.skg_gemm_f16(a.data_ptr(), K, w.data_ptr(), K, out.data_ptr(), None, N, M, N, K, b.data_ptr(), rp, None, rld, 1.0,
+                            flags, None, 0, 0, st)
         assert rc == 0, rc
     torch.cuda.synchronize()
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     e0.record()
-    L.skg_gemm_f16(a.data_ptr(), K, w.data_ptr(), K, out.data_ptr(), N, M, N, K, b.data_ptr(), rp, rld, 1.0, flags, st)
+    L.skg_gemm_f16(a.data_ptr(), K, w.data_ptr(), K, out.data_ptr(), None, N, M, N, K, b.data_ptr(), rp, None, rld, 1.0, flags, None, 0, 0, st)
     e1.record()
     torch.cuda.synchronize()
     us = e0.elapsed_time(e1) * 1e3

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """One guided UNet evaluation of config 0's shape (SD1.5, 1 sample, 32 x 32 latents) twice: with the per-operator cross-attention
-launches in the stashing forward (SKG_XATTN_KEEP=0) and with skg_xattn_block_f16_keep; compares eps, taps and every stash entry."""
+launches in the stashing forward (SKG_XATTN_KEEP=0) and with the stashing skg_xattn_block_f16; compares eps, taps and every stash entry."""
 import os
 import sys
 
