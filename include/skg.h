@@ -299,6 +299,12 @@ int skg_geglu_bwd(const void* H, int ldh, const void* dY, int lddy, void* dH, in
  * Nkv of each batch row's kv_stride key slots are valid.  O [batch*Nq][..] (ldo).
  * lse (float [batch][heads][Nq], natural-log-sum-exp of the scaled scores) may be NULL.
  * dh in {16, 32, 40, 64, 80, 160}; kv_stride % 8 == 0 (the V^T operand; SKG_ATTN_ROWV takes any kv_stride).
+ * Pad key slots (all four attention entry points): the slots Nkv .. kv_stride - 1 of every batch row ARE READ - skg_attn_fwd and
+ * skg_attn_bwd_dq stage whole 64-key tiles of up to kv_stride rows and only mask the scores - and must hold FINITE values (zeros, or
+ * whatever finite numbers a projection of padded token rows left there); the results do not depend on them, bit for bit
+ * (tests/test_gpu_attention_bwd.py).  An Inf or NaN there reaches the output as 0 * Inf.  K and V (V^T: every row) must therefore
+ * have batch * kv_stride readable rows (columns) for skg_attn_fwd and skg_attn_bwd_dq; skg_attn_bwd_dkv touches only the first Nkv
+ * rows of every batch row of K, V, dK and dV.
  * Replaces: xformers memory_efficient_attention (enabled at app.py:43) / diffusers
  * CrossAttention baddbmm+softmax+bmm for attn1, attn2 and the injected sketch_attn
  * (modules/clip_guided_attn.py:114, modules/sketch_guided_attn.py:127).
