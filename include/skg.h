@@ -308,16 +308,24 @@ int skg_geglu_bwd(const void* H, int ldh, const void* dY, int lddy, void* dH, in
  * Replaces: xformers memory_efficient_attention (enabled at app.py:43) / diffusers
  * CrossAttention baddbmm+softmax+bmm for attn1, attn2 and the injected sketch_attn
  * (modules/clip_guided_attn.py:114, modules/sketch_guided_attn.py:127).
- * flags (at most one of the two; both: SKG_E_BADARG):
+ * flags (SKG_ATTN_ROWV and SKG_ATTN_CAUSAL exclude each other: SKG_E_BADARG):
  *   SKG_ATTN_ROWV    Vt / ldvt are V handed over ROW-MAJOR: V [batch*kv_stride][ldv], head h at columns h*dh.. (e.g. the third
  *                    column block of a fused QKV projection, ldv = 3C).  The kernel reads its V fragments through the gfx950 LDS
  *                    transpose read (ds_read_b64_tr_b16), so no transposed copy of V is written.
  *   SKG_ATTN_CAUSAL  key j of a batch row is visible to query i only when j <= i (self-attention, Nq rows and kv_stride key
  *                    slots per batch row).  dh in {16, 32, 64}.  Replaces: the masked self-attention of transformers'
  *                    CLIPTextModel, which the reference calls through StableDiffusionPipeline._encode_prompt
- *                    (modules/pipeline.py:55-57). */
+ *                    (modules/pipeline.py:55-57).
+ *   SKG_ATTN_RESIDENT_KV  (only with SKG_ATTN_ROWV, otherwise SKG_E_BADARG) a hint for cross-attention over 81 ... 240 key slots
+ *                    (long prompts: clip_text.encode_tokens): K and V of one (batch row, head) are staged in LDS once per workgroup
+ *                    and the softmax is a plain one with the exact maximum, as for kv_stride <= 80 - instead of the streaming
+ *                    kernel.  Served: dh 40 / 64 / 80 up to kv_stride 240, dh 160 up to 160; every other call (kv_stride <= 80
+ *                    or > 240, other head widths, SKG_NO_ATTN_SHORT set) runs exactly as without the flag.  The results differ
+ *                    from the streaming kernel's in the last bits, which is why self-attention callers with 81 ... 240 keys
+ *                    (small or non-square maps) do not get it implicitly. */
 #define SKG_ATTN_CAUSAL 1u
 #define SKG_ATTN_ROWV 2u
+#define SKG_ATTN_RESIDENT_KV 4u
 int skg_attn_fwd(const void* Q, int ldq, const void* K, int ldk, const void* Vt, int ldvt,
                  void* O, int ldo, float* lse, int batch, int heads, int Nq, int Nkv,
                  int kv_stride, int dh, float scale, unsigned flags, void* stream);

@@ -1,4 +1,4 @@
-"""CLIP text encoder on the libskg.so kernels: prompts -> the (B, 77, D) conditioning the UNet cross-attends to.
+"""CLIP text encoder on the libskg.so kernels: prompts -> the (B, L, D) conditioning the UNet cross-attends to.
 
 Replaces ``self.text_encoder(text_input_ids)[0]`` inside StableDiffusionPipeline._encode_prompt, which the reference
 calls at modules/pipeline.py:55-57 (third-party transformers CLIPTextModel; restated and PINNED against transformers'
@@ -10,6 +10,12 @@ The token-embedding row gather is data movement (torch.index_select on the fp16 
 the causal softmax(QK^T)V is the flash kernel's CAUSAL instantiation (skg_attn_fwd with SKG_ATTN_CAUSAL), out-proj / fc2 carry the
 residual in the GEMM epilogue, quick_gelu (SD 1.x) or exact gelu (SD 2.x) and LayerNorm are their own kernels.
 Tokenisation (BPE) is host-side text processing and stays with transformers' CLIPTokenizer (`PromptEncoder`).
+
+Long prompts (`encode_tokens`, the reference's modules/clip_guided_trainer.py:40-66 fed by modules/dataset.py:114-123 and
+:204-211): an id matrix wider than 77 is cut into 75-token windows, each wrapped in BOS / EOS and encoded on its own, and the
+hidden states are concatenated along the sequence axis: L = width + 2 * windows keys, 78 ... 231 for the reference's
+max_length = 225.  All windows of a batch go through the layer stack in ONE pass, as (windows * B) rows of 77 tokens: the encoder
+is causal and row-local, so the shorter last window rides along padded behind its EOS and its pad rows are dropped.
 """
 from __future__ import annotations
 
@@ -110,26 +116,76 @@ class CLIPTextModel(CLIPFacade):
         return _TextOutput(self.engine().last_hidden_state(input_ids))
 
 
-class PromptEncoder:
-    """``(list[str]) -> (B, 77, D)``: the tokenizer + text-encoder half of diffusers' _encode_prompt
-    (modules/pipeline.py:55-57): pad to ``model_max_length`` with truncation, then ``text_encoder(ids)[0]``.
-    ``tokenizer`` is any callable with transformers' tokenizer call convention (CLIPTokenizer in practice)."""
+WINDOW = 75          # tokens of the prompt per window; with BOS and EOS a window is the encoder's 77 positions
 
-    def __init__(self, tokenizer, text_model: CLIPTextModel):
+
+def split_windows(input_ids, bos_token_id: int, eos_token_id: int) -> List[torch.Tensor]:
+    """The id matrices `encode_tokens` encodes, in order (host only).  input_ids int [B, W]: W <= 77 is taken as is; otherwise
+    consecutive windows of 75 columns of the RAW ids - the prompt's own BOS / EOS and the collate padding stay inside - each as
+    [BOS, window, EOS]; the last window is as short as what is left, so the widths sum to W + 2 * windows."""
+    ids = torch.as_tensor(input_ids)
+    if ids.dim() != 2:
+        raise ValueError(f"encode_tokens: input_ids must be [B, W], got {tuple(ids.shape)}")
+    B, W = ids.shape
+    if W <= WINDOW + 2:
+        return [ids]
+    ids = ids.to(torch.long)
+    bos = torch.full((B, 1), bos_token_id, dtype=torch.long, device=ids.device)
+    eos = torch.full((B, 1), eos_token_id, dtype=torch.long, device=ids.device)
+    return [torch.cat([bos, ids[:, c:c + WINDOW], eos], 1) for c in range(0, W, WINDOW)]
+
+
+def encode_tokens(tokenizer, text_encoder, input_ids) -> torch.Tensor:
+    """modules/clip_guided_trainer.py:40-66 on the HIP text encoder: int [B, W] -> fp16 [B, L, D], L = W (W <= 77) or
+    W + 2 * ceil(W / 75).  Of ``tokenizer`` only ``bos_token_id`` / ``eos_token_id`` are read; ``text_encoder`` is the
+    `CLIPTextModel` facade.  One pass through the layer stack for all windows (see the module docstring)."""
+    wins = split_windows(input_ids, tokenizer.bos_token_id, tokenizer.eos_token_id)
+    if len(wins) == 1:
+        return text_encoder(wins[0])[0]
+    B, full = wins[0].shape
+    last = wins[-1]
+    if last.shape[1] < full:      # pad rows behind the window's EOS: causal attention keeps them out of the rows in front
+        pad = torch.full((B, full - last.shape[1]), tokenizer.eos_token_id, dtype=last.dtype, device=last.device)
+        last = torch.cat([last, pad], 1)
+    h = text_encoder(torch.cat(wins[:-1] + [last], 0))[0]
+    return torch.cat([h[i * B:(i + 1) * B, :w.shape[1]] for i, w in enumerate(wins)], 1)
+
+
+class PromptEncoder:
+    """``(list[str]) -> (B, L, D)``: the tokenizer + text-encoder half of diffusers' _encode_prompt
+    (modules/pipeline.py:55-57): pad to ``model_max_length`` with truncation, then ``text_encoder(ids)[0]`` (L = 77).
+    ``tokenizer`` is any callable with transformers' tokenizer call convention (CLIPTokenizer in practice).
+
+    ``max_length`` (an integer; 225 is the reference trainer's) selects the long-prompt path instead: tokenise without padding
+    and truncate at ``max_length`` (modules/dataset.py:114-123), pad the batch to its longest prompt with ``tokenizer.pad``
+    (``collate_fn``, :204-211), then `encode_tokens`: L = W (W <= 77) or W + 2 * ceil(W / 75) for the padded width W, up to
+    231.  All prompts of one call share one L."""
+
+    def __init__(self, tokenizer, text_model: CLIPTextModel, max_length: Optional[int] = None):
+        if max_length is not None and int(max_length) < 1:
+            raise ValueError(f"PromptEncoder: max_length must be positive, got {max_length}")
         self.tokenizer, self.text_model = tokenizer, text_model
+        self.max_length = None if max_length is None else int(max_length)
 
     @classmethod
-    def from_pretrained(cls, folder: str):
+    def from_pretrained(cls, folder: str, max_length: Optional[int] = None):
         """``folder`` is a diffusers checkpoint directory with ``tokenizer/`` and ``text_encoder/`` inside."""
         from transformers import CLIPTokenizer          # BPE tables + host-side string processing only
         tok = CLIPTokenizer.from_pretrained(os.path.join(folder, "tokenizer"))
-        return cls(tok, CLIPTextModel.from_pretrained(folder, subfolder="text_encoder"))
+        return cls(tok, CLIPTextModel.from_pretrained(folder, subfolder="text_encoder"), max_length)
 
     def to(self, device):
         self.text_model.to(device)
         return self
 
+    def tokenize(self, prompts: List[str]) -> torch.Tensor:
+        """The long-prompt id matrix int [B, W] (``max_length`` set): unpadded truncated ids, padded to the longest."""
+        ids = self.tokenizer(list(prompts), padding="do_not_pad", truncation=True, max_length=self.max_length)["input_ids"]
+        return torch.as_tensor(self.tokenizer.pad({"input_ids": ids}, padding=True, return_tensors="pt")["input_ids"])
+
     def __call__(self, prompts: List[str]) -> torch.Tensor:
+        if self.max_length is not None:
+            return encode_tokens(self.tokenizer, self.text_model, self.tokenize(prompts))
         L = getattr(self.tokenizer, "model_max_length", None) or self.text_model.cfg.max_position_embeddings
         L = min(L, self.text_model.cfg.max_position_embeddings)
         enc = self.tokenizer(list(prompts), padding="max_length", max_length=L, truncation=True, return_tensors="pt")

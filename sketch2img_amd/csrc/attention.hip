@@ -544,10 +544,21 @@ __global__ __launch_bounds__(256, ((VAR >> 2) ? (VAR >> 2) : KS >= 5 ? 1 : (KS =
 // plain softmax over the wave's 20 scores per lane (the maximum is exact: no running reference), O^T = V^T P^T with the
 // probabilities as the B operand out of the accumulator registers, normalise, store.  What is left is one read of Q and one
 // write of O: the kernel is HBM-bound.
-template <int KS, int ND>
-__global__ __launch_bounds__(256, (KS >= 5 ? 2 : (KS >= 3 ? 3 : 4))) void attn_fwd_short_kernel(const AttnParams p, int qchunk) {
-  constexpr int NT = 5;                 // 16-key score tiles: kv_stride <= 80
-  constexpr int NSV = 3;                // 32-key k-steps of the PV product (the last half step is zero rows)
+//
+// Long prompts (clip_text.encode_tokens: 75-token windows, 78 ... 231 keys; SKG_ATTN_RESIDENT_KV): K and V of one (row, head) still
+// fit in LDS, so NT - the number of 16-key score tiles - is a template parameter: 5 (<= 80 keys, the kernel as it always was, the
+// same instruction stream), 10 (<= 160) and 15 (<= 240).  The LDS image 2 (16 NT KP + 32 NSV VP) bytes bounds the workgroups per
+// CU (163 840 bytes): NT = 10: d = 40 40 960 (4), d = 64 51 200 (3), d = 80 61 440 (2), d = 160 112 640 (1); NT = 15: 62 976 (2),
+// 79 360 (2), 94 720 (1), d = 160 174 592 - does not fit, not built.  A lane holds 4 NT scores of one query, so the softmax stays
+// in-lane plus two shuffles; any tile may be ragged or dead (Lp is a multiple of 8, not of 16: 231 keys -> 232 slots).
+// Measured (profiles/attn_resident_kv.txt): unlike at 77 keys this does NOT beat the streaming kernel - every 16-query tile of a wave
+// reads the whole K / V image from LDS (54 KB at d = 40, 231 keys) where attn_fwd_kernel shares each fragment between 2-3 query
+// tiles, at 1-2 waves per SIMD instead of 3-4 - so unet.py does not ask for it; it stays built and tested behind the flag.
+constexpr int short_min_blocks(int KS, int NT) { return NT > 5 ? (KS >= 5 || (KS >= 3 && NT > 10) ? 1 : 2) : (KS >= 5 ? 2 : (KS >= 3 ? 3 : 4)); }
+template <int KS, int ND, int NT = 5>
+__global__ __launch_bounds__(256, short_min_blocks(KS, NT)) void attn_fwd_short_kernel(const AttnParams p, int qchunk) {
+  // NT 16-key score tiles: kv_stride <= 16 NT
+  constexpr int NSV = (NT + 1) / 2;     // 32-key k-steps of the PV product (odd NT: the last half step is zero rows)
   constexpr int KP = KS * 32 + 16;
   constexpr int VP = vrow_pitch(ND);
   __shared__ __attribute__((aligned(16))) half_t Ks[16 * NT * KP];
@@ -572,9 +583,12 @@ __global__ __launch_bounds__(256, (KS >= 5 ? 2 : (KS >= 3 ? 3 : 4))) void attn_f
   const float sc = p.scale * LOG2E;
   // keys this lane holds in score tile t, register r: 16 t + 4 g + r.  77 text tokens: only the last tile is ragged
   // (three registers of the g = 3 lanes); fewer than 65 keys (tests, other callers) take the general mask
+  // NT > 5 (any key count up to 16 NT): tile rag = Nkv / 16 is the ragged one, the tiles behind it are dead as a whole - four
+  // lane masks and wave-uniform tile tests (a mask per (tile, register) is 120 SGPRs at NT = 15: they spilled)
+  const int rag = NT == 5 ? NT - 1 : p.Nkv >> 4;
   bool dead[4];
 #pragma unroll
-  for (int r = 0; r < 4; ++r) dead[r] = 16 * (NT - 1) + 4 * g + r >= p.Nkv;
+  for (int r = 0; r < 4; ++r) dead[r] = 16 * rag + 4 * g + r >= p.Nkv;
   const bool short_rows = p.Nkv <= 16 * (NT - 1);        // wave-uniform
   const int klim = p.Nkv - 4 * g;
   const int q_begin = bm.bx * qchunk, q_end = min(p.Nq, q_begin + qchunk);
@@ -616,18 +630,33 @@ __global__ __launch_bounds__(256, (KS >= 5 ? 2 : (KS >= 3 ? 3 : 4))) void attn_f
       }
 #pragma unroll
     for (int r = 0; r < 4; ++r)
-      if (dead[r]) s[NT - 1][r] = NEG_BIG;
-    if (short_rows) {
+      if (NT == 5 && dead[r]) s[NT - 1][r] = NEG_BIG;
+    if (NT == 5 && short_rows) {
 #pragma unroll
       for (int t = 0; t < NT - 1; ++t)
 #pragma unroll
         for (int r = 0; r < 4; ++r)
           if (16 * t + r >= klim) s[t][r] = NEG_BIG;
     }
+    if (NT > 5) {      // key 16 t + 4 g + r >= Nkv, every tile
+      int ragl = rag;      // (opaque: the 2 NT tile tests are redone per query tile instead of living in SGPRs across the loop)
+      asm volatile("" : "+s"(ragl));
+#pragma unroll
+      for (int t = 0; t < NT; ++t) {
+        if (t == ragl) {
+#pragma unroll
+          for (int r = 0; r < 4; ++r)
+            if (dead[r]) s[t][r] = NEG_BIG;
+        } else if (t > ragl) {
+          s[t] = float4_t{NEG_BIG, NEG_BIG, NEG_BIG, NEG_BIG};
+        }
+      }
+    }
+    // the lane's maximum over its 4 NT scores: the first two by themselves, then two more per v_max3
     float mx = max3f(s[0][0], s[0][1], s[0][2]);
-    mx = max3f(mx, s[0][3], s[1][0]); mx = max3f(mx, s[1][1], s[1][2]); mx = max3f(mx, s[1][3], s[2][0]);
-    mx = max3f(mx, s[2][1], s[2][2]); mx = max3f(mx, s[2][3], s[3][0]); mx = max3f(mx, s[3][1], s[3][2]);
-    mx = max3f(mx, s[3][3], s[4][0]); mx = max3f(mx, s[4][1], s[4][2]); mx = max3f(mx, s[4][3], mx);
+#pragma unroll
+    for (int j = 3; j + 1 < 4 * NT; j += 2) mx = max3f(mx, s[j >> 2][j & 3], s[(j + 1) >> 2][(j + 1) & 3]);
+    mx = max3f(mx, s[NT - 1][3], mx);
     mx = max3f(mx, __shfl_xor(mx, 16, 64), mx);
     mx = max3f(mx, __shfl_xor(mx, 32, 64), mx);
     float li = 0.f;
@@ -1474,8 +1503,8 @@ inline bool common_ok(int batch, int heads, int Nq, int Nkv, int kv_stride, int 
 extern "C" int skg_attn_fwd(const void* Q, int ldq, const void* K, int ldk, const void* Vt, int ldvt, void* O,
                             int ldo, float* lse, int batch, int heads, int Nq, int Nkv, int kv_stride, int dh,
                             float scale, unsigned flags, void* stream) {
-  const bool causal = flags & SKG_ATTN_CAUSAL, vrow = flags & SKG_ATTN_ROWV;
-  SKG_REQUIRE(!(flags & ~(SKG_ATTN_CAUSAL | SKG_ATTN_ROWV)) && !(causal && vrow));
+  const bool causal = flags & SKG_ATTN_CAUSAL, vrow = flags & SKG_ATTN_ROWV, resident = flags & SKG_ATTN_RESIDENT_KV;
+  SKG_REQUIRE(!(flags & ~(SKG_ATTN_CAUSAL | SKG_ATTN_ROWV | SKG_ATTN_RESIDENT_KV)) && !(causal && vrow) && (!resident || vrow));
   SKG_REQUIRE(Q && K && Vt && O && common_ok(batch, heads, Nq, Nkv, kv_stride, dh, !vrow));
   SKG_REQUIRE(ldq % 8 == 0 && ldk % 8 == 0 && ldvt % 8 == 0 && ldo % 4 == 0);
   SKG_REQUIRE(skg_aligned(Q, 16) && skg_aligned(K, 16) && skg_aligned(Vt, 16) && skg_aligned(O, 8));
@@ -1499,6 +1528,32 @@ extern "C" int skg_attn_fwd(const void* Q, int ldq, const void* K, int ldk, cons
       default: hipLaunchKernelGGL((attn_fwd_short_kernel<5, 10>), gs, dim3(256), 0, st, p, (int)qch); break;
     }
     SKG_CHECK_LAUNCH("skg_attn_fwd (short keys)");
+    return SKG_OK;
+  }
+  // SKG_ATTN_RESIDENT_KV (a hint: cross-attention over a long prompt's 81 ... 240 keys): the same kernel with 10 / 15 score tiles
+  // where K and V of one (row, head) fit the 160 KB of LDS - not d = 160 above 160 keys; everything else runs as without the flag
+  const int rtiles = kv_stride <= 160 ? 10 : 15;
+  if (resident && kv_stride > 80 && kv_stride <= 240 && !no_short && (dh == 40 || dh == 64 || dh == 80 || (dh == 160 && rtiles == 10))) {
+    // one staging pass of up to 240 K / V rows per workgroup: at least 128 queries behind it where the launch has them
+    long qch = ((long)heads * batch * Nq / 1024 + 63) / 64 * 64;
+    qch = qch < 128 ? 128 : (qch > 512 ? 512 : qch);
+    p.nx = skg_cdiv(Nq, (int)qch);
+    dim3 gs((unsigned)p.nx * heads * batch);
+    if (rtiles == 10) {
+      switch (dh) {
+        case 40: hipLaunchKernelGGL((attn_fwd_short_kernel<2, 3, 10>), gs, dim3(256), 0, st, p, (int)qch); break;
+        case 64: hipLaunchKernelGGL((attn_fwd_short_kernel<2, 4, 10>), gs, dim3(256), 0, st, p, (int)qch); break;
+        case 80: hipLaunchKernelGGL((attn_fwd_short_kernel<3, 5, 10>), gs, dim3(256), 0, st, p, (int)qch); break;
+        default: hipLaunchKernelGGL((attn_fwd_short_kernel<5, 10, 10>), gs, dim3(256), 0, st, p, (int)qch); break;
+      }
+    } else {
+      switch (dh) {
+        case 40: hipLaunchKernelGGL((attn_fwd_short_kernel<2, 3, 15>), gs, dim3(256), 0, st, p, (int)qch); break;
+        case 64: hipLaunchKernelGGL((attn_fwd_short_kernel<2, 4, 15>), gs, dim3(256), 0, st, p, (int)qch); break;
+        default: hipLaunchKernelGGL((attn_fwd_short_kernel<3, 5, 15>), gs, dim3(256), 0, st, p, (int)qch); break;
+      }
+    }
+    SKG_CHECK_LAUNCH("skg_attn_fwd (resident keys)");
     return SKG_OK;
   }
 #if defined(SKG_LAB) || defined(SKG_PHASES)

@@ -9,7 +9,7 @@ UNet, the LGP and the guidance gradient run in libskg.so; there is no diffusers 
 Around the hot path:
   * ``vae``          ``sketch2img_amd.vae.AutoencoderKL`` decodes / encodes on the HIP kernels; any other object with
                      ``decode(latents) -> tensor | .sample`` (and ``encode`` for app.py:109) is used as a PyTorch module;
-  * ``text_encoder`` a callable ``(list[str]) -> (B, 77, D) tensor`` - ``sketch2img_amd.clip_text.PromptEncoder``
+  * ``text_encoder`` a callable ``(list[str]) -> (B, L, D) tensor`` - ``sketch2img_amd.clip_text.PromptEncoder``
                      (CLIP tokenizer + the text transformer on the HIP kernels) is picked up automatically when the
                      checkpoint folder has ``tokenizer/`` and ``text_encoder/``.  Seeded pseudo-embeddings
                      (deterministic in the prompt text) and seeded synthetic UNet weights exist for boxes without
@@ -211,7 +211,7 @@ class AntiGradientPipeline:
     @classmethod
     def from_pretrained(cls, pretrained_model_name_or_path=None, vae=None, torch_dtype=None, scheduler=None,
                         text_encoder=None, unet_config: Optional[UNetConfig] = None, synthetic: bool = False,
-                        residual_fp32: bool = False, **kwargs):
+                        residual_fp32: bool = False, max_prompt_length: Optional[int] = None, **kwargs):
         """``pretrained_model_name_or_path``: a local diffusers-layout folder (``unet/``, optionally ``tokenizer/`` +
         ``text_encoder/``).  ``None`` or ``synthetic=True`` is the explicit opt-in to seeded synthetic UNet weights and
         seeded pseudo text embeddings (boxes without checkpoints, tests, bench.py); any other path that does not
@@ -221,7 +221,10 @@ class AntiGradientPipeline:
         numbers passes to the reference, app.py:34 being ``torch.float16``): the UNet keeps its residual stream and the
         convolution outputs that feed a norm as (hi, lo) fp16 pairs - max eps deviation from the fp32 reference <= 1e-3
         (north_star's bound; the all-fp16 default, like the reference's own fp16 GPU path, is ~1.7e-3 away).  Works with
-        ``setup_lgp`` guidance and with both SatMixin injections."""
+        ``setup_lgp`` guidance and with both SatMixin injections.
+
+        ``max_prompt_length`` (225 is the reference trainer's) goes to the ``PromptEncoder`` picked up from the folder: prompts
+        longer than 77 tokens are encoded in 75-token windows (``clip_text.encode_tokens``) instead of being cut."""
         if torch_dtype == torch.float32 and not residual_fp32:
             # NOT fp32 compute: the reference's torch_dtype=float32 means an fp32 model; here it selects the (hi, lo) fp16-pair mode
             # (~12 % slower than fp16, eps within 1e-3 of the fp32 reference) - say so once instead of mapping silently (ADVICE r4)
@@ -236,7 +239,7 @@ class AntiGradientPipeline:
         if text_encoder is None and root and os.path.isdir(os.path.join(root, "tokenizer")) \
                 and os.path.isdir(os.path.join(root, "text_encoder")):
             from ..clip_text import PromptEncoder
-            text_encoder = PromptEncoder.from_pretrained(root)
+            text_encoder = PromptEncoder.from_pretrained(root, max_length=max_prompt_length)
         return cls(UNetFacade(cfg, sd, "cpu", residual_fp32=residual_fp32), vae=vae, scheduler=scheduler,
                    text_encoder=text_encoder, allow_pseudo_text=synthetic)
 
@@ -280,9 +283,13 @@ class AntiGradientPipeline:
             raise ValueError("`negative_prompt` and `prompt` must have the same batch size")
         if self.text_encoder is None and not self.allow_pseudo_text:
             raise RuntimeError("AntiGradientPipeline: no text encoder - the checkpoint folder has no tokenizer/ + "
-                               "text_encoder/; pass text_encoder=<callable (list[str]) -> (B, 77, D)>, or build the "
+                               "text_encoder/; pass text_encoder=<callable (list[str]) -> (B, L, D)>, or build the "
                                "pipeline with synthetic=True to get seeded pseudo embeddings")
         enc = self.text_encoder or self._pseudo_text_encoder
+        if do_classifier_free_guidance and getattr(enc, "max_length", None) is not None:
+            # long prompts: the key count follows the longest prompt of a call, and both CFG halves need the same one
+            both = enc(negs + prompts).repeat_interleave(num_images_per_prompt, 0)
+            return both
         cond = enc(prompts).repeat_interleave(num_images_per_prompt, 0)
         if not do_classifier_free_guidance:
             return cond

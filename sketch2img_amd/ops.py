@@ -16,7 +16,7 @@ from ._lib import SkgError, SkgTap, check, lib
 
 EPI_RELU, EPI_OUT_F32, EPI_GEGLU = 1, 2, 4
 CONV_S1, CONV_S2, CONV_UP2, CONV_S2T, CONV_S2A = 0, 1, 2, 3, 4
-ATTN_CAUSAL, ATTN_ROWV = 1, 2
+ATTN_CAUSAL, ATTN_ROWV, ATTN_RESIDENT_KV = 1, 2, 4
 
 
 _workspace = {}
@@ -695,15 +695,17 @@ def nhwc_to_nchw(X, rows: int, C: int, H: int, W: int):
 
 
 def attn_fwd(Q, K, Vt, batch, heads, Nq, Nkv, kv_stride, dh, scale, out=None, want_lse=False, causal=False,
-             v_rows=False):
-    """v_rows=True: `Vt` is the row-major V ([batch*kv_stride, heads*dh] view, any row pitch) instead of its transpose."""
+             v_rows=False, resident_kv=False):
+    """v_rows=True: `Vt` is the row-major V ([batch*kv_stride, heads*dh] view, any row pitch) instead of its transpose.
+    resident_kv=True (needs v_rows): SKG_ATTN_RESIDENT_KV, the LDS-resident kernel for 81 ... 240 key slots where it is built -
+    a hint, every other call runs as without it."""
     _f16(Q, K, Vt)
-    assert not (causal and v_rows)
+    assert not (causal and v_rows) and (v_rows or not resident_kv)
     if out is None:
         out = torch.empty(batch * Nq, heads * dh, device=Q.device, dtype=torch.float16)
     lse = torch.empty(batch, heads, Nq, device=Q.device, dtype=torch.float32) if want_lse else None
     check(lib.skg_attn_fwd(_p(Q), _ld(Q), _p(K), _ld(K), _p(Vt), _ld(Vt), _p(out), _ld(out), _p(lse), batch,
-                           heads, Nq, Nkv, kv_stride, dh, scale, (ATTN_CAUSAL if causal else 0) | (ATTN_ROWV if v_rows else 0),
+                           heads, Nq, Nkv, kv_stride, dh, scale, (ATTN_CAUSAL if causal else 0) | (ATTN_ROWV if v_rows else 0) | (ATTN_RESIDENT_KV if resident_kv else 0),
                            _stream()), "skg_attn_fwd")
     return (out, lse) if want_lse else out
 

@@ -37,6 +37,7 @@ from typing import Dict, Optional, Sequence, Tuple
 import torch
 
 from . import lgp_train, ops
+from .clip_text import encode_tokens  # noqa: F401 (re-exported: the trainer's long-prompt encoding, clip_guided_trainer.py:40-66)
 from .config import UNetConfig
 from .flat_adamw import FlatAdamW, cosine_with_restarts  # noqa: F401 (cosine_with_restarts is re-exported)
 from .inject import CLIP_DIM, HipClipInjectorTrain, block_dims, module_name
@@ -97,7 +98,7 @@ class HipSatTrainer(FlatAdamW):
     @torch.no_grad()
     def loss_and_grads(self, net, latents: torch.Tensor, noise: torch.Tensor, timesteps: Sequence[int], ehs: torch.Tensor,
                        sketch_state: torch.Tensor, alphas_cumprod: torch.Tensor, loss_scale: float = LOSS_SCALE):
-        """latents, noise fp32 [B, 4, h, h]; timesteps: B ints; ehs [B, 77, D]; sketch_state [B, T, 1024].
+        """latents, noise fp32 [B, 4, h, h]; timesteps: B ints; ehs [B, L, D] (L = 77, or 78 ... 231 from encode_tokens); sketch_state [B, T, 1024].
         loss_scale: a power of two (step() divides by LOSS_SCALE: leave the default unless the caller rescales itself).
         Returns (loss, flat fp32 gradient x LOSS_SCALE in the layout of the master vector, d loss / d sketch_state x LOSS_SCALE
         fp32 [B, T, 1024])."""

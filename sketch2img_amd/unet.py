@@ -37,6 +37,12 @@ _FF_BLOCK = os.environ.get("SKG_FF_BLOCK", "1") != "0"              # fused feed
 _XATTN_BLOCK = os.environ.get("SKG_XATTN_BLOCK", "1") != "0"        # fused cross-attention sub-block at C = 320, 8 heads (csrc/xattn.hip)
 _FF_KEEP = os.environ.get("SKG_FF_KEEP", "1") != "0"                # ... also in a guided step (stashing launch; 0 = all rows unfused there)
 _XATTN_HEADS = (8,) if os.environ.get("SKG_XATTN_D64", "1") == "0" else (8, 5)     # head counts of the fused cross-attention launch at C = 320 (5 x 64: round 5)
+# (head width, 16-key score tiles) pairs whose cross-attention over a long prompt (80 < Lp <= 240 key slots) asks for the LDS-resident
+# forward (SKG_ATTN_RESIDENT_KV): the pairs that beat the streaming kernel by more than the run-to-run spread at both batch sizes of
+# profiles/attn_resident_kv.txt - none did (EXPERIMENTS.md, long prompts), so the default is empty; SKG_RESIDENT_KV=1 routes every
+# built pair (A/B runs)
+_RESIDENT_KV_BUILT = frozenset({(40, 10), (40, 15), (64, 10), (64, 15), (80, 10), (80, 15), (160, 10)})
+_RESIDENT_KV = _RESIDENT_KV_BUILT if os.environ.get("SKG_RESIDENT_KV", "0") == "1" else frozenset()
 _XATTN_KEEP = os.environ.get("SKG_XATTN_KEEP", "1") != "0"          # the fused cross-attention launch also in guided steps (stashing launch)
 _XATTN_KEEP_HP = os.environ.get("SKG_XATTN_KEEP_HP", "1") != "0"    # ... and in the accuracy mode's guided steps (pairs)
 _FF_PROJ = os.environ.get("SKG_FF_PROJ", "1") != "0"                # proj_out + outer residual inside the fused feed-forward launch
@@ -714,8 +720,9 @@ class HipUNet:
                 _copy_up(p1, p1_full, M1)
                 ops.batch_copy(q2, M1, q2_full, M1, 1, M1)
                 x, p1, q2 = x_full, p1_full, q2_full
-            o2, lse2 = ops.attn_fwd(q2, cb["K"], cb["V"], rows, heads, HW, self.ctx["L"], self.ctx["Lp"], dh, scale,
-                                    want_lse=True, v_rows=True)
+            Lp = self.ctx["Lp"]      # a long prompt's keys (encode_tokens: 78 ... 231) stay in LDS where that measured faster
+            o2, lse2 = ops.attn_fwd(q2, cb["K"], cb["V"], rows, heads, HW, self.ctx["L"], Lp, dh, scale, want_lse=True, v_rows=True,
+                                    resident_kv=80 < Lp <= 240 and (dh, 10 if Lp <= 160 else 15) in _RESIDENT_KV)
             p2, _ = _produce("gemm", o2, W[t + ".attn2.to_out.0.weight"], out=_fresh(x, M, C), bias=W[t + ".attn2.to_out.0.bias"], residual=p1)
         # C = 320: norm3 -> FF1 -> gate -> FF2 + residual in ONE row-local launch (skg_ff_block_f16[_hilo]: the row panel and the output
         # accumulators stay in registers, only weights stream).  In a guided step the same launch also stores what the backward of
