@@ -478,6 +478,13 @@ int skg_adamw_step(float* param, const float* grad, float* exp_avg, float* exp_a
 int skg_cfg_ddim_step(const void* eps_u, const void* eps_c, int ld, int lo_off, const float* x, float* x_prev,
                       float* eps_out, int samples, int HW, float g, float c0, float c1, float c2,
                       float c3, int vpred, void* stream);
+/* The same step with DDIM's noise term (eta > 0; diffusers DDIMScheduler.step(eta=, generator=)):
+ *   x_prev = c2*x0 + c_dir*eps + sigma*z,   sigma = eta * sqrt((1-a_prev)/(1-a_t) * (1 - a_t/a_prev)),  c_dir = sqrt(1 - a_prev - sigma^2)
+ * z: caller-drawn N(0, 1), float NCHW like x (required).  eps, x0, the pair offset, vpred and eps_out as above; the five
+ * scalars are host-side fp32 table arithmetic (sketch2img_amd/sampler.py DDIMTables.coeffs_eta). */
+int skg_cfg_ddim_eta_step(const void* eps_u, const void* eps_c, int ld, int lo_off, const float* x, const float* z,
+                          float* x_prev, float* eps_out, int samples, int HW, float g, float c0, float c1,
+                          float c2, float c_dir, float sigma, int vpred, void* stream);
 /* ---- VAE decoder helpers (modules/pipeline.py:118 decode_latents; third-party AutoencoderKL.decode) -------------
  * Row softmax y[m][:] = softmax(x[m][:]) of fp16 scores, fp32 arithmetic: the decoder's single-head mid attention
  * (AttentionBlock: softmax(q k^T / sqrt(C)) v over HW tokens) is GEMM -> this -> GEMM.  N % 8 == 0. */

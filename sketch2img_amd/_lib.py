@@ -26,7 +26,8 @@ LIB_PATH = os.environ.get("SKG_LIB") or os.path.join(_HERE, "libskg.so")
 # operand limit; 6: one entry point per kernel family - the _hilo / _gn / _keep / _hw / _causal / _rowv / _pairout / _dq_delta /
 # _strided / _from_partial2 / skg_ff_block_proj_f16 twins folded into the un-suffixed names, which take the superset argument
 # list with nullable pointers selecting the arm: INTEGRATION.md has the migration table), so that a stale build selected through
-# SKG_LIB fails at load instead of receiving shifted arguments
+# SKG_LIB fails at load instead of receiving shifted arguments.  Added since without a bump (a new symbol is compatible; a build
+# that lacks it fails the export check below): skg_cfg_ddim_eta_step, the DDIM step with the eta > 0 noise term
 ABI_VERSION = 6
 
 # spec letters: p = device/host pointer, i = int, f = float, u = unsigned, z = size_t (return only)
@@ -86,6 +87,7 @@ SIGNATURES = {
     "skg_adamw_step": ("i", "pppppzfffffifp"),
     "skg_lgp_mse_seed": ("i", "pippipiiifp"),
     "skg_cfg_ddim_step": ("i", "ppiipppiifffffip"),
+    "skg_cfg_ddim_eta_step": ("i", "ppiippppiiffffffip"),
     "skg_softmax_rows_f16": ("i", "pipiiip"),
     "skg_image_postprocess": ("i", "pipziffp"),
     "skg_image_to_u8": ("i", "pipziffp"),

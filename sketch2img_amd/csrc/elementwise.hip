@@ -261,14 +261,18 @@ __global__ __launch_bounds__(256) void nhwc2nchw_kernel(const half_t* __restrict
   }
 }
 
-// CFG combine + DDIM (eta = 0) on float NCHW latents, 4 channels.
+// CFG combine + DDIM on float NCHW latents, 4 channels.
 // lo_off != 0 (accuracy mode): eps is a PAIR, the lo part lo_off columns to the right of the hi part in the same rows
 // vpred: the model output is v (prediction_type "v_prediction", SD2.1-768): eps = c0 v + c1 x, x0 = c0 x - c1 v
+// NOISE (eta > 0): x_prev += sigma * z, z a caller-drawn N(0, 1) tensor indexed like x (c3 then is the direction coefficient
+// sqrt(1 - a_prev - sigma^2)); the two extra arguments sit at the end so that the NOISE = false instantiation keeps the
+// instruction stream and the argument offsets of the eta = 0 kernel
+template <bool NOISE>
 __global__ __launch_bounds__(256) void cfg_ddim_kernel(const half_t* __restrict__ eu, const half_t* __restrict__ ec,
                                                        int ld, int lo_off, const float* __restrict__ x,
                                                        float* __restrict__ xp, float* __restrict__ eps_out,
                                                        int samples, int HW, float g, float c0, float c1, float c2,
-                                                       float c3, int vpred) {
+                                                       float c3, int vpred, const float* __restrict__ z, float sigma) {
   const size_t total = (size_t)samples * 4 * HW;
   for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
     const int p = (int)(i % HW);
@@ -287,7 +291,15 @@ __global__ __launch_bounds__(256) void cfg_ddim_kernel(const half_t* __restrict_
     } else {
       x0 = (x[i] - c1 * e) / c0;
     }
-    xp[i] = c2 * x0 + c3 * e;
+    float xn;
+    {
+      // two rounded products and their sum in both instantiations - what the eta = 0 kernel compiles to - then the noise term on
+      // top: sigma = 0 reproduces the eta = 0 step bit for bit, whichever contractions the compiler would otherwise pick per variant
+#pragma clang fp contract(off)
+      xn = c2 * x0 + c3 * e;
+      if (NOISE) xn += sigma * z[i];
+    }
+    xp[i] = xn;
     if (eps_out) eps_out[i] = e;
   }
 }
@@ -568,10 +580,22 @@ extern "C" int skg_cfg_ddim_step(const void* eps_u, const void* eps_c, int ld, i
                                  float c3, int vpred, void* stream) {
   SKG_REQUIRE(eps_u && eps_c && x && x_prev && samples > 0 && HW > 0 && ld >= 4 && lo_off >= 0 && (lo_off == 0 || ld >= lo_off + 4));
   SKG_REQUIRE(vpred == 0 || vpred == 1);
-  hipLaunchKernelGGL(cfg_ddim_kernel, dim3(ew_grid((size_t)samples * 4 * HW)), dim3(256), 0,
+  hipLaunchKernelGGL(cfg_ddim_kernel<false>, dim3(ew_grid((size_t)samples * 4 * HW)), dim3(256), 0,
                      (hipStream_t)stream, (const half_t*)eps_u, (const half_t*)eps_c, ld, lo_off, x, x_prev, eps_out,
-                     samples, HW, g, c0, c1, c2, c3, vpred);
+                     samples, HW, g, c0, c1, c2, c3, vpred, (const float*)nullptr, 0.f);
   SKG_CHECK_LAUNCH("skg_cfg_ddim_step");
+  return SKG_OK;
+}
+
+extern "C" int skg_cfg_ddim_eta_step(const void* eps_u, const void* eps_c, int ld, int lo_off, const float* x, const float* z,
+                                     float* x_prev, float* eps_out, int samples, int HW, float g, float c0, float c1,
+                                     float c2, float c_dir, float sigma, int vpred, void* stream) {
+  SKG_REQUIRE(eps_u && eps_c && x && z && x_prev && samples > 0 && HW > 0 && ld >= 4 && lo_off >= 0 && (lo_off == 0 || ld >= lo_off + 4));
+  SKG_REQUIRE(vpred == 0 || vpred == 1);
+  hipLaunchKernelGGL(cfg_ddim_kernel<true>, dim3(ew_grid((size_t)samples * 4 * HW)), dim3(256), 0,
+                     (hipStream_t)stream, (const half_t*)eps_u, (const half_t*)eps_c, ld, lo_off, x, x_prev, eps_out,
+                     samples, HW, g, c0, c1, c2, c_dir, vpred, z, sigma);
+  SKG_CHECK_LAUNCH("skg_cfg_ddim_eta_step");
   return SKG_OK;
 }
 

@@ -79,7 +79,8 @@ _BATCH_KV = os.environ.get("SKG_INJ_BATCH", "1") != "0"      # A/B switch (bench
 
 
 class HipInjector:
-    """Callable installed as ``HipUNet.inject``; ``variant`` is 'clip' or 'sketch'."""
+    """Callable installed as ``HipUNet.inject``; ``variant`` is 'clip' or 'sketch'.  What HipUNet asks of an injector: the call
+    per block below and ``check_rows(rows)`` before its first launch (``halves_equal``, where present, extends the shared CFG front)."""
 
     def __init__(self, cfg: UNetConfig, state_dict: Dict[str, torch.Tensor], variant: str, device):
         assert variant in ("clip", "sketch")
@@ -139,6 +140,14 @@ class HipInjector:
             tok = r.to(self.dev, torch.float16).permute(0, 2, 3, 1).reshape(rows * hh * ww, C).contiguous()
             kv = ops.gemm(tok, w["wkv"])                       # res_sample is used un-normalised (:127)
             self.per_image[path] = dict(K=kv[:, :C], V=kv[:, C:], rows=rows, N=hh * ww)
+
+    def check_rows(self, rows: int) -> None:
+        """HipUNet.forward calls this before its first launch: the state / res samples set for this image hold one row per
+        batch row of the evaluation (S cond rows without CFG, [uncond rows; cond rows] with it)."""
+        for path, pi in self.per_image.items():
+            if pi["rows"] != rows:
+                raise ValueError(f"the injector's {'state' if self.variant != 'sketch' else 'res samples'} hold {pi['rows']} rows, "
+                                 f"the UNet evaluates {rows} ({path})")
 
     # ---- per UNet evaluation ------------------------------------------------------------------------------
     def __call__(self, path: str, h, rows: int, N: int, heads: int, cond_only: bool = False, out=None):
@@ -256,6 +265,12 @@ class HipClipInjectorTrain:
     def end(self):
         self.state16 = self.g = self.dstate = None
         self.stash = {}
+
+    def check_rows(self, rows: int) -> None:
+        """The injectors' protocol (HipInjector.check_rows): HipUNet.forward calls this before its first launch.  begin() holds the
+        tokens of one sample, so the evaluation has one row."""
+        if rows != 1:
+            raise ValueError(f"the training injector holds the sketch tokens of 1 sample, the UNet evaluates {rows} rows")
 
     # ---- forward (HipUNet._tr_fwd calls this) ---------------------------------------------------------------------------------
     def __call__(self, path: str, h, rows: int, N: int, heads: int, cond_only: bool = False, out=None):

@@ -30,7 +30,7 @@ import numpy as np
 import torch
 
 from ..config import SD15, SD21, UNetConfig, tap_channels
-from ..sampler import DDIMTables, DPMTables, HipSampler
+from ..sampler import DDIMTables, DPMTables, HipSampler, check_eta, check_generators, draw_noise
 from .latent_predictor import LatentEdgePredictor, hook_unet
 
 logger = logging.getLogger(__name__)      # (the reference: diffusers.utils.logging.get_logger(__name__), modules/pipeline.py:11)
@@ -304,14 +304,21 @@ class AntiGradientPipeline:
             out.append(torch.randn(77, self.unet.cfg.cross_attention_dim, generator=g))
         return torch.stack(out)
 
-    def prepare_latents(self, batch_size, num_channels_latents, height, width, dtype, device, generator, latents=None):
+    def _check_latents_shape(self, latents, batch_size, num_channels_latents, height, width):
+        """-> the latents' shape; caller-supplied latents of another shape are a ValueError (diffusers' wording)."""
         shape = (batch_size, num_channels_latents, height // self.vae_scale_factor, width // self.vae_scale_factor)
-        if latents is None:
+        if latents is not None and tuple(latents.shape) != shape:
+            raise ValueError(f"Unexpected latents shape, got {tuple(latents.shape)}, expected {shape}")
+        return shape
+
+    def prepare_latents(self, batch_size, num_channels_latents, height, width, dtype, device, generator, latents=None):
+        shape = self._check_latents_shape(latents, batch_size, num_channels_latents, height, width)
+        if latents is None and isinstance(generator, (list, tuple)):
+            latents = draw_noise(shape, generator, device)      # sample s from generator[s]; a wrong length is a ValueError
+        elif latents is None:
             gdev = generator.device if isinstance(generator, torch.Generator) else "cpu"
             latents = torch.randn(shape, generator=generator if isinstance(generator, torch.Generator) else None,
                                   device=gdev, dtype=torch.float32)
-        elif tuple(latents.shape) != shape:
-            raise ValueError(f"Unexpected latents shape, got {tuple(latents.shape)}, expected {shape}")
         return latents.to(device=device, dtype=torch.float32)       # init_noise_sigma = 1 for DDIM
 
     def decode_latents(self, latents):
@@ -355,14 +362,18 @@ class AntiGradientPipeline:
         width = width or self.unet.config.sample_size * self.vae_scale_factor
         self.check_inputs(prompt, height, width, callback_steps)
         check_image_size(height, width, self.vae_scale_factor * 2 ** (len(self.unet.cfg.block_out_channels) - 1))
-        if eta != 0.0:
-            raise NotImplementedError("only eta = 0 (deterministic sampling) is implemented")
+        eta = check_eta(eta)                                # DDIM's eta in [0, 1]; DPM-Solver++ ignores it (HipSampler.sample)
         batch_size = 1 if isinstance(prompt, str) else len(prompt)
-        device = self._execution_device
-        if guidance_scale <= 1.0:
-            raise NotImplementedError("classifier-free guidance is always on in the hot path (guidance_scale > 1)")
-        ehs = self._encode_prompt(prompt, device, num_images_per_prompt, True, negative_prompt)
         S = batch_size * num_images_per_prompt
+        device = self._execution_device
+        # modules/pipeline.py:52: guidance_scale <= 1 evaluates the cond rows alone and never encodes the negative prompt
+        do_classifier_free_guidance = guidance_scale > 1.0
+        if not do_classifier_free_guidance and sketch_image is not None:
+            # (the reference concatenates [noise_level] * 2 against S rows here and fails inside the LGP)
+            raise ValueError("`sketch_image` (LGP guidance) needs classifier-free guidance: pass guidance_scale > 1")
+        check_generators(generator, S)
+        self._check_latents_shape(latents, S, self.unet.in_channels, height, width)     # (ahead of the text encoder's device work)
+        ehs = self._encode_prompt(prompt, device, num_images_per_prompt, do_classifier_free_guidance, negative_prompt)
         tab = self._tables(num_inference_steps)
         lat = self.prepare_latents(S, self.unet.in_channels, height, width, torch.float32, device, generator, latents)
 
@@ -381,7 +392,8 @@ class AntiGradientPipeline:
         cb = None
         if callback is not None:
             cb = lambda i, t, x: callback(i, t, x) if i % callback_steps == 0 else None
-        out = sampler.sample(lat, target, num_inference_steps, guidance_scale, 1.6, callback=cb, tables=tab)
+        out = sampler.sample(lat, target, num_inference_steps, guidance_scale, 1.6, callback=cb, tables=tab, eta=eta,
+                             generator=generator, classifier_free=do_classifier_free_guidance)
         self.last_aux = sampler.last_aux
         if lgp is not None:
             self.lgp_model._sync_running_stats()

@@ -994,6 +994,21 @@ def cfg_ddim_step(eps_u, eps_c, x, samples, HW, g, coeffs: Tuple[float, float, f
     return (x_prev, eps_out) if want_eps else x_prev
 
 
+def cfg_ddim_eta_step(eps_u, eps_c, x, z, samples, HW, g, coeffs: Tuple[float, float, float, float, float],
+                      want_eps=False, lo_off: int = 0, v_prediction: bool = False):
+    """cfg_ddim_step with DDIM's noise term: coeffs = DDIMTables.coeffs_eta(t, eta) = (c0, c1, c2, c_dir, sigma),
+    x_prev = c2 x0 + c_dir eps + sigma z.  z: N(0, 1) drawn by the caller, fp32 and contiguous in x's shape."""
+    _f16(eps_u, eps_c)
+    assert z is not None and z.is_cuda and z.dtype == torch.float32 and z.is_contiguous() and z.shape == x.shape, \
+        "z: contiguous fp32 CUDA tensor of the latents' shape"
+    x_prev = torch.empty_like(x)
+    eps_out = torch.empty_like(x) if want_eps else None
+    c0, c1, c2, c_dir, sigma = coeffs
+    check(lib.skg_cfg_ddim_eta_step(_p(eps_u), _p(eps_c), _ld(eps_u), lo_off, _p(x), _p(z), _p(x_prev), _p(eps_out), samples, HW,
+                                    g, c0, c1, c2, c_dir, sigma, int(bool(v_prediction)), _stream()), "skg_cfg_ddim_eta_step")
+    return (x_prev, eps_out) if want_eps else x_prev
+
+
 def cfg_dpmpp2m_step(eps_u, eps_c, x, x0_io, samples, HW, g, coeffs: Tuple[float, float, float, float, float],
                      want_eps=False, lo_off: int = 0, v_prediction: bool = False):
     """coeffs = (alpha_s, sigma_s, a, b, c); x0_io is updated in place (previous x0 in, this step's x0 out)."""

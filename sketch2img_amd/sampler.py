@@ -12,9 +12,10 @@ SURVEY Q1): alpha, the BatchNorm statistics and the loss are per sample.
 """
 from __future__ import annotations
 
+import logging
 import os
 from dataclasses import dataclass
-from typing import Callable, List, Optional
+from typing import Callable, List, Optional, Sequence
 
 import numpy as np
 import torch
@@ -22,6 +23,40 @@ import torch
 from . import ops
 from .lgp import HipLGP
 from .unet import CIN_PAD, HipUNet, Stash
+
+logger = logging.getLogger(__name__)
+
+
+def check_eta(eta: float) -> float:
+    """DDIM's eta lies in [0, 1]: above 1 the radicand of the direction coefficient, 1 - a_prev - sigma^2, can go negative."""
+    if not 0.0 <= eta <= 1.0:
+        raise ValueError(f"`eta` has to be in [0, 1] but is {eta}")
+    return float(eta)
+
+
+def check_generators(generator, batch_size: int) -> None:
+    """A list (or tuple) of generators holds one per sample (the wording is diffusers')."""
+    if isinstance(generator, (list, tuple)) and len(generator) != batch_size:
+        raise ValueError(f"You have passed a list of generators of length {len(generator)}, but requested an effective batch "
+                         f"size of {batch_size}. Make sure the batch size matches the length of the generators.")
+
+
+def draw_noise(shape: Sequence[int], generator, device) -> torch.Tensor:
+    """One N(0, 1) tensor [S, 4, h, w] in fp32 on `device`, the way diffusers' randn_tensor draws it (the reference draws in the
+    model's fp16; the latents are fp32 here): a list of generators draws sample s as [1, 4, h, w] from generator[s] on that
+    generator's device, a single generator draws the whole tensor on its device, None draws from the default generator of
+    `device`.  The initial latents of a generator list and every step's noise of an eta > 0 DDIM trajectory come from here, in
+    this order: the latents first, then one draw per step in step order (the eager loop draws after the step's UNet evaluation,
+    the hipGraph path draws all T before the first replay - the same values from a generator either way)."""
+    shape = tuple(int(v) for v in shape)
+    if isinstance(generator, (list, tuple)):
+        check_generators(generator, shape[0])
+        z = torch.cat([torch.randn((1,) + shape[1:], generator=g, device=g.device, dtype=torch.float32).to(device) for g in generator])
+    elif generator is None:
+        z = torch.randn(shape, device=device, dtype=torch.float32)
+    else:
+        z = torch.randn(shape, generator=generator, device=generator.device, dtype=torch.float32)
+    return z.to(device).contiguous()
 
 
 @dataclass
@@ -50,6 +85,21 @@ class DDIMTables:
         a_t = self.alphas_cumprod[t]
         a_p = self.alphas_cumprod[prev] if prev >= 0 else torch.tensor(self.final_alpha_cumprod)
         return float(a_t ** 0.5), float((1 - a_t) ** 0.5), float(a_p ** 0.5), float((1 - a_p) ** 0.5)
+
+    def coeffs_eta(self, t: int, eta: float):
+        """(sqrt(a_t), sqrt(1-a_t), sqrt(a_prev), c_dir, sigma) of diffusers' DDIMScheduler.step(eta=) / _get_variance, fp32 table
+        arithmetic:  sigma = eta * sqrt((1-a_prev)/(1-a_t) * (1 - a_t/a_prev)),  c_dir = sqrt(1 - a_prev - sigma^2),
+        x_prev = sqrt(a_prev) x0 + c_dir eps + sigma z.  eta = 0: coeffs(t) and 0.0, the same floats."""
+        eta = check_eta(eta)
+        if eta == 0.0:
+            return self.coeffs(t) + (0.0,)
+        prev = t - self.ratio
+        a_t = self.alphas_cumprod[t]
+        a_p = self.alphas_cumprod[prev] if prev >= 0 else torch.tensor(self.final_alpha_cumprod)
+        variance = ((1 - a_p) / (1 - a_t)) * (1 - a_t / a_p)
+        sigma = eta * variance ** 0.5
+        c_dir = (1 - a_p - sigma ** 2) ** 0.5
+        return float(a_t ** 0.5), float((1 - a_t) ** 0.5), float(a_p ** 0.5), float(c_dir), float(sigma)
 
     def sigma(self, t: int) -> float:
         """get_noise_level's factor sqrt(1 - alphas_cumprod[t]) (modules/pipeline.py:133)."""
@@ -111,11 +161,26 @@ def guided_step(i: int, T: int) -> bool:
     return not (i > 0.5 * T)            # modules/pipeline.py:89-92,108
 
 
+def graph_key(tab, shape, unguided: bool, guidance_scale: float, beta: float, share_cfg_prefix: bool, eta: float = 0.0,
+              classifier_free: bool = True) -> tuple:
+    """Everything that is baked into the kernel arguments of a captured set of steps: the schedule (timesteps AND the table values
+    the per-step coefficients come from - two schedulers may share timesteps and differ in betas / final alpha), the prediction
+    type, shapes, the guidance constants (v_prediction was missing -> a stale graph would have been replayed), eta (the
+    step kernel and its sigma / c_dir) and whether the UNet runs the CFG-doubled batch or the cond rows alone."""
+    acp = tab.alphas_cumprod
+    return (type(tab).__name__, tuple(int(t) for t in tab.timesteps), tuple(shape), bool(unguided),
+            float(guidance_scale), float(beta), bool(share_cfg_prefix), bool(tab.v_prediction),
+            float(getattr(tab, "final_alpha_cumprod", 0.0)), int(acp.numel()), float(acp.double().sum()), float(acp[0]), float(acp[-1]),
+            getattr(tab, "solver_order", 0), getattr(tab, "lower_order_final", None), float(eta), bool(classifier_free))
+
+
 class HipSampler:
     """``use_graphs``: replay every step of the schedule from a captured hipGraph (one graph per step index - the
     per-step scalars and the per-timestep bias vectors are baked into the kernel arguments, the latents live in
     static buffers).  The reference's real caller samples ONE image per call (app.py:113-123); at that size a step is
     ~900 launches of a few microseconds each and the Python / ctypes launch path, not the GPU, sets the pace."""
+
+    _eta_ignored_logged = False               # "eta is ignored by DPM-Solver++" is said once per process, at debug level
 
     def __init__(self, unet: HipUNet, lgp: Optional[HipLGP] = None, use_graphs: bool = False):
         self.unet, self.lgp, self.use_graphs = unet, lgp, use_graphs
@@ -136,14 +201,21 @@ class HipSampler:
 
     @torch.no_grad()
     def step(self, x: torch.Tensor, noise: torch.Tensor, target: Optional[torch.Tensor], tab,
-             i: int, guidance_scale: float, beta: float, want_eps: bool = False):
-        """One iteration of the loop for S samples.  x fp32 [S,4,h,w] on the device -> x_{t-1}."""
+             i: int, guidance_scale: float, beta: float, want_eps: bool = False, eta: float = 0.0, generator=None,
+             z: Optional[torch.Tensor] = None, classifier_free: bool = True):
+        """One iteration of the loop for S samples.  x fp32 [S,4,h,w] on the device -> x_{t-1}.
+        eta > 0 (DDIM only; DPM-Solver++ has no eta): the step adds sigma_t z, z = `z` if given (fp32, x's shape, on the device:
+        the hipGraph path's static slice) else one draw_noise(x.shape, generator) after the UNet evaluation.
+        classifier_free=False (the reference's guidance_scale <= 1): the UNet evaluates the S cond rows alone (prepare_context got S
+        rows) and the step kernels take that one tensor as both CFG operands with g = 1 - u + 1 (u - u) is u exactly."""
         S, _, h, w = x.shape
         hw = h * w
         T = len(tab.timesteps)
         t = int(tab.timesteps[i])
         guided = guided_step(i, T) and target is not None and self.lgp is not None
-        x32 = ops.nchw_to_nhwc(torch.cat([x, x]).contiguous(), CIN_PAD)
+        if guided and not classifier_free:
+            raise ValueError("LGP guidance differentiates the cond half of a CFG-doubled batch: classifier_free=False has none")
+        x32 = ops.nchw_to_nhwc((torch.cat([x, x]) if classifier_free else x).contiguous(), CIN_PAD)
         stash = Stash() if guided else None
         # (the two CFG halves of x32 are the same latents: the text-independent front of the UNet runs once)
         fork = guided and self.fork_guidance and not torch.cuda.is_current_stream_capturing()
@@ -171,10 +243,12 @@ class HipSampler:
                 branch["done"] = torch.cuda.Event()
                 branch["done"].record(self._side)
 
-        eps, taps = self.unet.forward(x32, t, 2 * S, h, stash, want_taps=guided, shared_input=self.share_cfg_prefix,
-                                      on_taps=on_taps if fork else None, W=w)
+        eps, taps = self.unet.forward(x32, t, 2 * S if classifier_free else S, h, stash, want_taps=guided,
+                                      shared_input=self.share_cfg_prefix and classifier_free, on_taps=on_taps if fork else None, W=w)
         fork = fork and "done" in branch          # (a forward that never reached the hook runs the branch in line)
         eu, ec, lo_off = ops.eps_halves(eps, S, hw)      # (accuracy mode: eps is a (hi, lo) pair, combined in fp32 by the step kernel)
+        if not classifier_free:
+            ec, guidance_scale = eu, 1.0
         if isinstance(tab, DPMTables):
             if self._x0_before is None or self._x0_before.shape != x.shape:
                 self._x0_before, self._seen = torch.zeros_like(x), 0
@@ -182,6 +256,11 @@ class HipSampler:
             res = ops.cfg_dpmpp2m_step(eu, ec, x, self._x0_before, S, hw, guidance_scale, tab.coeffs(i, order), want_eps, lo_off=lo_off,
                                        v_prediction=tab.v_prediction)
             self._seen = min(self._seen + 1, tab.solver_order)
+        elif eta > 0.0:
+            if z is None:
+                z = draw_noise(x.shape, generator, x.device)
+            res = ops.cfg_ddim_eta_step(eu, ec, x, z, S, hw, guidance_scale, tab.coeffs_eta(t, eta), want_eps, lo_off=lo_off,
+                                        v_prediction=tab.v_prediction)
         else:
             res = ops.cfg_ddim_step(eu, ec, x, S, hw, guidance_scale, tab.coeffs(t), want_eps, lo_off=lo_off,
                                     v_prediction=tab.v_prediction)
@@ -201,9 +280,24 @@ class HipSampler:
     def sample(self, latents0: torch.Tensor, target: Optional[torch.Tensor], num_inference_steps: int = 50,
                guidance_scale: float = 7.5, beta: float = 1.6,
                callback: Optional[Callable[[int, int, torch.Tensor], None]] = None,
-               tables=None, graphs: Optional[bool] = None) -> torch.Tensor:
+               tables=None, graphs: Optional[bool] = None, eta: float = 0.0, generator=None,
+               classifier_free: bool = True) -> torch.Tensor:
+        """eta, generator: DDIM's stochastic step (DDIMTables.coeffs_eta, draw_noise); a generator list holds one per sample.
+        classifier_free=False: no CFG - the context prepared on the UNet holds the S cond rows - and no LGP guidance."""
         dev = self.unet.dev
         tab = tables or DDIMTables.make(num_inference_steps)
+        eta = check_eta(eta)
+        if eta > 0.0 and not isinstance(tab, DDIMTables):
+            # DPM-Solver++ has no eta (diffusers' prepare_extra_step_kwargs drops the argument for it): no noise is drawn either
+            if not HipSampler._eta_ignored_logged:
+                HipSampler._eta_ignored_logged = True
+                logger.debug("eta = %s is ignored: %s has no eta", eta, type(tab).__name__)
+            eta = 0.0
+        if not classifier_free and target is not None:
+            raise ValueError("classifier_free=False (guidance_scale <= 1) cannot be combined with a sketch target: the LGP guidance "
+                             "differentiates the cond half of a CFG-doubled batch (the reference fails in this mode too)")
+        if eta > 0.0:
+            check_generators(generator, latents0.shape[0])
         x = latents0.to(dev, torch.float32).contiguous()
         noise = x.clone()                                     # modules/pipeline.py:75
         if target is not None and tuple(target.shape[-2:]) != tuple(x.shape[-2:]):
@@ -213,10 +307,11 @@ class HipSampler:
         self.last_aux = []
         self.reset_history()
         if (self.use_graphs if graphs is None else graphs) and callback is None:
-            x = self._sample_graphed(x, tgt, tab, guidance_scale, beta)
+            x = self._sample_graphed(x, tgt, tab, guidance_scale, beta, eta, generator, classifier_free)
         else:
             for i, t in enumerate(tab.timesteps.tolist()):
-                x, _, aux = self.step(x, noise, tgt, tab, i, guidance_scale, beta)
+                x, _, aux = self.step(x, noise, tgt, tab, i, guidance_scale, beta, eta=eta, generator=generator,
+                                      classifier_free=classifier_free)
                 self.last_aux.append(aux)
                 if callback is not None:
                     callback(i, t, x)
@@ -224,20 +319,19 @@ class HipSampler:
         return x
 
     # ------------------------------------------------------------------------------------------ hipGraph replay
-    def _sample_graphed(self, x: torch.Tensor, tgt: Optional[torch.Tensor], tab, guidance_scale: float, beta: float):
+    def _sample_graphed(self, x: torch.Tensor, tgt: Optional[torch.Tensor], tab, guidance_scale: float, beta: float,
+                        eta: float = 0.0, generator=None, classifier_free: bool = True):
         """Captures (first call for a given schedule / shape) and replays one hipGraph per step.  Every launch of a
         step goes to torch's current stream, which is the capturing stream inside ``torch.cuda.graph``; nothing on the
-        step path allocates outside torch's (graph-private) pool or synchronises with the host."""
+        step path allocates outside torch's (graph-private) pool or synchronises with the host.
+        eta > 0: the set owns a static [T, S, 4, h, w] noise buffer, each captured step reads its slice; all T draws of a
+        trajectory are made here, once, in step order (draw_noise) - before the warm-up pass of a new set, which reads the
+        buffer too and so consumes no generator state - and copied in before the first replay."""
         T = len(tab.timesteps)
         inj = self.unet.inject
-        # everything that is baked into the captured kernel arguments: the schedule (timesteps AND the table values the per-step
-        # coefficients come from - two schedulers may share timesteps and differ in betas / final alpha), the prediction type, shapes,
-        # the guidance constants (ADVICE r5: v_prediction was missing -> a stale graph would have been replayed)
-        acp = tab.alphas_cumprod
-        key = (type(tab).__name__, tuple(int(t) for t in tab.timesteps), tuple(x.shape), tgt is None,
-               float(guidance_scale), float(beta), bool(self.share_cfg_prefix), bool(tab.v_prediction),
-               float(getattr(tab, "final_alpha_cumprod", 0.0)), int(acp.numel()), float(acp.double().sum()), float(acp[0]), float(acp[-1]),
-               getattr(tab, "solver_order", 0), getattr(tab, "lower_order_final", None))
+        key = graph_key(tab, x.shape, tgt is None, guidance_scale, beta, self.share_cfg_prefix, eta, classifier_free)
+        zall = torch.stack([draw_noise(x.shape, generator, x.device) for _ in range(T)]) if eta > 0.0 else None
+        step_kw = lambda zs, i: dict(eta=eta, z=None if zs is None else zs[i], classifier_free=classifier_free)
         # What a captured step points at besides the static latents: the text context's K / V (prepare_context builds a
         # NEW dict per prompt) and the injector's per-image K / V (set_state / set_res_samples build a new dict per sketch)
         # and scale.  The entry keeps STRONG references to those objects and is valid only while the pipeline still holds
@@ -257,6 +351,7 @@ class HipSampler:
             xs, ns = torch.empty_like(x), torch.empty_like(x)
             ts = None if tgt is None else torch.empty_like(tgt)
             x0b = torch.zeros_like(x)
+            zs = None if zall is None else zall.clone()
             # one eager pass first: the per-timestep bias vectors and every lazily built per-image buffer must exist before
             # a capture.  The split-K workspace of the captured launches is the set's own (allocated above, outside the
             # capture); scratch buffers first touched inside the capture come from the set's private pool.
@@ -268,7 +363,7 @@ class HipSampler:
             self._x0_before, self._seen = x0b, 0
             w = xs.clone()
             for i in range(T):
-                w, _, _ = self.step(w, ns, ts, tab, i, guidance_scale, beta)
+                w, _, _ = self.step(w, ns, ts, tab, i, guidance_scale, beta, **step_kw(zs, i))
             if saved is not None:       # the warm-up pass is not part of the trajectory: undo its BatchNorm side effects
                 for l in range(4):
                     self.lgp.running_mean[l].copy_(saved[0][l]); self.lgp.running_var[l].copy_(saved[1][l])
@@ -280,19 +375,21 @@ class HipSampler:
             for i in range(T):
                 g = torch.cuda.CUDAGraph()
                 with torch.cuda.graph(g, pool=pool), ops.private_buffers(owner):
-                    xn, _, aux = self.step(xs, ns, ts, tab, i, guidance_scale, beta)
+                    xn, _, aux = self.step(xs, ns, ts, tab, i, guidance_scale, beta, **step_kw(zs, i))
                     xs.copy_(xn)
                 graphs.append(g)
                 auxs.append(aux)
             if saved is not None:       # captures do not execute, but keep the Python-side counters where they were
                 self.lgp.num_batches_tracked = list(saved[2])
-            ent = self._graphs[key] = dict(graphs=graphs, auxs=auxs, xs=xs, ns=ns, ts=ts, x0b=x0b, owner=owner,
+            ent = self._graphs[key] = dict(graphs=graphs, auxs=auxs, xs=xs, ns=ns, ts=ts, x0b=x0b, zs=zs, owner=owner,
                                            ctx=self.unet.ctx, inject=inj, per_image=None if inj is None else inj.per_image,
                                            scale=None if inj is None else inj.scale)
         ent["xs"].copy_(x); ent["ns"].copy_(x)
         if tgt is not None:
             ent["ts"].copy_(tgt)
         ent["x0b"].zero_()
+        if zall is not None:
+            ent["zs"].copy_(zall)
         S = x.shape[0]
         for i, g in enumerate(ent["graphs"]):
             g.replay()

@@ -866,6 +866,10 @@ class HipUNet:
         sz = (H, H if W is None else W)
         cfg, W = self.cfg, self.W
         assert self.ctx is not None and self.ctx["rows"] == rows, "call prepare_context first"
+        # every injector (inject.HipInjector, inject.HipClipInjectorTrain) has check_rows: a row count that differs from the batch
+        # raises here.  It stays ahead of prepare_timesteps, the first call of this walk that launches kernels
+        if self.inject is not None:
+            self.inject.check_rows(rows)
         if sz[0] != sz[1]:
             self._check_rect(sz)
         self.prepare_timesteps([t])
