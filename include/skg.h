@@ -41,8 +41,14 @@ const char* skg_last_error(void);
 #define SKG_EPI_GEGLU 4u     /* skg_gemm_f16 only: B / bias rows are the interleaved FF1 pack (groups of four output
                               * columns [a a g g]); C is [M][N/2] = a * gelu(g).  No residual, fp16 out, K % 64 == 0
                               * (else SKG_E_UNSUPPORTED).  Fuses diffusers GEGLU into ff.net.0.proj. */
+#define SKG_EPI_BIAS_ROWS 8u /* skg_conv3x3_f16 (every mode) / skg_conv3x3_wino_f16 only: bias is fp16 [rows][Cout] (pitch Cout), one row
+                              * per SAMPLE - output row m reads bias[m / (OH * OW)][n].  Needs bias != NULL (else SKG_E_BADARG;
+                              * skg_gemm_f16: SKG_E_BADARG).  The time-embedding projection of a ResnetBlock folded into conv1.bias
+                              * when every sample of the batch has its own timestep (the trainers' unet(noisy_latents, timesteps,
+                              * ehs) at modules/pipeline.py:96 with a [B] timestep tensor). */
 
 /* C[m][n] = epi( alpha * (sum_k A[m][k] * B[n][k] + bias[n]) + residual[m][n] )
+ * (convolutions with SKG_EPI_BIAS_ROWS: bias[m / (OH * OW)][n] in place of bias[n])
  * A fp16 [M][K] (lda), B fp16 [N][K] (ldb), C fp16|fp32 [M][N] (ldc), bias fp16 [N] or NULL,
  * residual fp16 [M][N] (ldr) or NULL.  Requires K % 32 == 0, N % 8 == 0, lda/ldb % 8 == 0,
  * ldc/ldr % 4 == 0, 16-byte aligned A/B, 8-byte aligned C/residual/bias.
@@ -67,7 +73,10 @@ int skg_set_workspace(void* ws, size_t bytes, void* stream);
 
 /* Which kernel instantiation skg_gemm_f16 (mode 0, Cin ignored) / skg_conv3x3_f16 (mode = 1 + SKG_CONV_*)
  * run for this shape: 2000 + BN for the LDS-DMA kernel (gemm2_kernel<BN,MODE>), 1000 + BN for the generic one;
- * lets a profiler attribute a launch to the kernel instantiation that ran (bench.py roofline). */
+ * lets a profiler attribute a launch to the kernel instantiation that ran (bench.py roofline).  (A convolution with SKG_EPI_BIAS_ROWS
+ * runs the same kernel family, with two exceptions this query does not see: the LDS-DMA kernel runs such a launch on its 128-row tiles
+ * only - where it reports 2320 the launch runs 128 x 160 - and the 256 x 320 ping-pong tile (8320) is taken only when OH * OW % 256 == 0;
+ * tiles that can span samples - OH * OW % 128 != 0 - and fp32 outputs take the two-stage per-row instantiations.) */
 int skg_gemm_variant(int M, int N, int K, int Cin, int mode);
 
 /* 3x3 convolution, padding 1, as implicit GEMM over NHWC fp16.
@@ -166,7 +175,7 @@ int skg_conv3x3_sc_f16(const void* X, int ldx, const void* X2, int ldx2, int K2,
  *   GEMM kernel, fp32 slabs in the stream's workspace)  ->  Y = A^T M A + bias (+ residual) per 2 x 2 output tile.
  * X [rows*IH*IW][ldx >= Cin] fp16; U [Cout][16 * Cin] fp16 = G g G^T per (cout, cin), component c = 4 i + j at columns [c Cin, (c + 1) Cin)
  * (unet.pack_conv_wino); V: caller-owned scratch of skg_conv3x3_wino_v_bytes() bytes; Y [rows*IH*IW][ldy] (+ Y_lo: pair output);
- * flags: SKG_EPI_RELU only.  Needs IH, IW even, Cin % 64 == 0, Cout % 8 == 0 and a registered workspace of >= 64 * Mt * Cout bytes
+ * flags: SKG_EPI_RELU and SKG_EPI_BIAS_ROWS only.  Needs IH, IW even, Cin % 64 == 0, Cout % 8 == 0 and a registered workspace of >= 64 * Mt * Cout bytes
  * (skg_set_workspace); otherwise SKG_E_UNSUPPORTED (nothing launched: run skg_conv3x3_f16).  U and V carry one more fp16 rounding than
  * the implicit GEMM's operands (tools/eps_winograd.py prices it: default-mode eps rel 1.07e-3 -> 1.09e-3).
  * X == NULL: V already holds the input transform (skg_groupnorm_wino_fwd wrote it). */

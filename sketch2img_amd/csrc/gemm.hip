@@ -1,6 +1,7 @@
 // fp16 MFMA GEMM and 3x3 implicit-GEMM convolution for gfx950.
 //
 //   C[m][n] = epi(alpha * (sum_k A[m][k] * B[n][k] + bias[n]) + residual[m][n])
+// (SKG_EPI_BIAS_ROWS, convolutions: bias[m / (OH * OW)][n], a row per sample)
 //
 // One kernel template serves the dense GEMM and the four conv gather modes: only the A-operand
 // address generator differs (the K axis of a conv is (ky, kx, cin) with cin contiguous, so a
@@ -150,13 +151,14 @@ __global__ __launch_bounds__(256) void gemm_kernel(const GemmParams p) {
   for (int i = 0; i < MT; ++i) {
     const int m = m0 + wm * 64 + i * 16 + l16;
     if (m >= p.M) continue;
+    const half_t* const brow = p.bias + (p.bias_pitch ? (size_t)(m / p.gn_hw) * p.bias_pitch : 0);      // (the sample's bias row)
 #pragma unroll
     for (int j = 0; j < NT; ++j) {
       const int n = n0 + wn * WN + j * 16 + g * 4;
       if (n >= p.N) continue;
       float4_t v = acc[i][j];
       if (p.bias) {
-        const half4_t b = ld_half4(p.bias + n);
+        const half4_t b = ld_half4(brow + n);
         v[0] += (float)b[0]; v[1] += (float)b[1]; v[2] += (float)b[2]; v[3] += (float)b[3];
       }
       v *= p.alpha;
@@ -189,7 +191,7 @@ template <int MODE>
 int launch(const GemmParams& p, hipStream_t st) {
   if (!p.gn_partial) return launch_plain<MODE>(p, st);
 #ifdef SKG_LAB
-  const bool v9 = skg_gemm9_eligible(p, MODE);      // (no statistics epilogue: the stand-alone pass follows)
+  const bool v9 = !p.bias_pitch && skg_gemm9_eligible(p, MODE);      // (no statistics epilogue: the stand-alone pass follows)
 #else
   constexpr bool v9 = false;
 #endif
@@ -210,7 +212,7 @@ int launch_plain(const GemmParams& p, hipStream_t st) {
   }
 #endif
 #ifdef SKG_LAB      // round-5 experiment (tools/lab/gemm9.hip, EXPERIMENTS.md "the hand-placed K loop"): lab build only, SKG_GEMM9=<geometry><variant>
-  if (skg_gemm9_try_launch(p, MODE, st)) {
+  if (!p.bias_pitch && skg_gemm9_try_launch(p, MODE, st)) {      // (no per-sample bias row in the lab kernels)
     SKG_CHECK_LAUNCH("skg_gemm (v9)");
     return SKG_OK;
   }
@@ -220,7 +222,7 @@ int launch_plain(const GemmParams& p, hipStream_t st) {
     return SKG_OK;
   }
 #ifdef SKG_LAB      // withdrawn round-3 experiment (tools/lab/gemmk.hip, EXPERIMENTS.md): lab build only, SKG_GEMMK=1
-  if (skg_gemmk_try_launch(p, MODE, st)) {
+  if (!p.bias_pitch && skg_gemmk_try_launch(p, MODE, st)) {
     SKG_CHECK_LAUNCH("skg_gemm (k-pair)");
     return SKG_OK;
   }
@@ -375,6 +377,7 @@ static bool pair_args_ok(const void* C, const void* C_lo, int ldc, const void* r
 extern "C" int skg_gemm_f16(const void* A, int lda, const void* B, int ldb, void* C, void* C_lo, int ldc, int M, int N, int K,
                             const void* bias, const void* residual, const void* residual_lo, int ldr, float alpha,
                             unsigned flags, float* gn_partial, int HW, int groups, void* stream) {
+  SKG_REQUIRE(!(flags & SKG_EPI_BIAS_ROWS));      // (a bias row per sample: the 3x3 convolutions only)
   SKG_REQUIRE(!(C_lo || residual_lo) || pair_args_ok(C, C_lo, ldc, residual, residual_lo, ldr, K, flags));
   SKG_REQUIRE(!gn_partial || (gn_args_ok(gn_partial, M, N, HW, groups, ldc, flags) && skg_aligned(C, 16)));
   SKG_REQUIRE(A && B && C && M > 0 && N > 0 && K > 0);
@@ -412,6 +415,7 @@ extern "C" int skg_gemm_f16_rows(const void* A, int lda, const void* B, int ldb,
 extern "C" int skg_conv3x3_sc_f16(const void* X, int ldx, const void* X2, int ldx2, int K2, const void* Wcat, void* Y, void* Y_lo,
                                   int ldy, int rows, int IH, int IW, int Cin, int Cout, const void* bias, unsigned flags,
                                   float* gn_partial, int groups, void* stream) {
+  SKG_REQUIRE(!(flags & SKG_EPI_BIAS_ROWS));      // (a bias row per sample: conv1 only - skg_conv3x3_f16 / skg_conv3x3_wino_f16)
   SKG_REQUIRE(X && X2 && Wcat && Y && rows > 0 && IH > 0 && IW > 0 && K2 > 0 && K2 % 64 == 0 && Cin % 64 == 0 && Cout % 8 == 0);
   SKG_REQUIRE(ldx % 8 == 0 && ldx >= Cin && ldx2 % 8 == 0 && ldx2 >= K2 && ldy % 8 == 0 && ldy >= Cout);
   SKG_REQUIRE(skg_aligned(X, 16) && skg_aligned(X2, 16) && skg_aligned(Wcat, 16) && skg_aligned(Y, 16) && (!Y_lo || skg_aligned(Y_lo, 16)) &&
@@ -482,7 +486,8 @@ extern "C" int skg_conv3x3_wino_f16(const void* X, int ldx, const void* U, void*
               skg_aligned(Y, 8) && (!Y_lo || skg_aligned(Y_lo, 8)) && (!bias || skg_aligned(bias, 8)));
   SKG_REQUIRE((!residual && !residual_lo) || (ldr % 4 == 0 && ldr >= Cout && (!residual || skg_aligned(residual, 8)) &&
                                               (!residual_lo || skg_aligned(residual_lo, 8))));
-  SKG_REQUIRE(!(flags & ~SKG_EPI_RELU));
+  SKG_REQUIRE(!(flags & ~(SKG_EPI_RELU | SKG_EPI_BIAS_ROWS)));
+  SKG_REQUIRE(!(flags & SKG_EPI_BIAS_ROWS) || bias);
   // shapes this path takes (everything else: SKG_E_UNSUPPORTED, nothing launched - run skg_conv3x3_f16): even maps, whole 64-deep K
   // tiles per transform component, four output columns per thread of the output transform
   if ((IH & 1) || (IW & 1) || Cin % 64 != 0 || Cout % 8 != 0) return SKG_E_UNSUPPORTED;
@@ -492,6 +497,7 @@ extern "C" int skg_conv3x3_wino_f16(const void* X, int ldx, const void* U, void*
   p.bias = (const half_t*)bias; p.res = (const half_t*)residual; p.res_lo = (const half_t*)residual_lo; p.ldr = ldr;
   p.c_lo = (half_t*)Y_lo;
   p.M = rows * (IH / 2) * (IW / 2); p.N = Cout; p.K = 16 * Cin; p.alpha = 1.f; p.flags = flags;
+  p.bias_pitch = (flags & SKG_EPI_BIAS_ROWS) ? Cout : 0;
   p.wino = 16;
   ws_attach(p, st);
   if (!p.ws || (size_t)16 * p.M * p.N * 4 > p.ws_bytes) return SKG_E_UNSUPPORTED;      // the 16 fp32 slabs live in the stream's workspace
@@ -504,7 +510,7 @@ extern "C" int skg_conv3x3_wino_f16(const void* X, int ldx, const void* U, void*
     SKG_CHECK_LAUNCH("skg_conv3x3_wino_f16 (input transform)");
   }
   GemmParams g = p;      // the GEMM step: raw slabs only
-  g.bias = nullptr; g.res = nullptr; g.res_lo = nullptr; g.c_lo = nullptr; g.flags = 0;
+  g.bias = nullptr; g.bias_pitch = 0; g.res = nullptr; g.res_lo = nullptr; g.c_lo = nullptr; g.flags = 0;
   if (!skg_gemm2_try_launch(g, MODE_DIRECT, st)) return SKG_E_UNSUPPORTED;
   SKG_CHECK_LAUNCH("skg_conv3x3_wino_f16 (GEMM)");
   skg_wino_out_launch(p, p.ws, IH, IW, st);
@@ -559,6 +565,7 @@ extern "C" int skg_conv3x3_f16(const void* X, int ldx, const void* Wp, void* Y, 
                                int ldr, float alpha, unsigned flags, float* gn_partial, int groups, void* stream) {
   int OH, OW;
   conv_out_size(mode, IH, IW, &OH, &OW);
+  SKG_REQUIRE(!(flags & SKG_EPI_BIAS_ROWS) || bias);      // bias [rows][Cout], a row per sample
   SKG_REQUIRE(!(Y_lo || residual_lo) || pair_args_ok(Y, Y_lo, ldy, residual, residual_lo, ldr, Cin, flags));
   SKG_REQUIRE(!gn_partial || (rows > 0 && OH > 0 && OW > 0 && skg_aligned(Y, 16) &&
                               gn_args_ok(gn_partial, rows * OH * OW, Cout, OH * OW, groups, ldy, flags)));
@@ -573,6 +580,7 @@ extern "C" int skg_conv3x3_f16(const void* X, int ldx, const void* Wp, void* Y, 
   p.N = Cout; p.K = 9 * Cin; p.alpha = alpha; p.flags = flags;
   p.IH = IH; p.IW = IW; p.Cin = Cin;
   p.OH = OH; p.OW = OW; p.M = rows * OH * OW; p.gn_hw = OH * OW;
+  p.bias_pitch = (flags & SKG_EPI_BIAS_ROWS) ? Cout : 0;
   p.gn_partial = gn_partial; p.gn_groups = gn_partial ? groups : 0;
   p.c_lo = (half_t*)Y_lo; p.res_lo = (const half_t*)residual_lo;
   hipStream_t st = (hipStream_t)stream;

@@ -1,6 +1,9 @@
 // v2 fp16 MFMA GEMM / 3x3 implicit-GEMM convolution for gfx950: LDS-DMA staged, swizzled, double buffered.
 //
 //   C[m][n] = epi(alpha * (sum_k A[m][k] * B[n][k] + bias[n]) + residual[m][n])
+// (SKG_EPI_BIAS_ROWS, convolutions: bias[m / (OH * OW)][n].  A tile that lies inside one sample - OH * OW % BM == 0, the 64x64 to
+// 16x16 levels - offsets the bias pointer once per workgroup, a scalar, in front of the slice load; a launch whose tiles can span
+// samples runs the BROWS instantiations, whose epilogue looks the bias row up per output row)
 //
 // Block tile 128 x BN x 64 (BN = 160 | 128 | 64), 4 waves as 2(M) x 2(N), wave tile 64 x BN/2 out of
 // 16x16x32 f16 MFMAs (weights as the A operand so each lane owns 4 consecutive output channels).
@@ -147,7 +150,7 @@ __device__ __forceinline__ float4_t ld_agent(const float* p) {
 // launch (gemm2_splitk_kernel) share it, bit for bit
 __device__ __forceinline__ void splitk_epilogue(const GemmParams& p, float4_t v, size_t m, int n) {
   if (p.bias) {
-    const half4_t b = ld_half4(p.bias + n);
+    const half4_t b = ld_half4(p.bias + (p.bias_pitch ? (m / (size_t)p.gn_hw) * (size_t)p.bias_pitch : 0) + n);      // (the sample's bias row)
     v[0] += (float)b[0]; v[1] += (float)b[1]; v[2] += (float)b[2]; v[3] += (float)b[3];
   }
   v *= p.alpha;
@@ -183,7 +186,10 @@ __device__ __forceinline__ void splitk_epilogue(const GemmParams& p, float4_t v,
 // the ticket.  Bit-identical to the two-launch path (tools/lab/splitk_self_check.py) and 13-26 % SLOWER end to end in all three
 // forms tried (EXPERIMENTS.md): the reduction is 320 KB through one CU at memory-side latency where splitk_reduce_kernel has
 // the whole chip; the product keeps the reduce launch.
-template <int BM, int BN, int WGM, int WGN, int MODE, int NS, bool GNS, bool HILO, bool FIX>
+// BROWS: the instantiations for a bias row per sample (p.bias_pitch) on tiles that can span samples (launch_cfg: SKG_FLAG_BIAS_PER_ROW):
+// always the fp32-staged epilogue, whose second phase owns ONE output row per thread and adds that row's bias row there (the slice in
+// LDS stays zero), or the direct stores with a per-row lookup.  The plain instantiations only ever see tiles inside one sample.
+template <int BM, int BN, int WGM, int WGN, int MODE, int NS, bool GNS, bool HILO, bool FIX, bool BROWS = false>
 __device__ __forceinline__ void gemm2_body(const GemmParams& p, int tiles_n, int nwg, unsigned a_bytes, unsigned b_bytes,
                                            unsigned a_shift, int kt_per_split, float* __restrict__ ws) {
   constexpr int NW = WGM * WGN;       // waves
@@ -274,6 +280,7 @@ __device__ __forceinline__ void gemm2_body(const GemmParams& p, int tiles_n, int
   unsigned a_mask[ACH];               // S1/S2: bit t set <=> tap t reads a pixel inside the image
   int a_oy[ACH], a_ox[ACH];           // UP2/S2T only
   unsigned a_img[ACH];                // UP2/S2T: byte offset of the image + piece
+  int smp0 = 0;                       // conv: the sample of this lane's first row (lane 0 of a wave: of a row in the tile's first 32)
 #pragma unroll
   for (int j = 0; j < ACH; ++j) {
     const int r = (j * NW + wave) * 8 + lr;
@@ -287,6 +294,7 @@ __device__ __forceinline__ void gemm2_body(const GemmParams& p, int tiles_n, int
     } else {
       const int ohw = p.OH * p.OW;
       const int b = mm / ohw;
+      if (j == 0) smp0 = b;
       const int rr = mm - b * ohw;
       const int oy = rr / p.OW, ox = rr - oy * p.OW;
       const unsigned img = (unsigned)b * (unsigned)(p.IH * p.IW);
@@ -528,7 +536,14 @@ __device__ __forceinline__ void gemm2_body(const GemmParams& p, int tiles_n, int
   const int kt_begin = split * kt_per_split;
   const int KT = min(p.K / BK, kt_begin + kt_per_split);
   // the tile's bias slice is fetched now and parked in a register until the epilogue puts it into LDS
-  const float bias_r = (tid < BN && p.bias && n0 + tid < p.N) ? (float)p.bias[n0 + tid] : 0.f;
+  float bias_r = 0.f;
+  if constexpr (!BROWS) {
+    // (a bias row per sample: the whole tile lies inside one sample, the one the DMA description above already found for the
+    // rows of lane 0 - a scalar; bias_pitch = 0: the shared row)
+    const half_t* bias_t = p.bias;
+    if constexpr (MODE != MODE_DIRECT) bias_t += __builtin_amdgcn_readfirstlane(smp0) * p.bias_pitch;
+    bias_r = (tid < BN && p.bias && n0 + tid < p.N) ? (float)bias_t[n0 + tid] : 0.f;
+  }
   SKG_PH(1);
   {
     const DmaStep d0 = dma_prepare(kt_begin, true);
@@ -751,7 +766,7 @@ __device__ __forceinline__ void gemm2_body(const GemmParams& p, int tiles_n, int
       }
     }
   };
-  if (staged && !p.res && !HILO) {
+  if (staged && !p.res && !HILO && !BROWS) {
     // No residual: bias, alpha and ReLU are applied in registers and the value is rounded to fp16 (its final rounding;
     // for the fused GEGLU the same rounding the unfused path and the reference apply to the FF1 output) BEFORE it
     // goes through LDS - half the staging bytes, all 128 rows in one slab, every wave writes at once, two barriers
@@ -973,8 +988,24 @@ __device__ __forceinline__ void gemm2_body(const GemmParams& p, int tiles_n, int
             if (n0 + ec + k * TPR * 8 >= p.N) continue;
             float v[8] = {v0[k][0], v0[k][1], v0[k][2], v0[k][3], v1[k][0], v1[k][1], v1[k][2], v1[k][3]};
             half8_t o;
+            if constexpr (BROWS) {      // this thread's row reads its sample's bias row
+              const half_t* const brow = p.bias + (size_t)((m0 + sl * SROWS + er) / p.gn_hw) * p.bias_pitch + n0 + ec + k * TPR * 8;
+              const half4_t b0 = ld_half4(brow), b1 = ld_half4(brow + 4);
+              const float bb[8] = {(float)b0[0], (float)b0[1], (float)b0[2], (float)b0[3], (float)b1[0], (float)b1[1], (float)b1[2], (float)b1[3]};
+              if (HILO || p.res) {      // as this epilogue without the flag: (acc + b) * alpha + residual
 #pragma unroll
-            for (int e = 0; e < 8; ++e) v[e] = v[e] * p.alpha + (float)rv[sl][k][e];
+                for (int e = 0; e < 8; ++e) v[e] = (v[e] + bb[e]) * p.alpha + (float)rv[sl][k][e];
+              } else {                  // as the fp16-staged epilogue a launch without residual takes without the flag: acc * alpha + (b * alpha)
+#pragma unroll
+                for (int e = 0; e < 8; ++e) {
+                  const float ba = bb[e] * p.alpha;
+                  v[e] = __builtin_fmaf(v[e], p.alpha, ba);
+                }
+              }
+            } else {
+#pragma unroll
+              for (int e = 0; e < 8; ++e) v[e] = v[e] * p.alpha + (float)rv[sl][k][e];
+            }
             if constexpr (HILO) {
               if (p.res_lo) {
                 const half8_t rl = ld_half8(p.res_lo + (size_t)(m0 + er + sl * SROWS) * p.ldr + n0 + ec + k * TPR * 8);
@@ -1028,8 +1059,8 @@ __device__ __forceinline__ void gemm2_body(const GemmParams& p, int tiles_n, int
       const int n = n0 + wn * WN + j * 16 + g * 4;
       if (n >= p.N) continue;
       float4_t v = acc[i][j];
-      if (p.bias) {
-        const half4_t b = ld_half4(p.bias + n);
+      if (p.bias) {      // (BROWS: the row's own bias row; the plain instantiations never get here with a bias row per sample - launch_cfg)
+        const half4_t b = ld_half4(p.bias + (BROWS ? (size_t)(m / p.gn_hw) * p.bias_pitch : 0) + n);
         v[0] += (float)b[0]; v[1] += (float)b[1]; v[2] += (float)b[2]; v[3] += (float)b[3];
       }
       v *= p.alpha;
@@ -1051,12 +1082,12 @@ __device__ __forceinline__ void gemm2_body(const GemmParams& p, int tiles_n, int
   }   // persistent tile loop
 }
 
-template <int BM, int BN, int WGM, int WGN, int MODE, int NS = 2, bool GNS = false, bool HILO = false>
+template <int BM, int BN, int WGM, int WGN, int MODE, int NS = 2, bool GNS = false, bool HILO = false, bool BROWS = false>
 __global__ __launch_bounds__(WGM * WGN * 64, (NS * (BM + BN) * BK * 2 + 8 * BN <= 80 * 1024) ? 2 : 1) void gemm2_kernel(const GemmParams p, int tiles_n, int nwg,
                                                                   unsigned a_bytes, unsigned b_bytes,
                                                                   unsigned a_shift, int kt_per_split,
                                                                   float* __restrict__ ws) {
-  gemm2_body<BM, BN, WGM, WGN, MODE, NS, GNS, HILO, false>(p, tiles_n, nwg, a_bytes, b_bytes, a_shift, kt_per_split, ws);
+  gemm2_body<BM, BN, WGM, WGN, MODE, NS, GNS, HILO, false, BROWS>(p, tiles_n, nwg, a_bytes, b_bytes, a_shift, kt_per_split, ws);
 }
 #ifdef SKG_LAB
 // the self-finishing split-K launch (see FIX above; WITHDRAWN, lab build only: EXPERIMENTS.md round 4): its own kernel, so that
@@ -1215,7 +1246,7 @@ void launch_cfg(const GemmParams& p_in, hipStream_t st) {
   // K <= 640: the launches whose epilogue weighs as much as their K loop)
   static const int direct_epi = getenv("SKG_DIRECT_EPI") ? atoi(getenv("SKG_DIRECT_EPI")) : 0;
   const bool direct_ok = direct_epi && !(p.flags & (SKG_EPI_GEGLU | SKG_EPI_OUT_F32)) && !p.c_lo && !p.res_lo && !p.gn_partial && !p.up2 &&
-                         !p.seg_rows && !p.ntaps && p.N % BN == 0 && p.ldc % 8 == 0 && skg_aligned(p.C, 16) &&
+                         !p.seg_rows && !p.ntaps && !p.bias_pitch && p.N % BN == 0 && p.ldc % 8 == 0 && skg_aligned(p.C, 16) &&
                          (!p.res || (p.ldr % 8 == 0 && skg_aligned(p.res, 16))) && (!p.bias || skg_aligned(p.bias, 16)) &&
                          (direct_epi == 1 || p.K <= 640);
 #else
@@ -1231,6 +1262,10 @@ void launch_cfg(const GemmParams& p_in, hipStream_t st) {
   if (p.wino) splits = p.wino;      // Winograd GEMM step: one K slice per transform component (skg_gemm2_try_launch checked the preconditions)
   constexpr int NTHR = WGM * WGN * 64;
   if (BM == 128 && BN == 160 && splits == 1 && gn_fusable(p, MODE)) p.flags |= SKG_FLAG_GN_STATS;
+  // a bias row per sample: the plain instantiations place the tile's sample once per workgroup in front of their staged epilogues;
+  // tiles that can span samples (or a launch that would take the direct stores: fp32 output, an unaligned output or residual) run the BROWS instantiations (launch_mode: BM = 128)
+  if (p.bias_pitch && (p.gn_hw % BM != 0 || (p.flags & SKG_EPI_OUT_F32) || p.ldc % 8 != 0 || !skg_aligned(p.C, 16) || (p.res && (p.ldr % 8 != 0 || !skg_aligned(p.res, 16)))))
+    p.flags |= SKG_FLAG_BIAS_PER_ROW;
   if (direct_ok && splits == 1) p.flags |= 0x10000u;
   // XCDs per K slice: all 8 without split-K; 8 / ns when the slices line up with XCD boundaries
   const int ns_eff = splits > 1 ? skg_cdiv(KT, skg_cdiv(KT, splits)) : 1;
@@ -1295,6 +1330,20 @@ void launch_cfg(const GemmParams& p_in, hipStream_t st) {
   const bool hilo = p.c_lo || p.res_lo;
   constexpr bool HILO_OK = BM == 128 && (MODE == MODE_DIRECT || MODE == MODE_S1 || MODE == MODE_S2 || MODE == MODE_UP2);
   const bool gns = (p.flags & SKG_FLAG_GN_STATS) != 0;
+  if constexpr (BM == 128 && MODE != MODE_DIRECT) {      // (two stages, no statistics: gn_fusable wants whole 128-row chunks per sample)
+    if (p.flags & SKG_FLAG_BIAS_PER_ROW) {
+      if constexpr (HILO_OK) {
+        if (hilo) {
+          hipLaunchKernelGGL((gemm2_kernel<BM, BN, WGM, WGN, MODE, 2, false, true, true>), dim3(ntiles), dim3(NTHR), 0, st, p, tiles_n, ntiles,
+                             (unsigned)a, (unsigned)b, (unsigned)s, KT, (float*)nullptr);
+          return;
+        }
+      }
+      hipLaunchKernelGGL((gemm2_kernel<BM, BN, WGM, WGN, MODE, 2, false, false, true>), dim3(ntiles), dim3(NTHR), 0, st, p, tiles_n, ntiles,
+                         (unsigned)a, (unsigned)b, (unsigned)s, KT, (float*)nullptr);
+      return;
+    }
+  }
 #define G2_LAUNCH(NS_, GNS_, HILO_)                                                                                            \
   hipLaunchKernelGGL((gemm2_kernel<BM, BN, WGM, WGN, MODE, NS_, GNS_, HILO_>), dim3(ntiles), dim3(NTHR), 0, st, p, tiles_n, ntiles, \
                      (unsigned)a, (unsigned)b, (unsigned)s, KT, (float*)nullptr)
@@ -1352,7 +1401,7 @@ void launch_cfg(const GemmParams& p_in, hipStream_t st) {
 template <int MODE>
 void launch_mode(const GemmParams& p, hipStream_t st) {
   TileCfg t = pick_tile(p.M, p.N, p.K);
-  if (t.bm == 256 && (p.c_lo || p.res_lo || p.up2 || p.seg_rows)) t = TileCfg{128, 160};      // (hi / lo epilogue, polyphase row map: 128-row tiles)
+  if (t.bm == 256 && (p.c_lo || p.res_lo || p.up2 || p.seg_rows || p.bias_pitch)) t = TileCfg{128, 160};      // (hi / lo epilogue, polyphase row map, a bias row per sample: 128-row tiles)
   if (p.wino) t = p.N % 160 == 0 ? TileCfg{128, 160} : p.N % 128 == 0 ? TileCfg{128, 128} : TileCfg{128, 64};      // 16 slices of 128-row tiles
   if (t.bm == 256) launch_cfg<256, 320, 2, 4, MODE>(p, st);
   else if (t.bn == 160) {

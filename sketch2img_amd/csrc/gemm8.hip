@@ -82,6 +82,8 @@ __global__ __launch_bounds__(NTHR, 2) void gemm8_kernel(const GemmParams p, int 
   }
   const int tile_m = lid / tiles_n, tile_n = lid - tile_m * tiles_n;
   const int m0 = tile_m * BM, n0 = tile_n * BN;
+  // a bias row per sample: the launcher takes such a launch only when every tile lies inside one sample - a scalar of m0
+  const int bias_off = p.bias_pitch ? __builtin_amdgcn_readfirstlane((m0 / p.gn_hw) * p.bias_pitch) : 0;
 
   // ---- per-lane DMA source description (as gemm2.hip: one voffset per operand row, tap / k position in soffset) ----
   const int lr = lane >> 3, lq = lane & 7;
@@ -267,9 +269,10 @@ __global__ __launch_bounds__(NTHR, 2) void gemm8_kernel(const GemmParams p, int 
 #pragma unroll
   for (int j = 0; j < NT; ++j) bv[j] = float4_t{0.f, 0.f, 0.f, 0.f};
   if (p.bias) {
+    const half_t* const bias_t = p.bias + bias_off;
 #pragma unroll
     for (int j = 0; j < NT; ++j) {
-      const half4_t b = ld_half4(p.bias + n0 + wn * WN + j * 16 + g * 4);
+      const half4_t b = ld_half4(bias_t + n0 + wn * WN + j * 16 + g * 4);
       bv[j] = float4_t{(float)b[0], (float)b[1], (float)b[2], (float)b[3]};
     }
   }
@@ -415,6 +418,7 @@ int gemm8_tile(const GemmParams& p, int mode) {
   const bool hilo = p.c_lo || p.res_lo;      // accuracy mode: the 256 x 320 tile has the hi / lo epilogue, the rest is gemm2.hip's
   if (hilo && (mode != MODE_S1 || !p.c_lo || (p.res != nullptr) != (p.res_lo != nullptr))) return 0;
   if (p.ntaps || p.up2 || p.seg_rows) return 0;        // polyphase upsample / segmented rows: gemm2.hip's tap walk / row map
+  if (p.bias_pitch && (p.gn_hw <= 0 || p.gn_hw % BM != 0)) return 0;      // a bias row per sample on tiles that span samples: gemm2.hip's per-row lookup
   if (p.ldc % 4 != 0 || (p.res && p.ldr % 4 != 0)) return 0;
   unsigned long long a, b, s;
   if (!operand_bytes(p, mode, a, b, s)) return 0;

@@ -45,8 +45,14 @@ struct GemmParams {
   // tile tickets of the self-finishing split-K launch (gemm2_splitk_kernel): SKG_WS_TICKET_BYTES at the end of the registered
   // workspace, zeroed at registration and left zero by every launch (nullptr: the launch is followed by splitk_reduce_kernel)
   unsigned* ws_cnt;
+  // a bias row per sample (SKG_EPI_BIAS_ROWS, the 3x3 convolutions): bias is [rows][bias_pitch] and output row m reads bias row
+  // m / gn_hw (gn_hw = OH * OW, set by every conv launch; the Winograd output transform knows its sample anyway) (0 = one shared [N] row)
+  int bias_pitch;
 };
 constexpr unsigned SKG_FLAG_GN_STATS = 0x8000u;      // internal: set by the launcher when the chosen kernel fuses them
+// internal: set by the launcher of a tile kernel when a tile of a bias_pitch launch can span samples (gn_hw % BM != 0): the epilogue
+// looks the bias row up per output row instead of once per workgroup
+constexpr unsigned SKG_FLAG_BIAS_PER_ROW = 0x20000u;
 
 // v2 (gemm2.hip): returns true and launches if the shape is eligible, false otherwise (nothing launched).
 bool skg_gemm2_try_launch(const GemmParams& p, int mode, hipStream_t st);

@@ -93,7 +93,7 @@ __global__ __launch_bounds__(256) void wino_out_kernel(GemmParams p, const float
   const long r = mt / ((long)TW * TH);
   float4_t bias = {0.f, 0.f, 0.f, 0.f};
   if (p.bias) {
-    const half4_t b = ld_half4(p.bias + n);
+    const half4_t b = ld_half4(p.bias + (p.bias_pitch ? (size_t)r * p.bias_pitch : 0) + n);      // (r: the tile's sample)
     bias = float4_t{(float)b[0], (float)b[1], (float)b[2], (float)b[3]};
   }
 #pragma unroll

@@ -158,12 +158,19 @@ def add_noise(latents: torch.Tensor, noise: torch.Tensor, timesteps: Sequence[in
 
 
 @torch.no_grad()
-def unet_taps(net, noisy_latents: torch.Tensor, timesteps: Sequence[int], ehs: torch.Tensor):
+def unet_taps(net, noisy_latents: torch.Tensor, timesteps: Sequence[int], ehs: torch.Tensor, batched: bool = False):
     """The nine hooked feature maps (modules/latent_predictor.py:47-81) of a frozen UNet forward, one sample at a
     time because every sample has its own timestep (trainer.py:212) and the time-embedding bias is folded into the
-    conv epilogues per launch.  Returns [(fp16 [B*s*s, C], s)] x 9."""
+    conv epilogues per launch.  Returns [(fp16 [B*s*s, C], s)] x 9.
+    batched=True: ONE walk of B rows with a timestep per sample (HipUNet.forward's per-sample form: conv1 of every
+    ResnetBlock reads a bias row per sample) - the reference's own unet(noisy_latents, timesteps, ehs)."""
     from .unet import CIN_PAD
     B, _, h, _ = noisy_latents.shape
+    if batched:
+        net.prepare_context(ehs)
+        x32 = ops.nchw_to_nhwc(noisy_latents.to(net.dev, torch.float32).contiguous(), CIN_PAD)
+        _, taps = net.forward(x32, [int(t) for t in timesteps], B, h, None, want_taps=True, want_eps=False)
+        return [(t.contiguous(), s) for t, s in taps]
     per_tap: List[List[torch.Tensor]] = [[] for _ in range(9)]
     sizes: List[int] = []
     for b in range(B):
@@ -178,12 +185,12 @@ def unet_taps(net, noisy_latents: torch.Tensor, timesteps: Sequence[int], ehs: t
 
 @torch.no_grad()
 def train_step(trainer: HipLGPTrainer, net, latents: torch.Tensor, sketch_latents: torch.Tensor, ehs: torch.Tensor,
-               timesteps: Sequence[int], noise: torch.Tensor, alphas_cumprod: torch.Tensor):
+               timesteps: Sequence[int], noise: torch.Tensor, alphas_cumprod: torch.Tensor, batched: bool = False):
     """trainer.py:208-246 for one batch: noise the latents, frozen UNet forward, LGP loss + gradients, gradient
-    all-reduce across ranks, AdamW.  Returns the loss (0-dim tensor)."""
+    all-reduce across ranks, AdamW.  Returns the loss (0-dim tensor).  batched: see unet_taps."""
     noisy, noise_level = add_noise(latents.to(trainer.dev, torch.float32), noise.to(trainer.dev, torch.float32),
                                    timesteps, alphas_cumprod)
-    taps = unet_taps(net, noisy, timesteps, ehs)
+    taps = unet_taps(net, noisy, timesteps, ehs, batched=batched)
     loss, g = trainer.loss_and_grads(taps, noise_level, sketch_latents)
     trainer.all_reduce(g)
     trainer.step(g)

@@ -91,7 +91,8 @@ class UNetFacade:
     def __call__(self, sample, timestep, encoder_hidden_states, **kwargs):
         """UNet2DConditionModel-style call (evaluation.py:94): sample (rows,4,h,w) in the row order
         [uncond rows; cond rows], returns an object with ``.sample`` (fp32 NCHW epsilon).  Fills the hooked
-        feature taps (hook_unet) like the reference's forward hooks do."""
+        feature taps (hook_unet) like the reference's forward hooks do.  timestep: a scalar / one-element tensor, or - the
+        trainers' call - a tensor or sequence with one timestep per row (HipUNet.forward's per-sample form)."""
         from .. import ops
         from ..unet import CIN_PAD
         rows, _, h, w = sample.shape
@@ -100,7 +101,11 @@ class UNetFacade:
             net.prepare_context(encoder_hidden_states)
             net.ctx["src"] = encoder_hidden_states
         x32 = ops.nchw_to_nhwc(sample.to(self._device, torch.float32).contiguous(), CIN_PAD)
-        eps, taps = net.forward(x32, int(timestep), rows, h, W=w)
+        if isinstance(timestep, (list, tuple)) or (torch.is_tensor(timestep) and timestep.numel() > 1):
+            t = timestep.reshape(-1).to(torch.long) if torch.is_tensor(timestep) else list(timestep)
+        else:
+            t = int(timestep)
+        eps, taps = net.forward(x32, t, rows, h, W=w)
         if self._feature_taps is not None:
             for tp, (t, s) in zip(self._feature_taps, taps):
                 tp._nhwc = (t, rows, s)

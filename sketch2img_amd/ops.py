@@ -14,7 +14,7 @@ import torch
 
 from ._lib import SkgError, SkgTap, check, lib
 
-EPI_RELU, EPI_OUT_F32, EPI_GEGLU = 1, 2, 4
+EPI_RELU, EPI_OUT_F32, EPI_GEGLU, EPI_BIAS_ROWS = 1, 2, 4, 8
 CONV_S1, CONV_S2, CONV_UP2, CONV_S2T, CONV_S2A = 0, 1, 2, 3, 4
 ATTN_CAUSAL, ATTN_ROWV, ATTN_RESIDENT_KV = 1, 2, 4
 
@@ -141,6 +141,16 @@ class Pair:
     def empty(M: int, C: int, dev) -> "Pair":
         buf = torch.empty(M, 2 * C, device=dev, dtype=torch.float16)
         return Pair(buf[:, :C], buf[:, C:], buf)
+
+
+def _bias_rows_flag(bias: Optional[torch.Tensor], rows: int, Cout: int) -> int:
+    """EPI_BIAS_ROWS for a 2-D bias of a 3x3 convolution - one [Cout] row per sample, [rows, Cout] contiguous - and 0 for the shared
+    1-D one.  Any other shape raises ValueError before the C call."""
+    if bias is None or bias.dim() == 1:
+        return 0
+    if bias.dim() != 2 or tuple(bias.shape) != (rows, Cout) or not bias.is_contiguous():
+        raise ValueError(f"bias per sample: a contiguous [rows = {rows}, Cout = {Cout}] tensor expected, got {tuple(bias.shape)}")
+    return EPI_BIAS_ROWS
 
 
 def gn_fusable(M: int, N: int, HW: int, groups: int) -> bool:
@@ -283,10 +293,12 @@ def conv3x3(X: torch.Tensor, Wp: torch.Tensor, rows: int, IH: int, IW: int, mode
             relu: bool = False, gn_groups: Optional[int] = None, out_lo=None, residual_lo=None):
     """X [rows*IH*IW, Cin] (view), Wp [Cout, 9*Cin] tap-major.  Returns [rows*OH*OW, Cout];
     gn_groups=G: (out, GNPartial) - the GroupNorm partial sums of the output come with it.
+    bias: [Cout], or [rows, Cout] - a row per sample (EPI_BIAS_ROWS: output row m adds bias[m // (OH*OW)]).
     out_lo / residual_lo (accuracy mode): see gemm."""
-    _f16(X, Wp, bias, residual, out_lo, residual_lo)
     Cin = X.shape[1]
     Cout = Wp.shape[0]
+    brows = _bias_rows_flag(bias, rows, Cout)
+    _f16(X, Wp, bias, residual, out_lo, residual_lo)
     assert Wp.shape[1] == 9 * Cin and Wp.is_contiguous() and X.shape[0] == rows * IH * IW
     if mode == CONV_S1:
         OH, OW = IH, IW
@@ -302,7 +314,7 @@ def conv3x3(X: torch.Tensor, Wp: torch.Tensor, rows: int, IH: int, IW: int, mode
     part = GNPartial(rows, OH * OW, gn_groups, X.device) if gn_groups is not None else None
     check(lib.skg_conv3x3_f16(_p(X), _ld(X), _p(Wp), _p(out), _p(out_lo), _ld(out), rows, IH, IW, Cin, Cout, mode,
                               _p(bias), _p(residual), _p(residual_lo), _ld(r_any) if r_any is not None else 0,
-                              alpha, EPI_RELU if relu else 0, _p(part.buf) if part is not None else None, gn_groups or 0,
+                              alpha, (EPI_RELU if relu else 0) | brows, _p(part.buf) if part is not None else None, gn_groups or 0,
                               _stream()), "skg_conv3x3_f16")
     return out if part is None else (out, part)
 
@@ -342,9 +354,11 @@ def conv3x3_wino(X: Optional[torch.Tensor], U: torch.Tensor, rows: int, IH: int,
                  residual=None, relu: bool = False, out_lo=None, residual_lo=None, V: Optional[torch.Tensor] = None):
     """3x3 stride-1 convolution by Winograd F(2x2, 3x3) (skg_conv3x3_wino_f16): X [rows*IH*IW, Cin] (view), U [Cout, 16*Cin] =
     packs.pack_conv_wino(weight).  Returns [rows*IH*IW, Cout].  Raises SkgError(rc = -2) when declined (odd map, Cin % 64, no room for the
-    16 fp32 slabs in the stream's workspace): the caller runs conv3x3.  X = None, V = groupnorm_wino(...)[0]: the input transform exists."""
-    _f16(X, U, bias, residual, out_lo, residual_lo, V)
+    16 fp32 slabs in the stream's workspace): the caller runs conv3x3.  X = None, V = groupnorm_wino(...)[0]: the input transform exists.
+    bias: [Cout], or [rows, Cout] - a row per sample, as conv3x3."""
     Cout = U.shape[0]
+    brows = _bias_rows_flag(bias, rows, Cout)
+    _f16(X, U, bias, residual, out_lo, residual_lo, V)
     Cin = U.shape[1] // 16
     Mt = rows * (IH // 2) * (IW // 2)
     if X is None:
@@ -361,7 +375,7 @@ def conv3x3_wino(X: Optional[torch.Tensor], U: torch.Tensor, rows: int, IH: int,
     r_any = residual if residual is not None else residual_lo
     st = _stream()
     check(lib.skg_conv3x3_wino_f16(_p(X), _ld(X) if X is not None else 0, _p(U), _p(V), _p(out), _p(out_lo), _ld(out), rows, IH, IW, Cin, Cout, _p(bias),
-                                   _p(residual), _p(residual_lo), _ld(r_any) if r_any is not None else 0, EPI_RELU if relu else 0, st),
+                                   _p(residual), _p(residual_lo), _ld(r_any) if r_any is not None else 0, (EPI_RELU if relu else 0) | brows, st),
           "skg_conv3x3_wino_f16")
     return out
 

@@ -177,6 +177,29 @@ def _produce(fn: str, *args, out=None, residual=None, gn: Optional[Tuple[int, in
     return (out if isinstance(out, ops.Pair) else o), part
 
 
+def per_sample_timesteps(t, rows: int, shared_input: bool = False):
+    """What HipUNet.forward makes of its `t`: an int for one timestep shared by all rows (an int, or a sequence / 1-D integer tensor
+    of `rows` equal entries), else the list of `rows` ints - a timestep per sample.  ValueError: a length other than `rows`, or
+    shared_input (the two halves of the batch are identical) with halves whose timesteps differ row for row."""
+    if torch.is_tensor(t):
+        if t.dim() == 0:
+            return int(t)
+        if t.dim() != 1 or t.dtype.is_floating_point or t.dtype == torch.bool:
+            raise ValueError(f"timesteps: an int or a 1-D integer tensor of length rows expected, got {tuple(t.shape)} {t.dtype}")
+        ts = [int(v) for v in t.tolist()]
+    elif isinstance(t, (list, tuple)):
+        ts = [int(v) for v in t]
+    else:
+        return int(t)
+    if len(ts) != rows:
+        raise ValueError(f"timesteps: {len(ts)} entries for {rows} rows")
+    if all(v == ts[0] for v in ts):
+        return ts[0]
+    if shared_input and (rows % 2 or ts[: rows // 2] != ts[rows // 2:]):
+        raise ValueError("shared_input: the two halves of the batch must carry equal timesteps row for row")
+    return ts
+
+
 def _layernorm(v, gamma, beta, **kw):
     """LayerNorm of a value of either representation (a pair is normalised as hi + lo) -> fp16."""
     return ops.layernorm_hilo(v.hi, v.lo, gamma, beta, **kw) if isinstance(v, ops.Pair) else ops.layernorm(v, gamma, beta, **kw)
@@ -265,6 +288,9 @@ class HipUNet:
         self._sd_time = {k: v for k, v in state_dict.items()
                          if k.startswith("time_embedding.") or ".time_emb_proj." in k or k.endswith("conv1.bias")}
         self.tbias: Dict[int, Dict[str, torch.Tensor]] = {}
+        # the same rows as ONE [T, Cout] table per resnet (row tbias_row[t]): a timestep per sample is one gather per resnet
+        self.tbias_tab: Dict[str, torch.Tensor] = {}
+        self.tbias_row: Dict[int, int] = {}
         self.ctx: Optional[dict] = None
         self.inject: Optional[Callable] = None      # set by modules.*_guided_attn.SatMixin
 
@@ -477,7 +503,7 @@ class HipUNet:
         (diffusers get_timestep_embedding(flip_sin_to_cos=True, shift 0) -> TimestepEmbedding ->
         ResnetBlock2D.time_emb_proj(silu(.))), folded with conv1.bias."""
         cfg, W = self.cfg, self.W
-        ts = [int(t) for t in timesteps if int(t) not in self.tbias]
+        ts = list(dict.fromkeys(int(t) for t in timesteps if int(t) not in self.tbias))
         if not ts:
             return
         c0 = cfg.block_out_channels[0]
@@ -498,6 +524,9 @@ class HipUNet:
                 fused = ops.axpby(proj, W[p + ".conv1.bias"].expand(len(ts), -1).contiguous())
                 for i, t in enumerate(ts):
                     out[t][p] = fused[i].contiguous()
+                self.tbias_tab[p] = torch.cat([self.tbias_tab[p], fused]) if p in self.tbias_tab else fused
+        for t in ts:
+            self.tbias_row[t] = len(self.tbias_row)
         self.tbias.update(out)
 
     def prepare_context(self, ehs: torch.Tensor):
@@ -837,11 +866,16 @@ class HipUNet:
             ops.conv3x3(self._full_of(h), W[wk + ":2"], rows, *sz, ops.CONV_UP2, out=out.hi, out_lo=out.lo, bias=b)
         return out
 
-    def forward(self, x32: torch.Tensor, t: int, rows: int, H: int, stash: Optional[Stash] = None,
+    def forward(self, x32: torch.Tensor, t, rows: int, H: int, stash: Optional[Stash] = None,
                 want_taps: bool = True, want_eps: bool = True, down_only: bool = False, shared_input: bool = False,
                 on_taps: Optional[Callable] = None, W: Optional[int] = None):
         """x32: fp16 [rows*H*W, 32] (latent channels zero-padded; W defaults to H).  Returns (eps [rows*H*W, 8] or None,
         taps: list of 9 (tensor [rows*s*s, C], s)) - on a non-square map (tensor [rows*sh*sw, C], (sh, sw)).
+
+        t: one timestep for all rows (an int), or a sequence / 1-D integer tensor of `rows` timesteps, one per sample - the trainers'
+        unet(noisy_latents, timesteps, ehs).  The time projection folded into conv1.bias of every ResnetBlock then is a [rows, Cout]
+        stack, one gather per resnet, and conv1's epilogue reads a bias row per sample (ops.conv3x3 / conv3x3_wino with a 2-D bias);
+        nothing else in the walk depends on t.  Equal entries take the int path.
 
         shared_input: the caller guarantees that the two halves of x32 are IDENTICAL - the CFG-doubled batch of
         modules/pipeline.py:85, `torch.cat([latents] * 2)`.  The two halves of the evaluation then only differ from the
@@ -872,11 +906,16 @@ class HipUNet:
             self.inject.check_rows(rows)
         if sz[0] != sz[1]:
             self._check_rect(sz)
-        self.prepare_timesteps([t])
+        t = per_sample_timesteps(t, rows, shared_input)
+        self.prepare_timesteps(sorted(set(t)) if isinstance(t, list) else [t])
         assert not (down_only and self.residual_fp32), "accuracy mode: the whole UNet (with or without a stash, with or without an injector)"
         if stash is not None:
             stash.misc.update(rows=rows, H=H, W=sz[1])
-        tb = self.tbias[int(t)]
+        if isinstance(t, list):      # a timestep per sample: every resnet's bias rows in row order, one gather per resnet
+            idx = torch.tensor([self.tbias_row[v] for v in t], device=self.dev)
+            tb = {p: tab.index_select(0, idx) for p, tab in self.tbias_tab.items()}
+        else:
+            tb = self.tbias[t]
         boc = cfg.block_out_channels
         nb, lpb, lpb1 = len(boc), cfg.layers_per_block, cfg.layers_per_block + 1
         cats = _ConcatBuffers(self, rows, down_only)
@@ -893,7 +932,8 @@ class HipUNet:
             _copy_up(hc, slot, M1)
             cats.push(slot, self._dup_partial(hp1))
             x_full = _fresh(slot, 2 * M1, boc[0])
-            h1, hp1 = res("down_blocks.0.resnets.0", hc, S1, cur, tb, stash, out=_rows_of(x_full, M1, 2 * M1), xpart=hp1,
+            p0 = "down_blocks.0.resnets.0"      # (a timestep per sample: the halves' timesteps are equal row for row - the cond rows' stack)
+            h1, hp1 = res(p0, hc, S1, cur, {p0: tb[p0][S1:]} if isinstance(t, list) else tb, stash, out=_rows_of(x_full, M1, 2 * M1), xpart=hp1,
                           want_part=True, half=True)
             _copy_up(h1, x_full, M1)
             h, hp = tr("down_blocks.0.attentions.0", h1, rows, cur, cfg.num_heads[0], stash, out=cats.skip_slot(boc[0], cur),
