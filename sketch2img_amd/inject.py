@@ -229,7 +229,10 @@ class HipClipInjectorTrain:
     backward(d out) -> d h (the residual path added), the gradients of the block's 12 tensors accumulated (+=, scaled like
     d out) into the flat fp32 vector handed to begin(), and d loss / d state += ds . W_proj (fp32 [T, 1024]): the seam where a
     CLIP-vision backward can attach.  Weight gradients: ops.wgrad on the row-major operands (column views of qkv / d qkv), bias
-    gradients in the same pass, LayerNorm's through ops.layernorm_param_grads."""
+    gradients in the same pass, LayerNorm's through ops.layernorm_param_grads.
+
+    begin() with [B, T, 1024] tensors: the same block on B samples in one walk (rows = B, HipUNet.forward(diff_from=0)) - see
+    _call_batched for the layout.  The one-sample form keeps its launches."""
 
     def __init__(self, cfg: UNetConfig, w16, grad_view, device):
         """w16(key) -> fp16 view of the working copy; grad_view(flat, key) -> fp32 view (state-dict key names)."""
@@ -241,6 +244,7 @@ class HipClipInjectorTrain:
         self.stash: Dict[str, dict] = {}
         self.g: Optional[torch.Tensor] = None
         self.dstate: Optional[torch.Tensor] = None
+        self.batch: Optional[int] = None
         self.packs: Dict[str, dict] = {}
 
     def set_scale(self, scale: float):
@@ -258,22 +262,29 @@ class HipClipInjectorTrain:
                                     wp=wp, wpT=ops.transpose(wp))
 
     def begin(self, state16: torch.Tensor, g: torch.Tensor, dstate: torch.Tensor):
-        """One sample: its sketch tokens fp16 [T, 1024], the flat gradient vector to accumulate into, its d state [T, 1024] fp32."""
-        assert state16.dtype == torch.float16 and state16.dim() == 2 and state16.shape[1] == CLIP_DIM
+        """One sample: its sketch tokens fp16 [T, 1024], the flat gradient vector to accumulate into, its d state [T, 1024] fp32.
+        B samples in one UNet walk (rows = B): state16 fp16 [B, T, 1024] and d state fp32 [B, T, 1024] (B = 1 included)."""
+        assert state16.dtype == torch.float16 and state16.dim() in (2, 3) and state16.shape[-1] == CLIP_DIM
+        assert dstate.dtype == torch.float32 and dstate.shape == state16.shape, "d state: fp32, the shape of the state"
+        assert state16.dim() == 2 or dstate.is_contiguous()
+        self.batch = state16.shape[0] if state16.dim() == 3 else None      # None: the one-sample form
         self.state16, self.g, self.dstate, self.stash = state16.contiguous(), g, dstate, {}
 
     def end(self):
-        self.state16 = self.g = self.dstate = None
+        self.state16 = self.g = self.dstate = self.batch = None
         self.stash = {}
 
     def check_rows(self, rows: int) -> None:
         """The injectors' protocol (HipInjector.check_rows): HipUNet.forward calls this before its first launch.  begin() holds the
-        tokens of one sample, so the evaluation has one row."""
-        if rows != 1:
-            raise ValueError(f"the training injector holds the sketch tokens of 1 sample, the UNet evaluates {rows} rows")
+        tokens of one sample, so the evaluation has one row - or of B samples ([B, T, 1024]), one row each."""
+        have = 1 if self.batch is None else self.batch
+        if rows != have:
+            raise ValueError(f"the training injector holds the sketch tokens of {have} sample{'s' * (have != 1)}, the UNet evaluates {rows} rows")
 
     # ---- forward (HipUNet._tr_fwd calls this) ---------------------------------------------------------------------------------
     def __call__(self, path: str, h, rows: int, N: int, heads: int, cond_only: bool = False, out=None):
+        if self.batch is not None:
+            return self._call_batched(path, h, rows, N, heads, cond_only, out)
         assert rows == 1 and not cond_only and not isinstance(h, ops.Pair), "training evaluates one all-fp16 sample at a time"
         n, C, hd = self.dims[path]
         assert hd == heads and h.shape == (N, C)
@@ -296,6 +307,8 @@ class HipClipInjectorTrain:
 
     # ---- backward (HipUNet._tr_bwd calls this through backward_eps(inject_bwd=)) ---------------------------------------------------
     def backward(self, path: str, dout):
+        if self.batch is not None:
+            return self._backward_batched(path, dout)
         n, C, heads = self.dims[path]
         s, pk, w = self.stash.pop(path), self.packs[path], self.w16
         N, T = s["N"], self.state16.shape[0]
@@ -325,3 +338,74 @@ class HipClipInjectorTrain:
         ops.wgrad(ds, self.state16, gv("sketch_proj.weight"), gv("sketch_proj.bias"), **acc)
         self.dstate += ops.gemm(ds, pk["wpT"], out_f32=True)
         return ops.axpby(dx[:N], dout)
+
+    # ---- B samples in one walk (begin() with [B, T, 1024]) ------------------------------------------------------------------------
+    # Image rows h [B N, C] and token rows s [B T, C] stay two contiguous tensors - LayerNorm is per row, so the concatenated x is
+    # never built.  K / V of both are gathered per sample into ONE zeroed buffer [B L, 2C], L = ceil8(N + T): sample b's image keys
+    # in rows [b L, b L + N), its sketch keys behind them, the pad rows zero and masked by Nkv < kv_stride.  The attention trio runs
+    # with batch = B; every weight gradient contracts over all samples' rows in one launch per operand pair (to_k / to_v: one over
+    # the image rows and one over the token rows, in that fixed order): no atomics, bit-repeatable.
+    def _call_batched(self, path: str, h, rows: int, N: int, heads: int, cond_only: bool, out):
+        B = self.batch
+        assert rows == B and not cond_only and not isinstance(h, ops.Pair), "batched training evaluates B all-fp16 samples, one row each"
+        n, C, hd = self.dims[path]
+        assert hd == heads and h.shape == (B * N, C)
+        pk, w = self.packs[path], self.w16
+        T = self.state16.shape[1]
+        NT, L = N + T, (N + T + 7) // 8 * 8
+        dh = C // heads
+        ng, nb = w(f"{n}.sketch_norm.weight"), w(f"{n}.sketch_norm.bias")
+        s = ops.gemm(self.state16.view(B * T, CLIP_DIM), pk["wp"], bias=w(f"{n}.sketch_proj.bias"))
+        zh, sth = ops.layernorm(h, ng, nb, want_stats=True)
+        zs, sts = ops.layernorm(s, ng, nb, want_stats=True)
+        qkv = ops.gemm(zh, pk["wqkv"])                               # [B N, 3C]: q of the image rows (the only queries), their k | v
+        kvs = ops.gemm(zs, pk["wqkv"][C:])                           # [B T, 2C]: k | v of the sketch tokens
+        kv = torch.zeros(B * L, 2 * C, device=self.dev, dtype=torch.float16)
+        ops.batch_copy(qkv[:, C:], N, kv, L, B, N)
+        ops.batch_copy(kvs, T, kv[N:], L, B, T)
+        q = qkv[:, :C]
+        a, lse = ops.attn_fwd(q, kv[:, :C], kv[:, C:], B, heads, N, NT, L, dh, dh ** -0.5, want_lse=True, v_rows=True)
+        o = ops.gemm(a, pk["wo"], bias=w(f"{n}.sketch_attn.to_out.0.bias"))
+        res = ops.gemm(o, pk["wc"], out, bias=w(f"{n}.sketch_conv.bias"), residual=h, alpha=self.scale)
+        self.stash[path] = dict(h=h, s=s, sth=sth, sts=sts, zh=zh, zs=zs, q=q, kv=kv, a=a, lse=lse, o=o, N=N, L=L, heads=heads)
+        return res
+
+    def _backward_batched(self, path: str, dout):
+        n, C, heads = self.dims[path]
+        st, pk, w = self.stash.pop(path), self.packs[path], self.w16
+        B, T, N, L = self.batch, self.state16.shape[1], st["N"], st["L"]
+        NT = N + T
+        dh = C // heads
+        sc = dh ** -0.5
+        gv = lambda k: self.grad_view(self.g, f"{n}.{k}")
+        acc = dict(accumulate=True)
+        if "wkvT" not in pk:      # (the token rows' d z = d[k | v] . [Wk ; Wv]: built on first use, refresh() drops it with the rest)
+            pk["wkvT"] = ops.transpose(pk["wqkv"][C:])
+        kv, zh, zs = st["kv"], st["zh"], st["zs"]
+        # out = h + scale * (o . Wc^T + bc)
+        ops.wgrad(dout, st["o"], gv("sketch_conv.weight"), gv("sketch_conv.bias"), alpha=self.scale, **acc)
+        do = ops.gemm(dout, pk["wcT"], alpha=self.scale)
+        ops.wgrad(do, st["a"], gv("sketch_attn.to_out.0.weight"), gv("sketch_attn.to_out.0.bias"), **acc)
+        da = ops.gemm(do, pk["woT"])
+        # attention: per sample the N image rows are the queries, keys / values its N + T rows of the padded buffer
+        dqkv = torch.empty(B * N, 3 * C, device=self.dev, dtype=torch.float16)
+        dkv = torch.empty(B * L, 2 * C, device=self.dev, dtype=torch.float16)      # (pad rows: never written, never read)
+        K, V = kv[:, :C], kv[:, C:]
+        _, delta = ops.attn_bwd_dq_delta(st["q"], K, V, da, st["a"], st["lse"], B, heads, N, NT, L, dh, sc, out=dqkv[:, :C])
+        ops.attn_bwd_dkv_strided(st["q"], K, V, da, st["lse"], delta, B, heads, N, NT, L, dh, sc, dkv[:, :C], dkv[:, C:])
+        ops.batch_copy(dkv, L, dqkv[:, C:], N, B, N)                 # d[k | v] of the image rows next to their d q
+        dkvs = torch.empty(B * T, 2 * C, device=self.dev, dtype=torch.float16)
+        ops.batch_copy(dkv[N:], L, dkvs, T, B, T)                    # ... and of the token rows, dense
+        ops.wgrad(dqkv[:, :C], zh, gv("sketch_attn.to_q.weight"), **acc)
+        for j, leaf in ((0, "sketch_attn.to_k.weight"), (1, "sketch_attn.to_v.weight")):
+            ops.wgrad(dqkv[:, (1 + j) * C:(2 + j) * C], zh, gv(leaf), **acc)
+            ops.wgrad(dkvs[:, j * C:(1 + j) * C], zs, gv(leaf), **acc)
+        dzh = ops.gemm(dqkv, pk["wqkvT"])
+        dzs = ops.gemm(dkvs, pk["wkvT"])
+        ng = w(f"{n}.sketch_norm.weight")
+        ops.layernorm_param_grads(st["h"], dzh, st["sth"], gv("sketch_norm.weight"), gv("sketch_norm.bias"), **acc)
+        ops.layernorm_param_grads(st["s"], dzs, st["sts"], gv("sketch_norm.weight"), gv("sketch_norm.bias"), **acc)
+        ds = ops.layernorm_bwd(st["s"], dzs, ng, st["sts"])
+        ops.wgrad(ds, self.state16.view(B * T, CLIP_DIM), gv("sketch_proj.weight"), gv("sketch_proj.bias"), **acc)
+        self.dstate += ops.gemm(ds, pk["wpT"], out_f32=True).view(B, T, CLIP_DIM)
+        return ops.layernorm_bwd(st["h"], dzh, ng, st["sth"], residual=dout)

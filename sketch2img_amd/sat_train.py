@@ -5,11 +5,16 @@ modules/clip_guided_trainer.py:203-236).
     loss = mse(unet(noisy, t, ehs), noise)  ->  backward through the whole UNet into the 16 injected modules  ->
     gradient all-reduce across ranks (DDP, bucket_cap_mb = 15)  ->  AdamW, cosine_with_restarts schedule.
 
-How it runs here: one sample at a time (rows = 1) - every sample has its own timestep and the time-embedding bias is folded
+How it runs here by default: one sample at a time (rows = 1) - every sample has its own timestep and the time-embedding bias is folded
 into the conv epilogues per launch - with a Stash, so every block takes the unfused stashing launches; the injector is
 inject.HipClipInjectorTrain (forward with stash, backward with weight gradients); the backward is HipUNet.backward_eps.  The
 gradients of the B samples accumulate (+=) inside one flat fp32 vector; the loss and its seed come from ONE launch over the
 whole batch (skg_lgp_mse_train: the same [B*hw, >= 4] / NCHW layouts), so the seed carries 1 / numel of the whole batch.
+
+batched=True (opt-in, every entry point below): the reference's call form - ONE UNet walk at rows = B with a timestep per row
+(a bias row per sample in conv1's epilogue), a stash of every row (HipUNet.forward(diff_from=0)), the injector on B token sets
+(image rows and token rows as two tensors, K / V gathered per sample into one padded buffer, the attention trio at batch = B, every
+weight gradient contracted over all samples' rows) and one backward_eps over all rows.  Same values to rounding, not to the bit.
 
 What differs from the reference, on purpose (as in lgp_train.py): accelerate's fp16 autocast + GradScaler becomes fp16 compute
 with a STATIC power-of-two loss scale and fp32 master weights; bitsandbytes' AdamW8bit becomes plain fp32 AdamW with the same
@@ -97,18 +102,23 @@ class HipSatTrainer(FlatAdamW):
     # ------------------------------------------------------------------------------------------ fwd + bwd
     @torch.no_grad()
     def loss_and_grads(self, net, latents: torch.Tensor, noise: torch.Tensor, timesteps: Sequence[int], ehs: torch.Tensor,
-                       sketch_state: torch.Tensor, alphas_cumprod: torch.Tensor, loss_scale: float = LOSS_SCALE):
+                       sketch_state: torch.Tensor, alphas_cumprod: torch.Tensor, loss_scale: float = LOSS_SCALE, batched: bool = False):
         """latents, noise fp32 [B, 4, h, h]; timesteps: B ints; ehs [B, L, D] (L = 77, or 78 ... 231 from encode_tokens); sketch_state [B, T, 1024].
         loss_scale: a power of two (step() divides by LOSS_SCALE: leave the default unless the caller rescales itself).
         Returns (loss, flat fp32 gradient x LOSS_SCALE in the layout of the master vector, d loss / d sketch_state x LOSS_SCALE
-        fp32 [B, T, 1024])."""
-        fw = self.forward_batch(net, latents, noise, timesteps, ehs, sketch_state, alphas_cumprod, loss_scale)
-        return self.backward_batch(net, fw)
+        fp32 [B, T, 1024]).
+        batched: the whole batch in ONE UNet walk - the reference's unet(noisy_latents, timesteps, encoder_hidden_states) - instead of
+        one rows = 1 evaluation per sample: the same values to rounding (other kernel instantiations), B >= 1."""
+        fw = self.forward_batch(net, latents, noise, timesteps, ehs, sketch_state, alphas_cumprod, loss_scale, batched=batched)
+        return self.backward_batch(net, fw, batched=batched)
 
     @torch.no_grad()
-    def forward_batch(self, net, latents, noise, timesteps, ehs, sketch_state, alphas_cumprod, loss_scale: float = LOSS_SCALE):
+    def forward_batch(self, net, latents, noise, timesteps, ehs, sketch_state, alphas_cumprod, loss_scale: float = LOSS_SCALE,
+                      batched: bool = False):
         """The stashing forward of every sample, the loss and its seed (the loss is a mean over the whole batch, so all
-        forwards come first).  Returns what backward_batch consumes."""
+        forwards come first).  Returns what backward_batch consumes (with the same `batched`).
+        batched: one prepare_context, one stashing forward at rows = B with a timestep per row and diff_from = 0 (every row is
+        differentiated), the injector holding all B token sets."""
         from .unet import CIN_PAD, Stash
         if net.residual_fp32:
             raise NotImplementedError("HipSatTrainer: the accuracy mode (residual_fp32) is not supported - build the HipUNet "
@@ -129,6 +139,17 @@ class HipSatTrainer(FlatAdamW):
         prev = net.inject
         net.inject = self.injector
         try:
+            if batched:
+                if len(timesteps) != B:
+                    raise ValueError(f"timesteps: {len(timesteps)} entries for {B} samples")
+                net.prepare_context(ehs)
+                x32 = ops.nchw_to_nhwc(noisy.contiguous(), CIN_PAD)
+                stash = Stash()
+                self.injector.begin(state16, g, dstate)
+                eps, _ = net.forward(x32, [int(t) for t in timesteps], B, h, stash, want_taps=False, want_eps=True, diff_from=0)
+                loss, seed = mse_seed(eps, noise, B, h, loss_scale)
+                return dict(loss=loss, seed=seed, kept=[(stash, self.injector.stash, net.ctx)], g=g, dstate=dstate, state16=state16,
+                            hw=hw)
             eps_all = torch.empty(B * hw, 8, device=dev, dtype=torch.float16)
             kept = []
             for b in range(B):
@@ -146,12 +167,20 @@ class HipSatTrainer(FlatAdamW):
         return dict(loss=loss, seed=seed, kept=kept, g=g, dstate=dstate, state16=state16, hw=hw)
 
     @torch.no_grad()
-    def backward_batch(self, net, fw: dict):
-        """HipUNet.backward_eps of every sample into the flat gradient vector.  -> (loss, g, d sketch_state)."""
+    def backward_batch(self, net, fw: dict, batched: bool = False):
+        """HipUNet.backward_eps of every sample into the flat gradient vector.  -> (loss, g, d sketch_state).
+        batched (fw from forward_batch(batched=True)): one backward_eps over all rows."""
         g, dstate, kept, hw = fw["g"], fw["dstate"], fw["kept"], fw["hw"]
         prev, prev_ctx = net.inject, net.ctx
         net.inject = self.injector
         try:
+            if batched:
+                (stash, istash, ctx), kept[0] = kept[0], None
+                net.ctx = ctx
+                self.injector.begin(fw["state16"], g, dstate)
+                self.injector.stash = istash
+                net.backward_eps(stash, fw["seed"], inject_bwd=self.injector.backward)
+                return fw["loss"], g, dstate
             for b in range(len(kept)):
                 stash, istash, ctx = kept[b]
                 net.ctx = ctx                                      # (the cross-attention K / V of this sample's prompt)
@@ -173,12 +202,13 @@ class HipSatTrainer(FlatAdamW):
 
 
 @torch.no_grad()
-def loss_and_grads_through_tower(trainer: HipSatTrainer, tower, net, latents, noise, timesteps, ehs, pixel_values, alphas_cumprod):
+def loss_and_grads_through_tower(trainer: HipSatTrainer, tower, net, latents, noise, timesteps, ehs, pixel_values, alphas_cumprod,
+                                 batched: bool = False):
     """HipSatTrainer.loss_and_grads fed by the tower's stashing forward, then the tower's backward from d sketch_state.
     -> (loss, SatMixin flat gradient x LOSS_SCALE, tower flat gradient x LOSS_SCALE x tower.seam_scale, d sketch_state x LOSS_SCALE)."""
     assert pixel_values is not None, "training through the tower needs pixel_values"
     tokens, kept = tower.forward_train(pixel_values)
-    loss, g, dstate = trainer.loss_and_grads(net, latents, noise, timesteps, ehs, tokens, alphas_cumprod)
+    loss, g, dstate = trainer.loss_and_grads(net, latents, noise, timesteps, ehs, tokens, alphas_cumprod, batched=batched)
     gt = tower.new_grad()
     tower.backward(kept, tower.seam(dstate), gt)
     return loss, g, gt, dstate
@@ -187,18 +217,21 @@ def loss_and_grads_through_tower(trainer: HipSatTrainer, tower, net, latents, no
 @torch.no_grad()
 def train_step(trainer: HipSatTrainer, net, latents: torch.Tensor, ehs: torch.Tensor, sketch_state: Optional[torch.Tensor],
                timesteps: Sequence[int], noise: torch.Tensor, alphas_cumprod: torch.Tensor, tower=None,
-               pixel_values: Optional[torch.Tensor] = None):
+               pixel_values: Optional[torch.Tensor] = None, batched: bool = False):
     """clip_guided_trainer.py:203-236 for one batch: noise the latents, UNet forward / backward per sample, gradient all-reduce
     across ranks, AdamW.  Returns (loss (0-dim tensor), whether the optimizer stepped, d loss / d sketch_state x LOSS_SCALE).
 
     tower (a clip_vision_train.HipClipTowerTrainer) + pixel_values [B, 3, S, S]: the sketch tokens come from the tower's stashing
     forward (sketch_state is ignored: pass None), d sketch_state goes into the tower's backward, and the two optimizers step
-    together or not at all."""
+    together or not at all.
+
+    batched: the UNet evaluates the whole batch in one walk (HipSatTrainer.loss_and_grads); everything else is unchanged."""
     if tower is None:
-        loss, g, dstate = trainer.loss_and_grads(net, latents, noise, timesteps, ehs, sketch_state, alphas_cumprod)
+        loss, g, dstate = trainer.loss_and_grads(net, latents, noise, timesteps, ehs, sketch_state, alphas_cumprod, batched=batched)
         trainer.all_reduce(g)
         return loss, trainer.step(g), dstate
-    loss, g, gt, dstate = loss_and_grads_through_tower(trainer, tower, net, latents, noise, timesteps, ehs, pixel_values, alphas_cumprod)
+    loss, g, gt, dstate = loss_and_grads_through_tower(trainer, tower, net, latents, noise, timesteps, ehs, pixel_values, alphas_cumprod,
+                                                       batched=batched)
     trainer.all_reduce(g)
     tower.all_reduce(gt)
     # one GradScaler in the reference: a non-finite gradient in either set skips both.  The verdict is taken here, once per

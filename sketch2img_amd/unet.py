@@ -18,6 +18,7 @@ Work hoisted out of the per-step loop because it does not depend on the latent:
 """
 from __future__ import annotations
 
+import functools
 import math
 import os
 from dataclasses import dataclass, field
@@ -683,12 +684,13 @@ class HipUNet:
         return out, opart
 
     def _tr_fwd(self, p, x, rows, sz, heads, stash: Optional[Stash], out=None, xpart=None, want_part=False, shared=False,
-                x_full=None):
+                x_full=None, diff_from: Optional[int] = None):
         """x: fp16 or a Pair (the pair zone): p1, p2, p3, pin and the output have its representation, q2 / qkv are fp16.
         shared: x holds the COND rows only (rows // 2 of them) of a CFG-doubled batch whose two halves are identical up
         to here (see forward): everything in front of the first text-dependent operation - GroupNorm, proj_in, the whole
         self-attention, LayerNorm 2, to_q - runs once; p1 and q2 are written into the cond half of full-size buffers and
-        copied to the uncond half (x_full: the same for x, filled by the caller)."""
+        copied to the uncond half (x_full: the same for x, filled by the caller).
+        diff_from: the first row a stash keeps for the backward (forward's diff_from; None: rows // 2)."""
         cfg, W, pair = self.cfg, self.W, isinstance(x, ops.Pair)
         HW, M = sz[0] * sz[1], rows * sz[0] * sz[1]
         C = _hi(x).shape[1]
@@ -697,7 +699,9 @@ class HipUNet:
         t = p + ".transformer_blocks.0"
         keep = stash is not None
         r1 = rows // 2 if shared else rows                    # rows of the text-independent part
-        M1, M0 = r1 * HW, (rows // 2) * HW                    # M0: the first cond row of a stashing launch
+        M1, M0 = r1 * HW, (rows // 2 if diff_from is None else diff_from) * HW      # M0: the first stashed row of a stashing launch
+        # the split / fused stashing launches: the sampler's even CFG-doubled batches, or any batch with an explicit diff_from
+        split = diff_from is not None or rows % 2 == 0
         ln = lambda v, k: _layernorm(v, W[f"{t}.{k}.weight"], W[f"{t}.{k}.bias"], want_stats=True)
         g, gst = self._norm(x, r1, HW, 1e-6, p + ".norm", False, partial=xpart)
         pin, _ = _produce("gemm", *self._operand(g, p + ".proj_in.weight", ":n2"), out=_fresh(x, M1, C), bias=W[p + ".proj_in.bias"])
@@ -722,7 +726,7 @@ class HipUNet:
                 p1 = self.inject(t, p1, rows, HW, heads)
             p1_c = p1
         cb = self.ctx["blocks"][t + ".attn2"]
-        xab = (_XATTN_BLOCK and (not keep or ((_XATTN_KEEP_HP if pair else _XATTN_KEEP) and rows % 2 == 0)) and "kvpack" in cb
+        xab = (_XATTN_BLOCK and (not keep or ((_XATTN_KEEP_HP if pair else _XATTN_KEEP) and split)) and "kvpack" in cb
                and heads in _XATTN_HEADS and HW % 128 == 0)
         xk_half = ()
         if xab:
@@ -756,7 +760,7 @@ class HipUNet:
         # C = 320: norm3 -> FF1 -> gate -> FF2 + residual in ONE row-local launch (skg_ff_block_f16[_hilo]: the row panel and the output
         # accumulators stay in registers, only weights stream).  In a guided step the same launch also stores what the backward of
         # the cond rows reads: the FF1 output (interleaved pack) and norm3's statistics
-        ffb = _FF_BLOCK and (t + ".ff.pack") in W and (not keep or (rows % 2 == 0 and _FF_KEEP))
+        ffb = _FF_BLOCK and (t + ".ff.pack") in W and (not keep or (split and _FF_KEEP))
         ffp = ffb and _FF_PROJ and (not pair or _FF_PROJ_HP) and (t + ".ff.packp") in W and HW % 128 == 0
         gn = (HW, cfg.norm_groups) if want_part and self._gn_from_producer(rows, HW, C) else None
         out = _fresh(x, M, C) if out is None else out
@@ -778,12 +782,13 @@ class HipUNet:
             w1, b1 = W[t + ".ff.net.0.proj.weight"], W[t + ".ff.net.0.proj.bias"]
             if not keep and C % 64 == 0:        # no backward will follow: gate inside the GEMM epilogue (half the bytes)
                 gg = ops.gemm(a3, w1, bias=b1, geglu=True)
-            elif C % 64 == 0 and rows % 2 == 0:
+            elif C % 64 == 0 and split:
                 # guided step: only the cond half (second half of the rows) is differentiated, so only it needs the pre-activation
                 # f: the uncond half takes the fused-GEGLU GEMM (a fifth of the bytes of GEMM + gate kernel), the cond half the
-                # same fused epilogue that also stores the pre-activation the gate's backward needs
+                # same fused epilogue that also stores the pre-activation the gate's backward needs (diff_from = 0: no first part)
                 gg = torch.empty(M, 4 * C, device=self.dev, dtype=torch.float16)
-                ops.gemm(a3[:M0], w1, bias=b1, geglu=True, out=gg[:M0])
+                if M0:
+                    ops.gemm(a3[:M0], w1, bias=b1, geglu=True, out=gg[:M0])
                 _, f = ops.gemm_geglu_keep(a3[M0:], w1, b1, out=gg[M0:])
             else:
                 f = ops.gemm(a3, w1, bias=b1)
@@ -868,7 +873,7 @@ class HipUNet:
 
     def forward(self, x32: torch.Tensor, t, rows: int, H: int, stash: Optional[Stash] = None,
                 want_taps: bool = True, want_eps: bool = True, down_only: bool = False, shared_input: bool = False,
-                on_taps: Optional[Callable] = None, W: Optional[int] = None):
+                on_taps: Optional[Callable] = None, W: Optional[int] = None, diff_from: Optional[int] = None):
         """x32: fp16 [rows*H*W, 32] (latent channels zero-padded; W defaults to H).  Returns (eps [rows*H*W, 8] or None,
         taps: list of 9 (tensor [rows*s*s, C], s)) - on a non-square map (tensor [rows*sh*sw, C], (sh, sw)).
 
@@ -890,6 +895,11 @@ class HipUNet:
         conv_out are launched - the guidance branch (LGP + backward-to-input) depends on nothing later, so the sampler can put
         it on a second stream while this one finishes eps (sampler.HipSampler.fork_guidance).
 
+        diff_from (with a stash): the first row the backward will differentiate - the stash keeps rows diff_from ... rows - 1 where
+        it keeps a part only.  None: rows // 2, the cond half of a CFG-doubled batch (or the single row of rows = 1).  0: every row,
+        the trainers' batch (backward_eps then differentiates all of them); odd row counts are fine.  An explicit value also selects
+        the split / fused stashing launches whatever the parity of rows.  Not with shared_input (ValueError).
+
         One walk for both modes.  The blocks of the `pair_levels` outermost resolution levels (none in the default mode) carry the
         residual stream as (hi, lo) pairs: the same graph, the same kernels for every contraction, pair-aware epilogues / norms
         (skg_*_hilo), the same GroupNorm statistics from the producers' epilogues and the same shared CFG front; eps then is a pair
@@ -897,6 +907,12 @@ class HipUNet:
         pairs buy, tools/eps_decompose_stream.py): the stride-2 convolution that enters the zone reads the pair and writes fp16, the
         upsampler that leaves it reads fp16 and writes a pair; skips produced inside the zone are consumed inside it (the U-Net's
         skips connect equal resolutions).  Taps always carry the fp16 (hi) tensor."""
+        if diff_from is not None:
+            if shared_input:
+                raise ValueError("diff_from: not with shared_input (the shared CFG front keeps the cond half only)")
+            if not 0 <= int(diff_from) < rows:
+                raise ValueError(f"diff_from = {diff_from}: a row index below rows = {rows} expected")
+            diff_from = int(diff_from)
         sz = (H, H if W is None else W)
         cfg, W = self.cfg, self.W
         assert self.ctx is not None and self.ctx["rows"] == rows, "call prepare_context first"
@@ -910,7 +926,7 @@ class HipUNet:
         self.prepare_timesteps(sorted(set(t)) if isinstance(t, list) else [t])
         assert not (down_only and self.residual_fp32), "accuracy mode: the whole UNet (with or without a stash, with or without an injector)"
         if stash is not None:
-            stash.misc.update(rows=rows, H=H, W=sz[1])
+            stash.misc.update(rows=rows, H=H, W=sz[1], diff_from=rows // 2 if diff_from is None else diff_from)
         if isinstance(t, list):      # a timestep per sample: every resnet's bias rows in row order, one gather per resnet
             idx = torch.tensor([self.tbias_row[v] for v in t], device=self.dev)
             tb = {p: tab.index_select(0, idx) for p, tab in self.tbias_tab.items()}
@@ -919,7 +935,8 @@ class HipUNet:
         boc = cfg.block_out_channels
         nb, lpb, lpb1 = len(boc), cfg.layers_per_block, cfg.layers_per_block + 1
         cats = _ConcatBuffers(self, rows, down_only)
-        res, tr = self._res_fwd, self._tr_fwd      # (one body each: the representation of their input - fp16 or Pair - decides)
+        res = self._res_fwd                        # (one body each: the representation of their input - fp16 or Pair - decides)
+        tr = self._tr_fwd if diff_from is None else functools.partial(self._tr_fwd, diff_from=diff_from)
         # hp: GroupNorm partial sums of h left behind by the kernel that produced it, whenever the next consumer of h is a
         # GroupNorm of the 64 x 64 / 32 x 32 levels (None otherwise: concatenated inputs, small maps)
         shared = shared_input and rows % 2 == 0 and rows >= 2 and not down_only and nb > 1 and lpb >= 1
@@ -1131,9 +1148,9 @@ class HipUNet:
 
     def backward_eps(self, stash: Stash, d_eps: torch.Tensor, inject_bwd: Optional[Callable] = None) -> Optional[torch.Tensor]:
         """Backward from the UNet's output.  d_eps: fp16 [S*H*W, EPS_SEED_LD] (first 4 channels valid, the rest zero) for the rows
-        from rows // 2 on (S = rows - rows // 2: the cond half of a CFG-doubled batch, or the single row of a rows = 1 evaluation) of
-        a forward(..., stash, want_eps=True).  conv_out's data gradient, conv_norm_out's GroupNorm + SiLU backward, then every up
-        block, the mid block and the down path.  inject_bwd: see _tr_bwd - the forward ran with an injector, whose parameter
+        from r0 = the stashed forward's diff_from on (S = rows - r0; by default rows // 2: the cond half of a CFG-doubled batch, or the
+        single row of a rows = 1 evaluation; 0: every row of a trainer's batch) of a forward(..., stash, want_eps=True).
+        conv_out's data gradient, conv_norm_out's GroupNorm + SiLU backward, then every up block, the mid block and the down path.  inject_bwd: see _tr_bwd - the forward ran with an injector, whose parameter
         gradients are the point; the chain then stops in front of down_blocks.0.attentions.0 (nothing trainable lies further
         up) and returns None.  Without an injector: d loss / d x like backward().  All-fp16 mode, square maps, eager."""
         assert self.need_backward, "built with need_backward=False: no :T packs"
@@ -1145,7 +1162,7 @@ class HipUNet:
         if sz[0] != sz[1]:
             raise NotImplementedError("backward_eps: square maps only")
         assert "out_h" in stash.misc, "the stashed forward ran without want_eps"
-        r0 = rows // 2
+        r0 = stash.misc.get("diff_from", rows // 2)
         S = rows - r0
         HW = sz[0] * sz[1]
         assert d_eps.shape == (S * HW, EPS_SEED_LD)
