@@ -475,6 +475,16 @@ int skg_lgp_mse_train(const void* out, int ldo, const float* target, void* dOut,
 int skg_adamw_step(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, void* param_f16, size_t n,
                    float lr, float beta1, float beta2, float eps, float weight_decay, int step, float inv_grad_scale,
                    void* stream);
+/* ---- dynamic loss scale (sketch2img_amd/loss_scaler.py: the reference's GradScaler) ----------------------
+ * *flag = 1.0f if any of x[0, n) is +-inf or NaN (exponent bits all ones); otherwise *flag is left alone, so several vectors
+ * OR into one flag.  reset != 0 zeroes *flag first, on the stream.  x: any 4-byte aligned pointer, n >= 1; one pass, no
+ * host synchronisation. */
+int skg_nonfinite_flag(const float* x, size_t n, float* flag, int reset, void* stream);
+/* skg_adamw_step that reads *skip_flag (device memory, e.g. skg_nonfinite_flag's) once: non-zero -> param, exp_avg,
+ * exp_avg_sq and param_f16 are left untouched; zero -> the same bits as skg_adamw_step. */
+int skg_adamw_step_guarded(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, void* param_f16, size_t n,
+                           float lr, float beta1, float beta2, float eps, float weight_decay, int step,
+                           float inv_grad_scale, const float* skip_flag, void* stream);
 
 /* ---- sampler elementwise -------------------------------------------------------------------------
  * CFG combine + DDIM step (eta = 0) on float NCHW latents:

@@ -27,7 +27,8 @@ LIB_PATH = os.environ.get("SKG_LIB") or os.path.join(_HERE, "libskg.so")
 # _strided / _from_partial2 / skg_ff_block_proj_f16 twins folded into the un-suffixed names, which take the superset argument
 # list with nullable pointers selecting the arm: INTEGRATION.md has the migration table), so that a stale build selected through
 # SKG_LIB fails at load instead of receiving shifted arguments.  Added since without a bump (a new symbol is compatible; a build
-# that lacks it fails the export check below): skg_cfg_ddim_eta_step, the DDIM step with the eta > 0 noise term
+# that lacks it fails the export check below): skg_cfg_ddim_eta_step, the DDIM step with the eta > 0 noise term;
+# skg_nonfinite_flag and skg_adamw_step_guarded, the dynamic loss scale's verdict and its guarded optimizer step
 ABI_VERSION = 6
 
 # spec letters: p = device/host pointer, i = int, f = float, u = unsigned, z = size_t (return only)
@@ -108,6 +109,9 @@ SIGNATURES = {
     "skg_layernorm_param_grads": ("i", "pipiiipfipppp"),
     # CLIP vision tower training (clip_vision.py forward_train / backward): additive entry point, same ABI version
     "skg_quick_gelu_bwd_f16": ("i", "pipipiiip"),
+    # dynamic loss scale (loss_scaler.py): additive entry points, same ABI version
+    "skg_nonfinite_flag": ("i", "pzpip"),
+    "skg_adamw_step_guarded": ("i", "pppppzfffffifpp"),
 }
 
 _CT = {"p": ctypes.c_void_p, "i": ctypes.c_int, "f": ctypes.c_float, "u": ctypes.c_uint,

@@ -99,11 +99,18 @@ class HipClipTowerTrainer(FlatAdamW):
         return (dstate * self.seam_scale).to(torch.float16)
 
     # ------------------------------------------------------------------------------------------ optimizer
-    def step(self, g: torch.Tensor, checked: bool = False) -> bool:
-        """FlatAdamW.step (g carries LOSS_SCALE * seam_scale, AdamW runs on [0, n_opt)); a step that ran leaves the tower's packs stale."""
+    def step(self, g: torch.Tensor, checked: bool = False, scaler=None, scale: Optional[float] = None):
+        """FlatAdamW.step (g carries LOSS_SCALE * seam_scale, AdamW runs on [0, n_opt)); a step that ran leaves the tower's packs stale.
+        scaler + scale (the scaler's scale at the seed x seam_scale): the guarded form, settled when the verdict resolves."""
+        if scaler is not None:
+            return super().step(g, checked, scaler=scaler, scale=scale)
         stepped = super().step(g, checked)
         self._packs_stale = self._packs_stale or stepped
         return stepped
+
+    def settle(self, stepped: bool) -> None:
+        super().settle(stepped)
+        self._packs_stale = self._packs_stale or stepped
 
     def state_dict(self) -> Dict[str, torch.Tensor]:
         """The reference's sketch_encoder_model.pt: fp32 masters under transformers' CLIPVisionModel keys, in its order."""

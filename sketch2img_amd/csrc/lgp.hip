@@ -600,11 +600,16 @@ __global__ __launch_bounds__(256) void mse_train_kernel(const half_t* __restrict
   if (threadIdx.x == 0) loss_part[s] = acc / n;       // the caller sums the S partials (fixed order)
 }
 
-// AdamW (decoupled weight decay), fp32 master weights + fp16 working copy; g is the loss-scaled gradient
+// AdamW (decoupled weight decay), fp32 master weights + fp16 working copy; g is the loss-scaled gradient.
+// GUARDED: *skip (the loss scaler's verdict, written earlier on the stream by nonfinite_flag_kernel) != 0 -> nothing is touched;
+// otherwise the same body, so the two instantiations contract alike and agree to the bit.
+template <bool GUARDED>
 __global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, const float* __restrict__ g,
                                                     float* __restrict__ m, float* __restrict__ v,
                                                     half_t* __restrict__ p16, size_t n, float lr, float b1, float b2,
-                                                    float eps, float wd, float bc1, float bc2, float inv_scale) {
+                                                    float eps, float wd, float bc1, float bc2, float inv_scale,
+                                                    const float* __restrict__ skip) {
+  if (GUARDED && *skip != 0.f) return;
   for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) {
     const float gi = g[i] * inv_scale;
     const float mi = b1 * m[i] + (1.f - b1) * gi;
@@ -616,6 +621,36 @@ __global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, const
     p[i] = w;
     if (p16) p16[i] = (half_t)w;
   }
+}
+
+// ±inf / NaN: exponent bits all ones
+__device__ __forceinline__ unsigned nonfinite_bits(unsigned u) { return (u & 0x7f800000u) == 0x7f800000u; }
+__device__ __forceinline__ unsigned nonfinite_bits(const uint4& u) {
+  return nonfinite_bits(u.x) | nonfinite_bits(u.y) | nonfinite_bits(u.z) | nonfinite_bits(u.w);
+}
+
+// *flag = 1.0f when any of x[0, n) is non-finite, untouched otherwise (several vectors OR into one flag).  x is 4-byte aligned:
+// `head` (0 ... 3) scalars up to the first 16-byte boundary, nvec 16-byte loads (grid-stride, four in flight per lane), then the
+// scalar tail; head and tail belong to block 0.  A wave with a hit stores 1.0f from its first lane: every writer stores the same
+// value, so the stores need no order among themselves.
+__global__ __launch_bounds__(256) void nonfinite_flag_kernel(const unsigned* __restrict__ x, size_t n, size_t head,
+                                                             size_t nvec, float* __restrict__ flag) {
+  const uint4* __restrict__ xv = reinterpret_cast<const uint4*>(x + head);
+  const size_t stride = (size_t)gridDim.x * 256;
+  size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+  unsigned bad = 0;
+  for (; i + 3 * stride < nvec; i += 4 * stride) {
+    const uint4 a = xv[i], b = xv[i + stride], c = xv[i + 2 * stride], d = xv[i + 3 * stride];
+    bad |= nonfinite_bits(a) | nonfinite_bits(b) | nonfinite_bits(c) | nonfinite_bits(d);
+  }
+  for (; i < nvec; i += stride) bad |= nonfinite_bits(xv[i]);
+  if (blockIdx.x == 0) {
+    const size_t body_end = head + 4 * nvec;
+    if (threadIdx.x < head) bad |= nonfinite_bits(x[threadIdx.x]);
+    if (threadIdx.x >= 64 && body_end + (threadIdx.x - 64) < n) bad |= nonfinite_bits(x[body_end + (threadIdx.x - 64)]);
+  }
+  const unsigned long long hits = __ballot(bad != 0);
+  if (hits != 0 && (threadIdx.x & 63) == 0) *flag = 1.0f;
 }
 
 inline int ew_grid(size_t total_items) {
@@ -803,8 +838,33 @@ extern "C" int skg_adamw_step(float* param, const float* grad, float* exp_avg, f
                               float inv_grad_scale, void* stream) {
   SKG_REQUIRE(param && grad && exp_avg && exp_avg_sq && n > 0 && step >= 1 && lr >= 0.f);
   const float bc1 = 1.f - powf(beta1, (float)step), bc2 = 1.f - powf(beta2, (float)step);
-  hipLaunchKernelGGL(adamw_kernel, dim3(ew_grid(n)), dim3(256), 0, (hipStream_t)stream, param, grad, exp_avg,
-                     exp_avg_sq, (half_t*)param_f16, n, lr, beta1, beta2, eps, weight_decay, bc1, bc2, inv_grad_scale);
+  hipLaunchKernelGGL(adamw_kernel<false>, dim3(ew_grid(n)), dim3(256), 0, (hipStream_t)stream, param, grad, exp_avg,
+                     exp_avg_sq, (half_t*)param_f16, n, lr, beta1, beta2, eps, weight_decay, bc1, bc2, inv_grad_scale,
+                     (const float*)nullptr);
   SKG_CHECK_LAUNCH("skg_adamw_step");
+  return SKG_OK;
+}
+
+extern "C" int skg_adamw_step_guarded(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, void* param_f16,
+                                      size_t n, float lr, float beta1, float beta2, float eps, float weight_decay,
+                                      int step, float inv_grad_scale, const float* skip_flag, void* stream) {
+  SKG_REQUIRE(param && grad && exp_avg && exp_avg_sq && skip_flag && n > 0 && step >= 1 && lr >= 0.f);
+  const float bc1 = 1.f - powf(beta1, (float)step), bc2 = 1.f - powf(beta2, (float)step);
+  hipLaunchKernelGGL(adamw_kernel<true>, dim3(ew_grid(n)), dim3(256), 0, (hipStream_t)stream, param, grad, exp_avg,
+                     exp_avg_sq, (half_t*)param_f16, n, lr, beta1, beta2, eps, weight_decay, bc1, bc2, inv_grad_scale,
+                     skip_flag);
+  SKG_CHECK_LAUNCH("skg_adamw_step_guarded");
+  return SKG_OK;
+}
+
+extern "C" int skg_nonfinite_flag(const float* x, size_t n, float* flag, int reset, void* stream) {
+  SKG_REQUIRE(x && flag && n > 0 && skg_aligned(x, 4) && skg_aligned(flag, 4));
+  if (reset && hipMemsetAsync(flag, 0, sizeof(float), (hipStream_t)stream) != hipSuccess) return SKG_E_LAUNCH;
+  size_t head = (4 - (((uintptr_t)x >> 2) & 3)) & 3;          // floats up to the first 16-byte boundary
+  if (head > n) head = n;
+  const size_t nvec = (n - head) / 4;
+  hipLaunchKernelGGL(nonfinite_flag_kernel, dim3(ew_grid(nvec)), dim3(256), 0, (hipStream_t)stream, (const unsigned*)x, n,
+                     head, nvec, flag);
+  SKG_CHECK_LAUNCH("skg_nonfinite_flag");
   return SKG_OK;
 }

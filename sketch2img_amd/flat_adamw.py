@@ -1,8 +1,10 @@
 """The optimizer state the three trainers (lgp_train, sat_train, clip_vision_train) share: one flat fp32 master vector, its fp16
 working copy, AdamW's m / v, views of all of them by state-dict key, and the LR schedules.
 
-What replaces the reference's accelerate fp16 autocast + GradScaler + bitsandbytes AdamW8bit: fp16 compute on the working copy with a
-STATIC power-of-two gradient scale, fp32 masters, plain fp32 AdamW (skg_adamw_step divides the scale out and refreshes the fp16 copy).
+What replaces the reference's accelerate fp16 autocast + GradScaler + bitsandbytes AdamW8bit: fp16 compute on the working copy, fp32
+masters, plain fp32 AdamW (skg_adamw_step divides the gradient scale out and refreshes the fp16 copy).  The gradient scale is a static
+power of two by default; the reference's GradScaler - scale halved and step skipped on overflow, doubled after growth_interval good
+steps - is step(scaler=) with a loss_scaler.DynamicLossScaler (verdict on the device, skg_adamw_step_guarded, no host wait).
 """
 from __future__ import annotations
 
@@ -91,11 +93,24 @@ class FlatAdamW:
         return self.lr * self.schedule(self.step_count)
 
     @torch.no_grad()
-    def step(self, g: torch.Tensor, checked: bool = False) -> bool:
+    def step(self, g: torch.Tensor, checked: bool = False, scaler=None, scale: Optional[float] = None):
         """AdamW on the masters (g carries grad_scale), fp16 copy refreshed.  A non-finite gradient skips the step: False, before
         any kernel runs, with p, m, v, p16 and the step count untouched (the static-scale form of GradScaler's skipped step).
         checked=True: the caller has already found g finite (sat_train.train_step with a tower decides for both optimizers at
-        once), or wants no test (it costs a device synchronisation)."""
+        once), or wants no test (it costs a device synchronisation).
+
+        scaler (a loss_scaler.DynamicLossScaler whose check() has been queued over g) + scale (what g carries: the scaler's scale
+        when the backward was seeded, times the trainer's own static factor where it has one): the step is queued behind the
+        scaler's device flag (skg_adamw_step_guarded) as step step_count + 1 at the LR of step_count, and nothing waits.  Returns
+        the scaler's pending verdict; step_count advances when it resolves clean (settle), so a skipped step leaves step count,
+        LR schedule position, p, m, v and p16 as they were."""
+        if scaler is not None:
+            assert scale is not None and scale > 0.0, "step(scaler=) needs scale=: what the gradient carries"
+            scaler.register(self)
+            n = self.n_opt
+            ops.adamw_step_guarded(self.p[:n], g[:n], self.m[:n], self.v[:n], self.p16[:n], self.current_lr(), self.betas[0],
+                                   self.betas[1], self.eps, self.wd, self.step_count + 1, 1.0 / float(scale), scaler.flag)
+            return scaler.verdict
         if not checked and not bool(torch.isfinite(g).all()):
             return False
         lr = self.current_lr()
@@ -104,6 +119,11 @@ class FlatAdamW:
         ops.adamw_step(self.p[:n], g[:n], self.m[:n], self.v[:n], self.p16[:n], lr, self.betas[0], self.betas[1], self.eps, self.wd,
                        self.step_count, 1.0 / self.grad_scale)
         return True
+
+    def settle(self, stepped: bool) -> None:
+        """The scaler's verdict on the guarded step queued by step(scaler=): only a step that ran counts."""
+        if stepped:
+            self.step_count += 1
 
     def state_dict(self, keys: Optional[Iterable[str]] = None) -> Dict[str, torch.Tensor]:
         """Clones of the fp32 masters under their keys, in the order of `keys` (default: the vector's)."""

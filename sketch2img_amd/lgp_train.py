@@ -4,9 +4,10 @@
     batch)  ->  mse_loss(result, sketch latents)  ->  gradients of every LGP parameter  ->  optimizer step,
     with the gradients all-reduced across ranks first (the reference wraps the model in DDP, bucket_cap_mb = 15).
 
-What differs from the reference, on purpose: accelerate's fp16 autocast + GradScaler becomes fp16 compute with a
-static power-of-two loss scale and fp32 master weights; bitsandbytes' AdamW8bit becomes plain fp32 AdamW (same
-hyper-parameters: train.yaml lr 2e-4, weight_decay 1e-2, eps 1e-8, "constant_with_warmup" over 150 steps).  The
+What differs from the reference, on purpose: accelerate's fp16 autocast becomes fp16 compute with fp32 master weights
+and, by default, a static power-of-two loss scale (LOSS_SCALE); the reference's GradScaler is train_step(scaler=) with a
+loss_scaler.DynamicLossScaler.  bitsandbytes' AdamW8bit becomes plain fp32 AdamW (same hyper-parameters: train.yaml
+lr 2e-4, weight_decay 1e-2, eps 1e-8, "constant_with_warmup" over 150 steps).  The
 reference's loop also contains a NameError (trainer.py:230 vs :236) and cannot run as published; the
 intended computation is restated in tests against PyTorch autograd of the oracle LGP.
 
@@ -51,10 +52,12 @@ class HipLGPTrainer(FlatAdamW):
     # ------------------------------------------------------------------------------------------ fwd + bwd
     @torch.no_grad()
     def loss_and_grads(self, taps: Sequence[Tuple[torch.Tensor, int]], noise_level: torch.Tensor,
-                       target: torch.Tensor):
+                       target: torch.Tensor, loss_scale: float = LOSS_SCALE):
         """taps: 9 x (fp16 [B*s*s, C_i], s) of the frozen UNet; noise_level fp32 [B,4,h,h] = sqrt(1-abar_t) * noise
         per sample (trainer.py:196-204); target fp32 [B,4,h,h] (the sketch latents).
-        Returns (loss scalar tensor, flat fp32 gradient vector multiplied by LOSS_SCALE)."""
+        loss_scale: a power of two (step() divides by LOSS_SCALE: leave the default unless the caller rescales itself,
+        as train_step(scaler=) does).
+        Returns (loss scalar tensor, flat fp32 gradient vector multiplied by loss_scale)."""
         B, _, h, _ = target.shape
         hw, M = h * h, B * h * h
         dev = self.dev
@@ -89,7 +92,7 @@ class HipLGPTrainer(FlatAdamW):
             Z = ops.gemm(A, w.contiguous(), bias=bias.contiguous(), relu=(l < 3))
         out = Z
         # ---- loss and seed
-        dOut, parts = ops.lgp_mse_train(out, target, B, h, SEED_LD, LOSS_SCALE)
+        dOut, parts = ops.lgp_mse_train(out, target, B, h, SEED_LD, loss_scale)
         loss = parts.sum()
         g = self.new_grad()
         gv = lambda k: self.grad_view(g, k)
@@ -130,9 +133,14 @@ class HipLGPTrainer(FlatAdamW):
         return loss, g
 
     # ------------------------------------------------------------------------------------------ optimizer
-    def step(self, g: torch.Tensor) -> None:
-        """AdamW, unconditionally: no finiteness test (it would add a device synchronisation and a skipped step)."""
-        super().step(g, checked=True)
+    def step(self, g: torch.Tensor, scaler=None, scale: Optional[float] = None):
+        """AdamW, unconditionally: no finiteness test (it would add a device synchronisation and a skipped step).
+        scaler + scale: FlatAdamW.step's guarded form (the step is skipped on the device when the scaler's check found
+        a non-finite gradient); returns the pending verdict."""
+        if scaler is None:
+            super().step(g, checked=True)
+            return None
+        return super().step(g, scaler=scaler, scale=scale)
 
     def state_dict(self) -> Dict[str, torch.Tensor]:
         """The reference's 30-key checkpoint (fp32 master weights + running statistics)."""
@@ -185,12 +193,26 @@ def unet_taps(net, noisy_latents: torch.Tensor, timesteps: Sequence[int], ehs: t
 
 @torch.no_grad()
 def train_step(trainer: HipLGPTrainer, net, latents: torch.Tensor, sketch_latents: torch.Tensor, ehs: torch.Tensor,
-               timesteps: Sequence[int], noise: torch.Tensor, alphas_cumprod: torch.Tensor, batched: bool = False):
+               timesteps: Sequence[int], noise: torch.Tensor, alphas_cumprod: torch.Tensor, batched: bool = False,
+               scaler=None):
     """trainer.py:208-246 for one batch: noise the latents, frozen UNet forward, LGP loss + gradients, gradient
-    all-reduce across ranks, AdamW.  Returns the loss (0-dim tensor).  batched: see unet_taps."""
+    all-reduce across ranks, AdamW.  Returns the loss (0-dim tensor).  batched: see unet_taps.
+
+    scaler (a loss_scaler.DynamicLossScaler): the reference's GradScaler in place of the static LOSS_SCALE - seed with
+    scaler.scale, backward, all-reduce, scaler.check(g), the guarded AdamW step; nothing waits for the verdict.  Returns
+    (loss, verdict): bool(verdict) tells whether the step ran (and resolves it).  The verdict is taken after the
+    all-reduce, where a non-finite value in any rank's addend has made the sum non-finite on every rank: the ranks
+    agree without a collective of their own."""
     noisy, noise_level = add_noise(latents.to(trainer.dev, torch.float32), noise.to(trainer.dev, torch.float32),
                                    timesteps, alphas_cumprod)
     taps = unet_taps(net, noisy, timesteps, ehs, batched=batched)
+    if scaler is not None:
+        s = scaler.scale                                   # (resolves the previous step's verdict)
+        loss, g = trainer.loss_and_grads(taps, noise_level, sketch_latents, loss_scale=s)
+        trainer.all_reduce(g)
+        verdict = scaler.check(g)
+        trainer.step(g, scaler=scaler, scale=s)
+        return loss, verdict
     loss, g = trainer.loss_and_grads(taps, noise_level, sketch_latents)
     trainer.all_reduce(g)
     trainer.step(g)

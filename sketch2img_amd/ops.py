@@ -906,6 +906,23 @@ def adamw_step(param, grad, exp_avg, exp_avg_sq, param_f16, lr, beta1, beta2, ep
                              eps, weight_decay, step, inv_grad_scale, _stream()), "skg_adamw_step")
 
 
+def adamw_step_guarded(param, grad, exp_avg, exp_avg_sq, param_f16, lr, beta1, beta2, eps, weight_decay, step: int,
+                       inv_grad_scale: float, skip_flag):
+    """adamw_step behind a one-float device flag (nonfinite_flag's): non-zero -> nothing is touched, zero -> adamw_step's bits."""
+    n = param.numel()
+    assert param.dtype == grad.dtype == exp_avg.dtype == exp_avg_sq.dtype == skip_flag.dtype == torch.float32
+    assert grad.numel() == n and skip_flag.numel() == 1
+    check(lib.skg_adamw_step_guarded(_p(param), _p(grad), _p(exp_avg), _p(exp_avg_sq), _p(param_f16), n, lr, beta1, beta2,
+                                     eps, weight_decay, step, inv_grad_scale, _p(skip_flag), _stream()), "skg_adamw_step_guarded")
+
+
+def nonfinite_flag(x, flag, reset: bool = False):
+    """flag (one fp32 element on x's device) = 1.0 if the dense fp32 tensor x holds an inf or a NaN, else untouched; reset zeroes
+    it first.  Queued on the current stream: nothing waits."""
+    assert x.dtype == flag.dtype == torch.float32 and x.is_contiguous() and flag.numel() == 1 and x.numel() > 0
+    check(lib.skg_nonfinite_flag(_p(x), x.numel(), _p(flag), int(bool(reset)), _stream()), "skg_nonfinite_flag")
+
+
 # ---- injected-attention training (sat_train.py) ---------------------------------------------------------
 def wgrad(dY, X, dW=None, db=None, alpha: float = 1.0, accumulate: bool = False, want_db: bool = False):
     """dW [N, K] fp32 = or += alpha * dY^T . X (dY [M, N], X [M, K]: fp16 row-major views, contraction over the rows) and,

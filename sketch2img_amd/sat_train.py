@@ -16,9 +16,10 @@ batched=True (opt-in, every entry point below): the reference's call form - ONE 
 (image rows and token rows as two tensors, K / V gathered per sample into one padded buffer, the attention trio at batch = B, every
 weight gradient contracted over all samples' rows) and one backward_eps over all rows.  Same values to rounding, not to the bit.
 
-What differs from the reference, on purpose (as in lgp_train.py): accelerate's fp16 autocast + GradScaler becomes fp16 compute
-with a STATIC power-of-two loss scale and fp32 master weights; bitsandbytes' AdamW8bit becomes plain fp32 AdamW with the same
-hyper-parameters.
+What differs from the reference, on purpose (as in lgp_train.py): accelerate's fp16 autocast becomes fp16 compute with fp32 master
+weights and, by default, a STATIC power-of-two loss scale; the reference's GradScaler is train_step(scaler=) with a
+loss_scaler.DynamicLossScaler (one scaler, one verdict for SatMixin and tower).  bitsandbytes' AdamW8bit becomes plain fp32 AdamW
+with the same hyper-parameters.
 
 The CLIP vision tower, which the reference trains in the same optimizer (clip_guided_trainer.py:116-119), attaches at the seam:
 loss_and_grads returns d loss / d sketch_state, and train_step(tower=, pixel_values=) takes the sketch tokens from
@@ -194,21 +195,29 @@ class HipSatTrainer(FlatAdamW):
         return fw["loss"], g, dstate
 
     # ------------------------------------------------------------------------------------------ optimizer
-    def step(self, g: torch.Tensor, checked: bool = False) -> bool:
-        """FlatAdamW.step (g carries LOSS_SCALE); a step that ran leaves the injector's packs stale."""
+    def step(self, g: torch.Tensor, checked: bool = False, scaler=None, scale: Optional[float] = None):
+        """FlatAdamW.step (g carries LOSS_SCALE, or `scale` under a scaler); a step that ran leaves the injector's packs stale."""
+        if scaler is not None:
+            return super().step(g, checked, scaler=scaler, scale=scale)        # (settle() marks the packs)
         stepped = super().step(g, checked)
         self._packs_stale = self._packs_stale or stepped
         return stepped
 
+    def settle(self, stepped: bool) -> None:
+        super().settle(stepped)
+        self._packs_stale = self._packs_stale or stepped
+
 
 @torch.no_grad()
 def loss_and_grads_through_tower(trainer: HipSatTrainer, tower, net, latents, noise, timesteps, ehs, pixel_values, alphas_cumprod,
-                                 batched: bool = False):
+                                 batched: bool = False, loss_scale: float = LOSS_SCALE):
     """HipSatTrainer.loss_and_grads fed by the tower's stashing forward, then the tower's backward from d sketch_state.
-    -> (loss, SatMixin flat gradient x LOSS_SCALE, tower flat gradient x LOSS_SCALE x tower.seam_scale, d sketch_state x LOSS_SCALE)."""
+    -> (loss, SatMixin flat gradient x LOSS_SCALE, tower flat gradient x LOSS_SCALE x tower.seam_scale, d sketch_state x LOSS_SCALE);
+    loss_scale (a power of two) takes LOSS_SCALE's place in all three."""
     assert pixel_values is not None, "training through the tower needs pixel_values"
     tokens, kept = tower.forward_train(pixel_values)
-    loss, g, dstate = trainer.loss_and_grads(net, latents, noise, timesteps, ehs, tokens, alphas_cumprod, batched=batched)
+    loss, g, dstate = trainer.loss_and_grads(net, latents, noise, timesteps, ehs, tokens, alphas_cumprod, loss_scale=loss_scale,
+                                             batched=batched)
     gt = tower.new_grad()
     tower.backward(kept, tower.seam(dstate), gt)
     return loss, g, gt, dstate
@@ -217,7 +226,7 @@ def loss_and_grads_through_tower(trainer: HipSatTrainer, tower, net, latents, no
 @torch.no_grad()
 def train_step(trainer: HipSatTrainer, net, latents: torch.Tensor, ehs: torch.Tensor, sketch_state: Optional[torch.Tensor],
                timesteps: Sequence[int], noise: torch.Tensor, alphas_cumprod: torch.Tensor, tower=None,
-               pixel_values: Optional[torch.Tensor] = None, batched: bool = False):
+               pixel_values: Optional[torch.Tensor] = None, batched: bool = False, scaler=None):
     """clip_guided_trainer.py:203-236 for one batch: noise the latents, UNet forward / backward per sample, gradient all-reduce
     across ranks, AdamW.  Returns (loss (0-dim tensor), whether the optimizer stepped, d loss / d sketch_state x LOSS_SCALE).
 
@@ -225,7 +234,32 @@ def train_step(trainer: HipSatTrainer, net, latents: torch.Tensor, ehs: torch.Te
     forward (sketch_state is ignored: pass None), d sketch_state goes into the tower's backward, and the two optimizers step
     together or not at all.
 
-    batched: the UNet evaluates the whole batch in one walk (HipSatTrainer.loss_and_grads); everything else is unchanged."""
+    batched: the UNet evaluates the whole batch in one walk (HipSatTrainer.loss_and_grads); everything else is unchanged.
+
+    scaler (a loss_scaler.DynamicLossScaler): the reference's GradScaler in place of the static LOSS_SCALE.  The backward is seeded
+    with scaler.scale (reading it resolves the previous step's verdict); after the all-reduce scaler.check(g[, gt]) queues the
+    finiteness test of both flat gradients into the scaler's one device flag, and the guarded AdamW steps of both optimizers read that
+    flag: both step or neither, and the host waits for nothing.  The second return value is then the verdict object in place of the
+    bool - bool(verdict) resolves it - and d sketch_state carries scaler.scale (the tower's gradient scaler.scale x its seam scale,
+    which stays a fixed ratio).  The ranks agree without a collective of their own: the verdict is taken after the all-reduce,
+    where a non-finite value in any rank's addend has made the sum non-finite on every rank."""
+    if scaler is not None:
+        s = scaler.scale
+        if tower is None:
+            loss, g, dstate = trainer.loss_and_grads(net, latents, noise, timesteps, ehs, sketch_state, alphas_cumprod, loss_scale=s,
+                                                     batched=batched)
+            trainer.all_reduce(g)
+            verdict = scaler.check(g)
+            trainer.step(g, scaler=scaler, scale=s)
+            return loss, verdict, dstate
+        loss, g, gt, dstate = loss_and_grads_through_tower(trainer, tower, net, latents, noise, timesteps, ehs, pixel_values,
+                                                           alphas_cumprod, batched=batched, loss_scale=s)
+        trainer.all_reduce(g)
+        tower.all_reduce(gt)
+        verdict = scaler.check(g, gt)
+        trainer.step(g, scaler=scaler, scale=s)
+        tower.step(gt, scaler=scaler, scale=s * tower.seam_scale)
+        return loss, verdict, dstate
     if tower is None:
         loss, g, dstate = trainer.loss_and_grads(net, latents, noise, timesteps, ehs, sketch_state, alphas_cumprod, batched=batched)
         trainer.all_reduce(g)
