@@ -70,7 +70,6 @@ class HipClipTowerTrainer(FlatAdamW):
             self.fused[p + ".qkv.weight"] = (self.layout[p + ".q_proj.weight"][0], torch.Size((3 * D, D)))
             self.fused[p + ".qkv.bias"] = (self.layout[p + ".q_proj.bias"][0], torch.Size((3 * D,)))
         self.vision: Optional[HipCLIPVision] = None        # built (packs and all) by the first forward_train
-        self._packs_stale = False
 
     def _at(self, key: str) -> Tuple[int, torch.Size]:
         return self.layout[key] if key in self.layout else self.fused[key]
@@ -83,12 +82,13 @@ class HipClipTowerTrainer(FlatAdamW):
 
     def refresh(self) -> None:
         """Bring what the tower derives from the working copy up to date (its padded and transposed packs): a no-op unless an
-        optimizer step has run since the last call.  forward_train calls it; a caller may do so earlier, after step()."""
+        optimizer step has run since the last call (FlatAdamW.stale).  forward_train calls it; a caller may do so earlier, after
+        step()."""
         if self.vision is None:
             self.vision = HipCLIPVision(self.cfg, None, self.dev, views=(self.w16, self.w32, self.grad_view))
-        elif self._packs_stale:
+        elif self.stale:
             self.vision.refresh()
-        self._packs_stale = False
+        self.stale = False
 
     def backward(self, kept: dict, d_tokens: torch.Tensor, g: torch.Tensor) -> None:
         """d_tokens fp16 [B, N, D], scaled by LOSS_SCALE * seam_scale -> += into the flat fp32 gradient g (same scale)."""
@@ -99,19 +99,8 @@ class HipClipTowerTrainer(FlatAdamW):
         return (dstate * self.seam_scale).to(torch.float16)
 
     # ------------------------------------------------------------------------------------------ optimizer
-    def step(self, g: torch.Tensor, checked: bool = False, scaler=None, scale: Optional[float] = None):
-        """FlatAdamW.step (g carries LOSS_SCALE * seam_scale, AdamW runs on [0, n_opt)); a step that ran leaves the tower's packs stale.
-        scaler + scale (the scaler's scale at the seed x seam_scale): the guarded form, settled when the verdict resolves."""
-        if scaler is not None:
-            return super().step(g, checked, scaler=scaler, scale=scale)
-        stepped = super().step(g, checked)
-        self._packs_stale = self._packs_stale or stepped
-        return stepped
-
-    def settle(self, stepped: bool) -> None:
-        super().settle(stepped)
-        self._packs_stale = self._packs_stale or stepped
-
+    # FlatAdamW.step as it is: g carries LOSS_SCALE * seam_scale (under a scaler: the scaler's scale at the seed x seam_scale), AdamW
+    # runs on [0, n_opt), and a step that ran leaves the tower's packs stale
     def state_dict(self) -> Dict[str, torch.Tensor]:
         """The reference's sketch_encoder_model.pt: fp32 masters under transformers' CLIPVisionModel keys, in its order."""
         return super().state_dict(clip_vision_param_shapes(self.cfg))

@@ -42,6 +42,9 @@ class FlatAdamW:
         self.lr, self.betas, self.eps, self.wd = lr, betas, eps, weight_decay
         self.schedule, self.grad_scale = schedule, float(grad_scale)
         self.step_count = 0
+        # a step ran since what a trainer derives from the fp16 copy (the injector's / the tower's packs) was built: set by a static
+        # step that ran and by settle(True); the trainer reads and clears it before it refreshes its packs
+        self.stale = False
         frozen = set(frozen)
         self.layout: Dict[str, Tuple[int, torch.Size]] = {}
         off = 0
@@ -118,12 +121,14 @@ class FlatAdamW:
         n = self.n_opt
         ops.adamw_step(self.p[:n], g[:n], self.m[:n], self.v[:n], self.p16[:n], lr, self.betas[0], self.betas[1], self.eps, self.wd,
                        self.step_count, 1.0 / self.grad_scale)
+        self.stale = True
         return True
 
     def settle(self, stepped: bool) -> None:
-        """The scaler's verdict on the guarded step queued by step(scaler=): only a step that ran counts."""
+        """The scaler's verdict on the guarded step queued by step(scaler=): only a step that ran counts (and leaves packs stale)."""
         if stepped:
             self.step_count += 1
+            self.stale = True
 
     def state_dict(self, keys: Optional[Iterable[str]] = None) -> Dict[str, torch.Tensor]:
         """Clones of the fp32 masters under their keys, in the order of `keys` (default: the vector's)."""

@@ -165,6 +165,11 @@ def add_noise(latents: torch.Tensor, noise: torch.Tensor, timesteps: Sequence[in
     return a * latents + s * noise, s * noise
 
 
+def row_groups(B: int, batched: bool) -> List[Tuple[int, int]]:
+    """The [b0, b1) sample ranges a trainer walks the UNet on: the samples one by one, or (batched) the whole batch at once."""
+    return [(0, B)] if batched else [(b, b + 1) for b in range(B)]
+
+
 @torch.no_grad()
 def unet_taps(net, noisy_latents: torch.Tensor, timesteps: Sequence[int], ehs: torch.Tensor, batched: bool = False):
     """The nine hooked feature maps (modules/latent_predictor.py:47-81) of a frozen UNet forward, one sample at a
@@ -174,21 +179,14 @@ def unet_taps(net, noisy_latents: torch.Tensor, timesteps: Sequence[int], ehs: t
     ResnetBlock reads a bias row per sample) - the reference's own unet(noisy_latents, timesteps, ehs)."""
     from .unet import CIN_PAD
     B, _, h, _ = noisy_latents.shape
-    if batched:
-        net.prepare_context(ehs)
-        x32 = ops.nchw_to_nhwc(noisy_latents.to(net.dev, torch.float32).contiguous(), CIN_PAD)
-        _, taps = net.forward(x32, [int(t) for t in timesteps], B, h, None, want_taps=True, want_eps=False)
-        return [(t.contiguous(), s) for t, s in taps]
-    per_tap: List[List[torch.Tensor]] = [[] for _ in range(9)]
-    sizes: List[int] = []
-    for b in range(B):
-        net.prepare_context(ehs[b:b + 1])
-        x32 = ops.nchw_to_nhwc(noisy_latents[b:b + 1].to(net.dev, torch.float32).contiguous(), CIN_PAD)
-        _, taps = net.forward(x32, int(timesteps[b]), 1, h, None, want_taps=True, want_eps=False)
-        sizes = [s for _, s in taps]
-        for i, (t, _) in enumerate(taps):
-            per_tap[i].append(t)
-    return [(torch.cat(ts).contiguous(), s) for ts, s in zip(per_tap, sizes)]
+    walks = []
+    for b0, b1 in row_groups(B, batched):
+        net.prepare_context(ehs[b0:b1])
+        x32 = ops.nchw_to_nhwc(noisy_latents[b0:b1].to(net.dev, torch.float32).contiguous(), CIN_PAD)
+        t = [int(v) for v in timesteps] if batched else int(timesteps[b0])
+        walks.append(net.forward(x32, t, b1 - b0, h, None, want_taps=True, want_eps=False)[1])
+    # tap by tap, the groups' rows one after the other (one group: its taps as they are)
+    return [((per[0][0] if batched else torch.cat([t for t, _ in per])).contiguous(), per[0][1]) for per in zip(*walks)]
 
 
 @torch.no_grad()
@@ -206,14 +204,12 @@ def train_step(trainer: HipLGPTrainer, net, latents: torch.Tensor, sketch_latent
     noisy, noise_level = add_noise(latents.to(trainer.dev, torch.float32), noise.to(trainer.dev, torch.float32),
                                    timesteps, alphas_cumprod)
     taps = unet_taps(net, noisy, timesteps, ehs, batched=batched)
-    if scaler is not None:
-        s = scaler.scale                                   # (resolves the previous step's verdict)
-        loss, g = trainer.loss_and_grads(taps, noise_level, sketch_latents, loss_scale=s)
-        trainer.all_reduce(g)
-        verdict = scaler.check(g)
-        trainer.step(g, scaler=scaler, scale=s)
-        return loss, verdict
-    loss, g = trainer.loss_and_grads(taps, noise_level, sketch_latents)
+    s = LOSS_SCALE if scaler is None else scaler.scale     # (reading it resolves the previous step's verdict)
+    loss, g = trainer.loss_and_grads(taps, noise_level, sketch_latents, loss_scale=s)
     trainer.all_reduce(g)
-    trainer.step(g)
-    return loss
+    if scaler is None:
+        trainer.step(g)                                    # (unconditionally: HipLGPTrainer.step)
+        return loss
+    verdict = scaler.check(g)
+    trainer.step(g, scaler=scaler, scale=s)
+    return loss, verdict

@@ -47,6 +47,7 @@ from .clip_text import encode_tokens  # noqa: F401 (re-exported: the trainer's l
 from .config import UNetConfig
 from .flat_adamw import FlatAdamW, cosine_with_restarts  # noqa: F401 (cosine_with_restarts is re-exported)
 from .inject import CLIP_DIM, HipClipInjectorTrain, block_dims, module_name
+from .lgp_train import row_groups
 
 LOSS_SCALE = 8192.0        # 2^13, see the module docstring
 _LEAVES = ("sketch_proj.weight", "sketch_proj.bias", "sketch_norm.weight", "sketch_norm.bias", "sketch_attn.to_q.weight",
@@ -98,7 +99,7 @@ class HipSatTrainer(FlatAdamW):
         self.cfg = cfg
         self.injector = HipClipInjectorTrain(cfg, self.w16, self.grad_view, self.dev)
         self.injector.set_scale(scale)
-        self._packs_stale = True
+        self.stale = True          # (FlatAdamW's flag: the injector's packs are built by the first forward_batch)
 
     # ------------------------------------------------------------------------------------------ fwd + bwd
     @torch.no_grad()
@@ -116,10 +117,10 @@ class HipSatTrainer(FlatAdamW):
     @torch.no_grad()
     def forward_batch(self, net, latents, noise, timesteps, ehs, sketch_state, alphas_cumprod, loss_scale: float = LOSS_SCALE,
                       batched: bool = False):
-        """The stashing forward of every sample, the loss and its seed (the loss is a mean over the whole batch, so all
-        forwards come first).  Returns what backward_batch consumes (with the same `batched`).
-        batched: one prepare_context, one stashing forward at rows = B with a timestep per row and diff_from = 0 (every row is
-        differentiated), the injector holding all B token sets."""
+        """The stashing forward of every row group - the samples one by one - the loss and its seed (the loss is a mean over the
+        whole batch, so all forwards come first).  Returns what backward_batch consumes (with the same `batched`).
+        batched: one group, the batch - one prepare_context, one stashing forward at rows = B with a timestep per row and
+        diff_from = 0 (every row is differentiated), the injector holding all B token sets."""
         from .unet import CIN_PAD, Stash
         if net.residual_fp32:
             raise NotImplementedError("HipSatTrainer: the accuracy mode (residual_fp32) is not supported - build the HipUNet "
@@ -127,9 +128,11 @@ class HipSatTrainer(FlatAdamW):
         B, _, h, w = latents.shape
         assert h == w, "square maps only"
         dev = self.dev
-        if self._packs_stale:
+        if self.stale:             # an optimizer step ran since the injector's packs were built (FlatAdamW.step / settle)
+            self.stale = False
             self.injector.refresh()
-            self._packs_stale = False
+        if batched and len(timesteps) != B:
+            raise ValueError(f"timesteps: {len(timesteps)} entries for {B} samples")
         noise = noise.to(dev, torch.float32).contiguous()
         noisy = add_noise(latents.to(dev, torch.float32), noise, timesteps, alphas_cumprod)
         state16 = sketch_state.to(dev, torch.float16)
@@ -137,29 +140,22 @@ class HipSatTrainer(FlatAdamW):
         hw = h * h
         g = self.new_grad()
         dstate = torch.zeros(B, T, CLIP_DIM, device=dev, dtype=torch.float32)
+        eps_all = None if batched else torch.empty(B * hw, 8, device=dev, dtype=torch.float16)
+        kept = []
         prev = net.inject
         net.inject = self.injector
         try:
-            if batched:
-                if len(timesteps) != B:
-                    raise ValueError(f"timesteps: {len(timesteps)} entries for {B} samples")
-                net.prepare_context(ehs)
-                x32 = ops.nchw_to_nhwc(noisy.contiguous(), CIN_PAD)
+            for b0, b1 in row_groups(B, batched):
+                net.prepare_context(ehs[b0:b1])
+                x32 = ops.nchw_to_nhwc(noisy[b0:b1].contiguous(), CIN_PAD)
                 stash = Stash()
-                self.injector.begin(state16, g, dstate)
-                eps, _ = net.forward(x32, [int(t) for t in timesteps], B, h, stash, want_taps=False, want_eps=True, diff_from=0)
-                loss, seed = mse_seed(eps, noise, B, h, loss_scale)
-                return dict(loss=loss, seed=seed, kept=[(stash, self.injector.stash, net.ctx)], g=g, dstate=dstate, state16=state16,
-                            hw=hw)
-            eps_all = torch.empty(B * hw, 8, device=dev, dtype=torch.float16)
-            kept = []
-            for b in range(B):
-                net.prepare_context(ehs[b:b + 1])
-                x32 = ops.nchw_to_nhwc(noisy[b:b + 1].contiguous(), CIN_PAD)
-                stash = Stash()
-                self.injector.begin(state16[b], g, dstate[b])
-                eps, _ = net.forward(x32, int(timesteps[b]), 1, h, stash, want_taps=False, want_eps=True)
-                ops.batch_copy(eps, hw, eps_all[b * hw:], hw, 1, hw)
+                if batched:        # the group is the batch: a timestep per row, 3-D state, every row differentiated
+                    self.injector.begin(state16, g, dstate)
+                    eps_all, _ = net.forward(x32, [int(t) for t in timesteps], B, h, stash, want_taps=False, want_eps=True, diff_from=0)
+                else:              # one sample: its timestep, its 2-D state, its eps rows into the batch buffer
+                    self.injector.begin(state16[b0], g, dstate[b0])
+                    eps, _ = net.forward(x32, int(timesteps[b0]), 1, h, stash, want_taps=False, want_eps=True)
+                    ops.batch_copy(eps, hw, eps_all[b0 * hw:], hw, 1, hw)
                 kept.append((stash, self.injector.stash, net.ctx))
             loss, seed = mse_seed(eps_all, noise, B, h, loss_scale)
         finally:
@@ -169,43 +165,27 @@ class HipSatTrainer(FlatAdamW):
 
     @torch.no_grad()
     def backward_batch(self, net, fw: dict, batched: bool = False):
-        """HipUNet.backward_eps of every sample into the flat gradient vector.  -> (loss, g, d sketch_state).
-        batched (fw from forward_batch(batched=True)): one backward_eps over all rows."""
+        """HipUNet.backward_eps of every row group of forward_batch (same `batched`: the samples one by one, or all rows at once) into
+        the flat gradient vector.  -> (loss, g, d sketch_state)."""
         g, dstate, kept, hw = fw["g"], fw["dstate"], fw["kept"], fw["hw"]
+        groups = row_groups(len(fw["dstate"]), batched)
+        assert len(groups) == len(kept), "backward_batch: the `batched` of the forward_batch that made fw"
         prev, prev_ctx = net.inject, net.ctx
         net.inject = self.injector
         try:
-            if batched:
-                (stash, istash, ctx), kept[0] = kept[0], None
-                net.ctx = ctx
-                self.injector.begin(fw["state16"], g, dstate)
+            for i, (b0, b1) in enumerate(groups):
+                (stash, istash, ctx), kept[i] = kept[i], None
+                net.ctx = ctx                                      # (the cross-attention K / V of this group's prompts)
+                if batched:
+                    self.injector.begin(fw["state16"], g, dstate)
+                else:
+                    self.injector.begin(fw["state16"][b0], g, dstate[b0])
                 self.injector.stash = istash
-                net.backward_eps(stash, fw["seed"], inject_bwd=self.injector.backward)
-                return fw["loss"], g, dstate
-            for b in range(len(kept)):
-                stash, istash, ctx = kept[b]
-                net.ctx = ctx                                      # (the cross-attention K / V of this sample's prompt)
-                self.injector.begin(fw["state16"][b], g, dstate[b])
-                self.injector.stash = istash
-                net.backward_eps(stash, fw["seed"][b * hw:(b + 1) * hw], inject_bwd=self.injector.backward)
-                kept[b] = None
+                net.backward_eps(stash, fw["seed"][b0 * hw:b1 * hw], inject_bwd=self.injector.backward)
         finally:
             self.injector.end()
             net.inject, net.ctx = prev, prev_ctx
         return fw["loss"], g, dstate
-
-    # ------------------------------------------------------------------------------------------ optimizer
-    def step(self, g: torch.Tensor, checked: bool = False, scaler=None, scale: Optional[float] = None):
-        """FlatAdamW.step (g carries LOSS_SCALE, or `scale` under a scaler); a step that ran leaves the injector's packs stale."""
-        if scaler is not None:
-            return super().step(g, checked, scaler=scaler, scale=scale)        # (settle() marks the packs)
-        stepped = super().step(g, checked)
-        self._packs_stale = self._packs_stale or stepped
-        return stepped
-
-    def settle(self, stepped: bool) -> None:
-        super().settle(stepped)
-        self._packs_stale = self._packs_stale or stepped
 
 
 @torch.no_grad()
@@ -243,35 +223,26 @@ def train_step(trainer: HipSatTrainer, net, latents: torch.Tensor, ehs: torch.Te
     bool - bool(verdict) resolves it - and d sketch_state carries scaler.scale (the tower's gradient scaler.scale x its seam scale,
     which stays a fixed ratio).  The ranks agree without a collective of their own: the verdict is taken after the all-reduce,
     where a non-finite value in any rank's addend has made the sum non-finite on every rank."""
-    if scaler is not None:
-        s = scaler.scale
-        if tower is None:
-            loss, g, dstate = trainer.loss_and_grads(net, latents, noise, timesteps, ehs, sketch_state, alphas_cumprod, loss_scale=s,
-                                                     batched=batched)
-            trainer.all_reduce(g)
-            verdict = scaler.check(g)
-            trainer.step(g, scaler=scaler, scale=s)
-            return loss, verdict, dstate
+    s = LOSS_SCALE if scaler is None else scaler.scale         # (reading it resolves the previous step's verdict)
+    if tower is None:
+        loss, g, dstate = trainer.loss_and_grads(net, latents, noise, timesteps, ehs, sketch_state, alphas_cumprod, loss_scale=s,
+                                                 batched=batched)
+        steps = [(trainer, g, s)]                              # (optimizer, its flat gradient, the scale that gradient carries)
+    else:
         loss, g, gt, dstate = loss_and_grads_through_tower(trainer, tower, net, latents, noise, timesteps, ehs, pixel_values,
                                                            alphas_cumprod, batched=batched, loss_scale=s)
-        trainer.all_reduce(g)
-        tower.all_reduce(gt)
-        verdict = scaler.check(g, gt)
-        trainer.step(g, scaler=scaler, scale=s)
-        tower.step(gt, scaler=scaler, scale=s * tower.seam_scale)
+        steps = [(trainer, g, s), (tower, gt, s * tower.seam_scale)]
+    for opt, grad, _ in steps:
+        opt.all_reduce(grad)
+    if scaler is not None:
+        verdict = scaler.check(*(grad for _, grad, _ in steps))
+        for opt, grad, scale in steps:
+            opt.step(grad, scaler=scaler, scale=scale)
         return loss, verdict, dstate
-    if tower is None:
-        loss, g, dstate = trainer.loss_and_grads(net, latents, noise, timesteps, ehs, sketch_state, alphas_cumprod, batched=batched)
-        trainer.all_reduce(g)
-        return loss, trainer.step(g), dstate
-    loss, g, gt, dstate = loss_and_grads_through_tower(trainer, tower, net, latents, noise, timesteps, ehs, pixel_values, alphas_cumprod,
-                                                       batched=batched)
-    trainer.all_reduce(g)
-    tower.all_reduce(gt)
-    # one GradScaler in the reference: a non-finite gradient in either set skips both.  The verdict is taken here, once per
-    # vector (the tower's is ~3e8 floats), and handed down.
-    if not (bool(torch.isfinite(g).all()) and bool(torch.isfinite(gt).all())):
-        return loss, False, dstate
-    trainer.step(g, checked=True)
-    tower.step(gt, checked=True)
-    return loss, True, dstate
+    # one GradScaler in the reference: a non-finite gradient in either set skips both.  The verdict is taken here, once per vector
+    # (the tower's is ~3e8 floats; the second is not read when the first has failed), and handed down
+    stepped = all(bool(torch.isfinite(grad).all()) for _, grad, _ in steps)
+    if stepped:
+        for opt, grad, _ in steps:
+            opt.step(grad, checked=True)
+    return loss, stepped, dstate

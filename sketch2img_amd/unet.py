@@ -8,8 +8,8 @@ modules/pipeline.py:159.  Weights use the diffusers state_dict key names.
 
 Data layout in HBM: every activation is fp16, token-major [rows*H*W, C]; rows are
 ordered [uncond rows of all samples ; cond rows of all samples] so the backward pass (cond rows
-only - the uncond gradient is discarded at modules/pipeline.py:159) works on the contiguous second
-half of every stashed buffer.  Weight-pack layouts: packs.py (which packs a net has: HipUNet._pack / _pack_hp here).
+only - the uncond gradient is discarded at modules/pipeline.py:159) works on a contiguous suffix
+of every buffer, which is all a Stash keeps of it (a free view).  Weight-pack layouts: packs.py (which packs a net has: HipUNet._pack / _pack_hp here).
 
 Work hoisted out of the per-step loop because it does not depend on the latent:
   * the time-embedding MLP and every ResnetBlock2D.time_emb_proj(silu(temb)) -> one fused bias
@@ -110,10 +110,25 @@ UP2_DGRAD = os.environ.get("SKG_UP2_DGRAD", "1") != "0"         # A/B: the upsam
 
 @dataclass
 class Stash:
-    """Activations kept by a grad-enabled forward for the backward pass."""
+    """Activations kept by a grad-enabled forward for the backward pass: of every tensor exactly the rows the backward
+    differentiates, the last rows - first of the evaluation's batch rows (forward sets both before its first launch)."""
     res: Dict[str, dict] = field(default_factory=dict)
     tr: Dict[str, dict] = field(default_factory=dict)
     misc: dict = field(default_factory=dict)
+    rows: int = 0          # batch rows of the evaluation
+    first: int = 0         # the first differentiated row (forward's diff_from; rows // 2 without one)
+
+    def suffix(self, key: str, v: Optional[torch.Tensor], unit: int) -> Optional[torch.Tensor]:
+        """The view of v's last rows - first batch rows.  unit: tensor rows per batch row (HW for activations and per-token
+        statistics, 1 for per-image tensors).  Every tensor a forward produces holds a suffix of the batch rows - all of them, the
+        cond half of a shared CFG front, the rows a stashing launch kept - and how many is read off the tensor itself, so a wrong
+        belief about a launch fails here, under the name `key`, not as a mis-slice in the backward.  None passes through."""
+        if v is None:
+            return None
+        S, (n, rem) = self.rows - self.first, divmod(v.shape[0], unit)
+        if rem or not S <= n <= self.rows:
+            raise ValueError(f"stash {key}: {v.shape[0]} rows at {unit} per batch row - a suffix of {S} ... {self.rows} batch rows expected")
+        return v if n == S else v[(n - S) * unit:]
 
 
 class _Packs(dict):
@@ -620,11 +635,11 @@ class HipUNet:
         return _produce("gemm", *self._operand(x, p + ".conv_shortcut.weight", ":2"), out=_fresh(x, M, Cout),
                         bias=self.W[p + ".conv_shortcut.bias"])[0]
 
-    def _res_fwd(self, p, x, rows, sz, tb, stash: Optional[Stash], out=None, xpart=None, want_part=False, half=False):
+    def _res_fwd(self, p, x, rows, sz, tb, stash: Optional[Stash], out=None, xpart=None, want_part=False):
         """x: fp16, or a Pair in the accuracy mode's pair zone - the output (and conv1's, which feeds norm2) has its representation.
         xpart: GroupNorm partial sums of x from its producer (or None).  Returns (out, partial sums of out or None):
         they are produced when want_part is set and the level takes its statistics from the producers.
-        half: `rows` are the COND rows only (the shared CFG prefix, see forward): the stash says so."""
+        `rows` may be the COND rows only (the shared CFG prefix, see forward): the stash keeps the differentiated rows either way."""
         W, pair = self.W, isinstance(x, ops.Pair)
         G, HW, M = self.cfg.norm_groups, sz[0] * sz[1], rows * sz[0] * sz[1]
         k1, k2 = p + ".conv1.weight", p + ".conv2.weight"
@@ -680,7 +695,8 @@ class HipUNet:
             w2 = W[k2 + ":n2"][:, : 9 * a2.shape[1]].contiguous() if n2_pair else W[k2]
             out, opart = _produce("conv3x3", a2, w2, rows, *sz, out=out, bias=W[p + ".conv2.bias"], residual=sc, gn=ogn)
         if stash is not None:      # (the backward differentiates the fp16 - hi - values in either mode)
-            stash.res[p] = dict(x=_hi(x), st1=st1, h1=_hi(h1), st2=st2, sz=sz, half=half)
+            k = lambda name, v, unit=HW: stash.suffix(f"{p}.{name}", v, unit)
+            stash.res[p] = dict(x=k("x", _hi(x)), st1=k("st1", st1, 1), h1=k("h1", _hi(h1)), st2=k("st2", st2, 1), sz=sz)
         return out, opart
 
     def _tr_fwd(self, p, x, rows, sz, heads, stash: Optional[Stash], out=None, xpart=None, want_part=False, shared=False,
@@ -690,7 +706,7 @@ class HipUNet:
         to here (see forward): everything in front of the first text-dependent operation - GroupNorm, proj_in, the whole
         self-attention, LayerNorm 2, to_q - runs once; p1 and q2 are written into the cond half of full-size buffers and
         copied to the uncond half (x_full: the same for x, filled by the caller).
-        diff_from: the first row a stash keeps for the backward (forward's diff_from; None: rows // 2)."""
+        diff_from (forward's; None: rows // 2): selects the split / fused stashing launches and the first row they keep."""
         cfg, W, pair = self.cfg, self.W, isinstance(x, ops.Pair)
         HW, M = sz[0] * sz[1], rows * sz[0] * sz[1]
         C = _hi(x).shape[1]
@@ -728,7 +744,6 @@ class HipUNet:
         cb = self.ctx["blocks"][t + ".attn2"]
         xab = (_XATTN_BLOCK and (not keep or ((_XATTN_KEEP_HP if pair else _XATTN_KEEP) and split)) and "kvpack" in cb
                and heads in _XATTN_HEADS and HW % 128 == 0)
-        xk_half = ()
         if xab:
             # norm2 -> to_q -> attention over the text keys -> to_out + residual in ONE row-local launch (skg_xattn_block_f16[_hilo]);
             # the text-dependent part needs both halves, so a shared front ends here
@@ -741,7 +756,6 @@ class HipUNet:
                 # guided step: the same launch also stores what the backward of the cond rows (second half) reads - norm2's
                 # statistics, q, the attention output and its lse (skg_xattn_block_f16[_hilo]_keep), for those rows only
                 p2, st2, q2_c, o2, lse2 = ops.xattn_block(p1, *xargs, keep_from=M0)
-                xk_half = ("st2", "q2", "o2", "lse2")
             else:
                 p2 = ops.xattn_block(p1, *xargs)
                 st2 = q2_c = o2 = lse2 = None                 # (only a stash would read them, and there is none)
@@ -793,29 +807,19 @@ class HipUNet:
             else:
                 f = ops.gemm(a3, w1, bias=b1)
                 gg = ops.geglu(f, interleaved=True)
-                f = f[M0:]
             p3, _ = _produce("gemm", gg, W[t + ".ff.net.2.weight"], out=_fresh(x, M, C), bias=W[t + ".ff.net.2.bias"], residual=p2)
         if not ffp:
             out, opart = _produce("gemm", *self._operand(p3, p + ".proj_out.weight", ":2"), out=out, bias=W[p + ".proj_out.bias"],
                                   residual=x, gn=gn)
         if keep:
-            # the fp16 (hi) tensors the backward of the cond rows reads.  x / p1 / q2: what the text-independent part produced (after
-            # the injector, for p1) - the cond rows only under a shared front.  half: the keys whose tensors hold the cond rows only,
-            # derived from what each tensor actually holds - r1 rows or all of them - whatever the injector did, so that a backward
-            # through an injected block could never slice an M1-row tensor a second time
-            ent = dict(x=_hi(x_c), gst=gst, pin=_hi(pin), st1=st1, qkv=qkv, o1=o1, lse1=lse1, p1=_hi(p1_c), st2=st2, q2=q2_c)
-            half = tuple(k for k in self._stash_half(ent, r1, rows, HW) if k not in xk_half) + xk_half      # (the stashing cross-attention launch: cond rows only)
-            stash.tr[p] = dict(ent, o2=o2, lse2=lse2, p2=_hi(p2), st3=st3, f=f, sz=sz, heads=heads, half=half)
+            # the fp16 (hi) tensors the backward reads, each narrowed to the differentiated rows by what it actually holds - all rows,
+            # the cond rows of a shared front (x / p1 / q2: what the text-independent part produced, after the injector for p1) or the
+            # rows a stashing launch kept - whatever the injector did
+            per_row = dict(x=_hi(x_c), pin=_hi(pin), st1=st1, qkv=qkv, o1=o1, p1=_hi(p1_c), st2=st2, q2=q2_c, o2=o2, p2=_hi(p2), st3=st3, f=f)
+            per_image = dict(gst=gst, lse1=lse1, lse2=lse2)
+            stash.tr[p] = dict({k: stash.suffix(f"{p}.{k}", v, HW) for k, v in per_row.items()},
+                               **{k: stash.suffix(f"{p}.{k}", v, 1) for k, v in per_image.items()}, sz=sz, heads=heads)
         return out, opart
-
-    @staticmethod
-    def _stash_half(ent: dict, r1: int, rows: int, HW: int) -> tuple:
-        """Keys of a transformer stash entry whose tensors hold the cond rows only (r1 = rows // 2 of them), derived from what each
-        tensor actually holds - never from how the forward believes it got there - so that the backward can not slice a cond-only
-        tensor a second time.  Per-row tensors have r1 * HW rows; gst / lse1 are per image."""
-        if r1 == rows:
-            return ()
-        return tuple(k for k, v in ent.items() if v is not None and v.shape[0] == (r1 if k in ("gst", "lse1") else r1 * HW))
 
     @staticmethod
     def _dup_partial(part):
@@ -926,7 +930,8 @@ class HipUNet:
         self.prepare_timesteps(sorted(set(t)) if isinstance(t, list) else [t])
         assert not (down_only and self.residual_fp32), "accuracy mode: the whole UNet (with or without a stash, with or without an injector)"
         if stash is not None:
-            stash.misc.update(rows=rows, H=H, W=sz[1], diff_from=rows // 2 if diff_from is None else diff_from)
+            stash.rows, stash.first = rows, rows // 2 if diff_from is None else diff_from
+            stash.misc.update(H=H, W=sz[1])
         if isinstance(t, list):      # a timestep per sample: every resnet's bias rows in row order, one gather per resnet
             idx = torch.tensor([self.tbias_row[v] for v in t], device=self.dev)
             tb = {p: tab.index_select(0, idx) for p, tab in self.tbias_tab.items()}
@@ -951,7 +956,7 @@ class HipUNet:
             x_full = _fresh(slot, 2 * M1, boc[0])
             p0 = "down_blocks.0.resnets.0"      # (a timestep per sample: the halves' timesteps are equal row for row - the cond rows' stack)
             h1, hp1 = res(p0, hc, S1, cur, {p0: tb[p0][S1:]} if isinstance(t, list) else tb, stash, out=_rows_of(x_full, M1, 2 * M1), xpart=hp1,
-                          want_part=True, half=True)
+                          want_part=True)
             _copy_up(h1, x_full, M1)
             h, hp = tr("down_blocks.0.attentions.0", h1, rows, cur, cfg.num_heads[0], stash, out=cats.skip_slot(boc[0], cur),
                        xpart=hp1, want_part=0 < lpb - 1, shared=True, x_full=x_full)
@@ -1041,7 +1046,7 @@ class HipUNet:
             eps, _ = _produce("conv3x3", *self._operand(n, "conv_out.weight", ":2"), rows, *cur, out=_fresh(h, rows * HW, COUT_PAD),
                               bias=W["conv_out.bias"])
             if stash is not None and not isinstance(h, ops.Pair):      # what backward_eps reads (references only: no extra launch)
-                stash.misc.update(out_h=h, out_st=nst)
+                stash.misc.update(out_h=stash.suffix("conv_norm_out.h", h, HW), out_st=stash.suffix("conv_norm_out.st", nst, 1))
         taps = taps_down + [tap_at, tap_r0, tap_r1] + taps_up
         return eps, (taps if want_taps else None)
 
@@ -1058,18 +1063,12 @@ class HipUNet:
         return buf
 
     # ------------------------------------------------------------------ modules, backward (cond rows)
-    def _res_bwd(self, p, dout, S, st: dict, r0: Optional[int] = None):
-        """S: number of differentiated rows; r0: the first of them in the stashed tensors (default S: the cond half of a
-        CFG-doubled batch; backward_eps passes rows // 2 with S = rows - rows // 2, so rows = 1 differentiates its one row)."""
+    def _res_bwd(self, p, dout, S, st: dict):
+        """S: number of differentiated rows - the rows every tensor of the stash entry st holds (Stash.suffix)."""
         cfg, W = self.cfg, self.W
         sz = st["sz"]
         HW, G = sz[0] * sz[1], cfg.norm_groups
-        r0 = S if r0 is None else r0
-        if st.get("half"):        # the shared CFG prefix was evaluated on the cond rows only
-            x, h1, st1, st2 = st["x"], st["h1"], st["st1"], st["st2"]
-        else:
-            x, h1 = st["x"][r0 * HW:], st["h1"][r0 * HW:]
-            st1, st2 = st["st1"][r0:], st["st2"][r0:]
+        x, h1, st1, st2 = st["x"], st["h1"], st["st1"], st["st2"]
         dn2 = self._conv_wino(p + ".conv2.weight:winoT", dout, S, sz)
         if dn2 is None:
             dn2 = ops.conv3x3(dout, W[p + ".conv2.weight:T"], S, *sz)
@@ -1084,58 +1083,52 @@ class HipUNet:
         return ops.groupnorm_bwd(x, dn1, S, HW, G, st1, W[p + ".norm1.weight"], W[p + ".norm1.bias"], True,
                                  residual=sc)
 
-    def _tr_bwd(self, p, dout, S, st: dict, r0: Optional[int] = None, inject_bwd: Optional[Callable] = None):
-        """S / r0: see _res_bwd.  inject_bwd(block path, d p1) -> d (p1 in front of the injected attention): the backward of the
+    def _tr_bwd(self, p, dout, S, st: dict, inject_bwd: Optional[Callable] = None):
+        """S: see _res_bwd.  inject_bwd(block path, d p1) -> d (p1 in front of the injected attention): the backward of the
         injector the stashed forward ran between the self-attention and norm2 (backward_eps)."""
         cfg, W = self.cfg, self.W
         sz, heads = st["sz"], st["heads"]
         HW = sz[0] * sz[1]
-        r0 = S if r0 is None else r0
-        M0 = S * HW                                              # rows of every gradient tensor
-        O0 = r0 * HW                                             # where the differentiated rows start in the stashed tensors
         C = dout.shape[1]
         dh = C // heads
         scale = dh ** -0.5
         t = p + ".transformer_blocks.0"
-        half = st.get("half", ())
-        c = lambda a: a[O0:]
-        cc = lambda k: st[k] if k in half else st[k][O0:]        # activations [rows*HW, .] of the cond rows
-        cs = lambda k: st[k] if k in half else st[k][r0:]        # per-row statistics / lse of the cond rows
         dp3 = ops.gemm(dout, W[p + ".proj_out.weight:T"])
         dgg = ops.gemm(dp3, W[t + ".ff.net.2.weight:T"])
-        df = ops.geglu_bwd(st["f"], dgg, interleaved=True)            # f is stashed for the cond rows only
+        df = ops.geglu_bwd(st["f"], dgg, interleaved=True)
         da3 = ops.gemm(df, W[t + ".ff.net.0.proj.weight:T"])
-        dp2 = ops.layernorm_bwd(c(st["p2"]), da3, W[t + ".norm3.weight"], cc("st3"), residual=dp3)
-        # cross-attention: only dQ (K/V come from the constant text embeddings)
+        dp2 = ops.layernorm_bwd(st["p2"], da3, W[t + ".norm3.weight"], st["st3"], residual=dp3)
+        # cross-attention: only dQ (K/V come from the constant text embeddings - of every row of the evaluation: the differentiated
+        # rows' keys start at row `first`, the one thing the stash did not narrow)
         do2 = ops.gemm(dp2, W[t + ".attn2.to_out.0.weight:T"])
         cb = self.ctx["blocks"][t + ".attn2"]
         L, Lp = self.ctx["L"], self.ctx["Lp"]
+        first = self.ctx["rows"] - S
+        K2, V2 = cb["K"][first * Lp:], cb["V"][first * Lp:]
         if _ATTN_DQ_DELTA:      # delta = sum_d dO O in the prologue of the dQ launch (one launch and one read of dO fewer)
-            dq2, _ = ops.attn_bwd_dq_delta(cc("q2"), cb["K"][r0 * Lp:], cb["V"][r0 * Lp:], do2, cc("o2"), cs("lse2"), S, heads, HW, L, Lp, dh, scale)
+            dq2, _ = ops.attn_bwd_dq_delta(st["q2"], K2, V2, do2, st["o2"], st["lse2"], S, heads, HW, L, Lp, dh, scale)
         else:
-            delta2 = ops.attn_bwd_delta(cc("o2"), do2, S, heads, HW, dh)
-            dq2 = ops.attn_bwd_dq(cc("q2"), cb["K"][r0 * Lp:], cb["V"][r0 * Lp:], do2, cs("lse2"),
-                                  delta2, S, heads, HW, L, Lp, dh, scale)
+            delta2 = ops.attn_bwd_delta(st["o2"], do2, S, heads, HW, dh)
+            dq2 = ops.attn_bwd_dq(st["q2"], K2, V2, do2, st["lse2"], delta2, S, heads, HW, L, Lp, dh, scale)
         da2 = ops.gemm(dq2, W[t + ".attn2.to_q.weight:T"])
-        dp1 = ops.layernorm_bwd(cc("p1"), da2, W[t + ".norm2.weight"], cc("st2"), residual=dp2)
+        dp1 = ops.layernorm_bwd(st["p1"], da2, W[t + ".norm2.weight"], st["st2"], residual=dp2)
         if inject_bwd is not None:      # the stashed p1 is the injector's output: through it to the self-attention's output
             dp1 = inject_bwd(t, dp1)
         # self-attention
         do1 = ops.gemm(dp1, W[t + ".attn1.to_out.0.weight:T"])
-        qkv = cc("qkv")
+        qkv, o1, lse1 = st["qkv"], st["o1"], st["lse1"]
         Q, K, V = qkv[:, :C], qkv[:, C:2 * C], qkv[:, 2 * C:]
-        lse1 = cs("lse1")
-        dqkv = torch.empty(M0, 3 * C, device=self.dev, dtype=torch.float16)
+        dqkv = torch.empty(S * HW, 3 * C, device=self.dev, dtype=torch.float16)
         if _ATTN_DQ_DELTA:
-            _, delta1 = ops.attn_bwd_dq_delta(Q, K, V, do1, cc("o1"), lse1, S, heads, HW, HW, HW, dh, scale, out=dqkv[:, :C])
+            _, delta1 = ops.attn_bwd_dq_delta(Q, K, V, do1, o1, lse1, S, heads, HW, HW, HW, dh, scale, out=dqkv[:, :C])
         else:
-            delta1 = ops.attn_bwd_delta(cc("o1"), do1, S, heads, HW, dh)
+            delta1 = ops.attn_bwd_delta(o1, do1, S, heads, HW, dh)
             ops.attn_bwd_dq(Q, K, V, do1, lse1, delta1, S, heads, HW, HW, HW, dh, scale, out=dqkv[:, :C])
         ops.attn_bwd_dkv(Q, K, V, do1, lse1, delta1, S, heads, HW, HW, dh, scale, dK=dqkv[:, C:2 * C], dV=dqkv[:, 2 * C:])
         da1 = ops.gemm(dqkv, W[t + ".attn1.qkv:T"])
-        dpin = ops.layernorm_bwd(cc("pin"), da1, W[t + ".norm1.weight"], cc("st1"), residual=dp1)
+        dpin = ops.layernorm_bwd(st["pin"], da1, W[t + ".norm1.weight"], st["st1"], residual=dp1)
         dg = ops.gemm(dpin, W[p + ".proj_in.weight:T"])
-        return ops.groupnorm_bwd(cc("x"), dg, S, HW, cfg.norm_groups, cs("gst"), W[p + ".norm.weight"],
+        return ops.groupnorm_bwd(st["x"], dg, S, HW, cfg.norm_groups, st["gst"], W[p + ".norm.weight"],
                                  W[p + ".norm.bias"], False, residual=dout)
 
     # ------------------------------------------------------------------ backward
@@ -1143,13 +1136,13 @@ class HipUNet:
         """tap_grads: 9 fp16 tensors [S*s*s, C] (cond rows) in tap order.  Returns d loss / d x for the
         cond rows, fp16 [S*H*W, 8] (first 4 channels valid; H x W: the stashed forward's size)."""
         assert self.need_backward and self.inject is None, "backward with injected attention is not supported"
-        rows = stash.misc["rows"]
-        return self._backward_chain(stash, tap_grads[8], tap_grads, 2, rows // 2, rows // 2, None, False)
+        return self._backward_chain(stash, tap_grads[8], tap_grads, 2, None, False)
 
     def backward_eps(self, stash: Stash, d_eps: torch.Tensor, inject_bwd: Optional[Callable] = None) -> Optional[torch.Tensor]:
         """Backward from the UNet's output.  d_eps: fp16 [S*H*W, EPS_SEED_LD] (first 4 channels valid, the rest zero) for the rows
-        from r0 = the stashed forward's diff_from on (S = rows - r0; by default rows // 2: the cond half of a CFG-doubled batch, or the
-        single row of a rows = 1 evaluation; 0: every row of a trainer's batch) of a forward(..., stash, want_eps=True).
+        the stash holds - from stash.first, the stashed forward's diff_from, on (S = rows - first; by default rows // 2: the cond half of a
+        CFG-doubled batch, or the single row of a rows = 1 evaluation; 0: every row of a trainer's batch) - of a
+        forward(..., stash, want_eps=True).
         conv_out's data gradient, conv_norm_out's GroupNorm + SiLU backward, then every up block, the mid block and the down path.  inject_bwd: see _tr_bwd - the forward ran with an injector, whose parameter
         gradients are the point; the chain then stops in front of down_blocks.0.attentions.0 (nothing trainable lies further
         up) and returns None.  Without an injector: d loss / d x like backward().  All-fp16 mode, square maps, eager."""
@@ -1158,25 +1151,25 @@ class HipUNet:
             raise NotImplementedError("backward_eps: the accuracy mode (residual_fp32) is not supported")
         assert (self.inject is None) == (inject_bwd is None), "an injected forward needs the injector's backward (and only it)"
         cfg, W = self.cfg, self.W
-        rows, sz = stash.misc["rows"], (stash.misc["H"], stash.misc.get("W", stash.misc["H"]))
+        sz = (stash.misc["H"], stash.misc.get("W", stash.misc["H"]))
         if sz[0] != sz[1]:
             raise NotImplementedError("backward_eps: square maps only")
         assert "out_h" in stash.misc, "the stashed forward ran without want_eps"
-        r0 = stash.misc.get("diff_from", rows // 2)
-        S = rows - r0
+        S = stash.rows - stash.first
         HW = sz[0] * sz[1]
         assert d_eps.shape == (S * HW, EPS_SEED_LD)
         dn = ops.conv3x3(d_eps, W["conv_out.weight:T"], S, *sz)
-        dh = ops.groupnorm_bwd(stash.misc["out_h"][r0 * HW:], dn, S, HW, cfg.norm_groups, stash.misc["out_st"][r0:],
+        dh = ops.groupnorm_bwd(stash.misc["out_h"], dn, S, HW, cfg.norm_groups, stash.misc["out_st"],
                                W["conv_norm_out.weight"], W["conv_norm_out.bias"], True)
         nb = len(cfg.block_out_channels)
-        return self._backward_chain(stash, dh, [None] * 9, nb - 1, S, r0, inject_bwd, inject_bwd is not None)
+        return self._backward_chain(stash, dh, [None] * 9, nb - 1, inject_bwd, inject_bwd is not None)
 
-    def _backward_chain(self, stash: Stash, dh, tap_grads, first_up: int, S: int, r0: int, inject_bwd, stop_early: bool):
-        """The reversed graph from the output of up block `first_up` (after its upsampler, if it has one) to the input.
-        S rows are differentiated, starting at row r0 of the stashed tensors.  stop_early: return None after
-        down_blocks.0.attentions.0 instead of finishing the first ResnetBlock and conv_in."""
+    def _backward_chain(self, stash: Stash, dh, tap_grads, first_up: int, inject_bwd, stop_early: bool):
+        """The reversed graph from the output of up block `first_up` (after its upsampler, if it has one) to the input, on the
+        stash's rows - first differentiated rows.  stop_early: return None after down_blocks.0.attentions.0 instead of finishing
+        the first ResnetBlock and conv_in."""
         cfg, W = self.cfg, self.W
+        S = stash.rows - stash.first
         sz = (stash.misc["H"], stash.misc.get("W", stash.misc["H"]))
         nb = len(cfg.block_out_channels)
         lpb = cfg.layers_per_block
@@ -1192,9 +1185,6 @@ class HipUNet:
         n_skips = 1 + sum(lpb + (1 if i < nb - 1 else 0) for i in range(nb))
         gskip: List[Optional[torch.Tensor]] = [None] * n_skips
         # ---- up path, reversed (backward: blocks 2, 1, 0 - block 3 does not feed any tap; backward_eps: from block nb - 1)
-        cur = sz                                 # spatial size of up block first_up's output (after its upsampler; nb = 4)
-        for _ in range(nb - 1 - 3):              # generic: taps end at up block 2
-            pass
         # index of the skip consumed first by up block i: pops from the end
         pop_idx = n_skips
         consumed = {}
@@ -1202,7 +1192,7 @@ class HipUNet:
             for j in range(lpb + 1):
                 pop_idx -= 1
                 consumed[(i, j)] = pop_idx
-        cur = sz
+        cur = sz                                 # spatial size of up block first_up's output (after its upsampler; nb = 4)
         plan = up_block_plan(cfg)
         for i in range(first_up, -1, -1):
             if i < nb - 1:
@@ -1217,8 +1207,8 @@ class HipUNet:
                     dh = ops.sumpool2x2(du, S, *cur)
             for j in range(lpb, -1, -1):
                 if i > 0:
-                    dh = self._tr_bwd(f"up_blocks.{i}.attentions.{j}", dh, S, stash.tr[f"up_blocks.{i}.attentions.{j}"], r0, inject_bwd)
-                dcat = self._res_bwd(f"up_blocks.{i}.resnets.{j}", dh, S, stash.res[f"up_blocks.{i}.resnets.{j}"], r0)
+                    dh = self._tr_bwd(f"up_blocks.{i}.attentions.{j}", dh, S, stash.tr[f"up_blocks.{i}.attentions.{j}"], inject_bwd)
+                dcat = self._res_bwd(f"up_blocks.{i}.resnets.{j}", dh, S, stash.res[f"up_blocks.{i}.resnets.{j}"])
                 ch = plan[i][j][0]
                 k = consumed[(i, j)]
                 gskip[k] = add(gskip[k], dcat[:, ch:])
@@ -1227,11 +1217,11 @@ class HipUNet:
                 dh = add(dh, tap_grads[6 + i - 1])      # output of up block i-1 (after its upsampler)
         # ---- mid
         dh = add(dh, tap_grads[5])
-        dh = self._res_bwd("mid_block.resnets.1", dh, S, stash.res["mid_block.resnets.1"], r0)
+        dh = self._res_bwd("mid_block.resnets.1", dh, S, stash.res["mid_block.resnets.1"])
         dh = add(dh, tap_grads[3])
-        dh = self._tr_bwd("mid_block.attentions.0", dh, S, stash.tr["mid_block.attentions.0"], r0, inject_bwd)
+        dh = self._tr_bwd("mid_block.attentions.0", dh, S, stash.tr["mid_block.attentions.0"], inject_bwd)
         dh = add(dh, tap_grads[4])
-        dh = self._res_bwd("mid_block.resnets.0", dh, S, stash.res["mid_block.resnets.0"], r0)
+        dh = self._res_bwd("mid_block.resnets.0", dh, S, stash.res["mid_block.resnets.0"])
         # ---- down path, reversed
         k = n_skips - 1
         for i in range(nb - 1, -1, -1):
@@ -1246,9 +1236,9 @@ class HipUNet:
                 dh = add(dh, gskip[k]); k -= 1
                 if i < nb - 1:
                     dh = self._tr_bwd(f"down_blocks.{i}.attentions.{j}", dh, S,
-                                      stash.tr[f"down_blocks.{i}.attentions.{j}"], r0, inject_bwd)
+                                      stash.tr[f"down_blocks.{i}.attentions.{j}"], inject_bwd)
                     if stop_early and i == 0 and j == 0:
                         return None
-                dh = self._res_bwd(f"down_blocks.{i}.resnets.{j}", dh, S, stash.res[f"down_blocks.{i}.resnets.{j}"], r0)
+                dh = self._res_bwd(f"down_blocks.{i}.resnets.{j}", dh, S, stash.res[f"down_blocks.{i}.resnets.{j}"])
         dh = add(dh, gskip[0])
         return ops.conv3x3(dh, W["conv_in.weight:T"], S, *sz)

@@ -236,7 +236,7 @@ def test_backward_eps_all_rows_without_injector_vs_autograd(e2e, diff_from):
     net.prepare_context(ehs)
     stash = Stash()
     net.forward(ops.nchw_to_nhwc(x.to(DEV), CIN_PAD), list(ts), rows, h, stash, want_taps=False, want_eps=True, diff_from=diff_from)
-    assert stash.misc["diff_from"] == diff_from
+    assert stash.first == diff_from
     seed = torch.zeros(S * h * h, EPS_SEED_LD, dtype=torch.float16, device=DEV)
     seed[:, :4] = dE[diff_from:].reshape(S, 4, h * h).transpose(1, 2).reshape(S * h * h, 4).half().to(DEV)
     dx = ops.nhwc_to_nchw(net.backward_eps(stash, seed), S, 4, h, h).cpu()
@@ -285,14 +285,14 @@ def test_c320_transformer_block_all_rows_stashed(monkeypatch):
     tok = lambda t: t.permute(0, 2, 3, 1).reshape(rows * HW, C).half().to(DEV).contiguous()
     img = lambda t: t.float().cpu().view(rows, hh, hh, C).permute(0, 3, 1, 2)
     net.prepare_context(ehs)
-    stash = Stash()
+    stash = Stash(rows=rows, first=0)
     out, _ = net._tr_fwd(p, tok(x), rows, (hh, hh), heads, stash, diff_from=0)
     fused = [c for c in calls if c[0] in ("xattn_block", "ff_block_proj", "ff_block")]
     print(f"[C=320 block rows=3 diff_from=0] launches: {calls} -> {'fused stashing' if fused else 'per-operator'}")
     assert calls and all(kf in (0, None) for _, kf in calls) and all(kf == 0 for _, kf in fused)
     st = stash.tr[p]
     assert st["f"].shape[0] == rows * HW and st["q2"].shape[0] == rows * HW and st["lse2"].shape[0] == rows
-    dx = net._tr_bwd(p, tok(dout), rows, st, 0)
+    dx = net._tr_bwd(p, tok(dout), rows, st)
     for tag, got, i in (("out", img(out), 0), ("d x", img(dx), 1)):
         e, b = _rel(got, ref[i]), 2 * _rel(emu[i], ref[i])
         print(f"[C=320 block rows=3 diff_from=0] {tag}: hip {e:.3e} bound {b:.3e}")
