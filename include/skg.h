@@ -534,6 +534,16 @@ int skg_gaussian_sample(const void* moments, int ld, const float* noise, float* 
 int skg_cfg_dpmpp2m_step(const void* eps_u, const void* eps_c, int ld, int lo_off, const float* x, float* x0_io,
                          float* x_prev, float* eps_out, int samples, int HW, float g, float alpha_s,
                          float sigma_s, float a, float b, float c, int vpred, void* stream);
+/* The same update with the noise term of the stochastic solver (scheduler config algorithm_type "sde-dpmsolver++"):
+ *   x_prev = a*x + b*x0 + c*x0_before + d*z
+ * with  h = lambda_t - lambda_s,  a = (sigma_t/sigma_s)*exp(-h),  b = alpha_t*(1 - exp(-2h))  [second order: * (1 + 0.5/r0)],
+ * c = 0  [second order: -0.5*alpha_t*(1 - exp(-2h))/r0],  d = sigma_t*sqrt(1 - exp(-2h))  (DPMTables.coeffs_sde).
+ * z: caller-drawn N(0, 1), float NCHW like x (required).  The three products are summed as skg_cfg_dpmpp2m_step sums them and
+ * d*z is added on top as a rounded product: d = 0 gives that entry point's result bit for bit.  Additive entry point
+ * (SKG_ABI_VERSION unchanged). */
+int skg_cfg_dpmpp2m_sde_step(const void* eps_u, const void* eps_c, int ld, int lo_off, const float* x, const float* z,
+                             float* x0_io, float* x_prev, float* eps_out, int samples, int HW, float g, float alpha_s,
+                             float sigma_s, float a, float b, float c, float d, int vpred, void* stream);
 /* guidance update, modules/pipeline.py:159-161, per sample s:
  *   g = -grad[s] (fp16 NHWC [HW][ld], first 4 ch);  alpha = sqrt(2)*||x_in - x_prev|| / ||g|| * beta
  *   x_prev += alpha * g.   aux float [samples][4] receives (alpha, ||g||, ||x_in-x_prev||*sqrt2, 0). */

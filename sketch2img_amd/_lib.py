@@ -28,7 +28,8 @@ LIB_PATH = os.environ.get("SKG_LIB") or os.path.join(_HERE, "libskg.so")
 # list with nullable pointers selecting the arm: INTEGRATION.md has the migration table), so that a stale build selected through
 # SKG_LIB fails at load instead of receiving shifted arguments.  Added since without a bump (a new symbol is compatible; a build
 # that lacks it fails the export check below): skg_cfg_ddim_eta_step, the DDIM step with the eta > 0 noise term;
-# skg_nonfinite_flag and skg_adamw_step_guarded, the dynamic loss scale's verdict and its guarded optimizer step
+# skg_nonfinite_flag and skg_adamw_step_guarded, the dynamic loss scale's verdict and its guarded optimizer step;
+# skg_cfg_dpmpp2m_sde_step, the DPM-Solver++ 2M step with the noise term of algorithm_type "sde-dpmsolver++"
 ABI_VERSION = 6
 
 # spec letters: p = device/host pointer, i = int, f = float, u = unsigned, z = size_t (return only)
@@ -94,6 +95,7 @@ SIGNATURES = {
     "skg_image_to_u8": ("i", "pipziffp"),
     "skg_gaussian_sample": ("i", "pippiiifp"),
     "skg_cfg_dpmpp2m_step": ("i", "ppiippppiiffffffip"),
+    "skg_cfg_dpmpp2m_sde_step": ("i", "ppiipppppiifffffffip"),
     "skg_guidance_update": ("i", "pipppiifp"),
     "skg_box_probe_mfma": ("i", "pip"),
     # sketch generator (anime2sketch.py): additive entry points, same ABI version

@@ -386,11 +386,15 @@ __global__ __launch_bounds__(256) void gaussian_sample_kernel(const half_t* __re
 // CFG combine + one DPM-Solver++ (2M) update: x0 = (x - sigma_s*eps)/alpha_s; x_prev = a*x + b*x0 + c*x0_before.
 // x0_io holds the previous step's x0 on entry (ignored when c == 0) and this step's x0 on exit.
 // vpred: the model output is v: x0 = alpha_s x - sigma_s v (eps_out: alpha_s v + sigma_s x)
+// NOISE (algorithm_type "sde-dpmsolver++"): x_prev += d * z, z a caller-drawn N(0, 1) tensor indexed like x (a, b, c then are
+// DPMTables.coeffs_sde's); as in cfg_ddim_kernel the two extra arguments sit at the end so that the NOISE = false instantiation
+// keeps the instruction stream and the argument offsets of the deterministic kernel
+template <bool NOISE>
 __global__ __launch_bounds__(256) void cfg_dpm_kernel(const half_t* __restrict__ eu, const half_t* __restrict__ ec,
                                                       int ld, int lo_off, const float* __restrict__ x, float* __restrict__ x0_io,
                                                       float* __restrict__ xp, float* __restrict__ eps_out,
                                                       int samples, int HW, float g, float alpha_s, float sigma_s,
-                                                      float a, float b, float c, int vpred) {
+                                                      float a, float b, float c, int vpred, const float* __restrict__ z, float d) {
   const size_t total = (size_t)samples * 4 * HW;
   for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
     const int p = (int)(i % HW);
@@ -411,6 +415,12 @@ __global__ __launch_bounds__(256) void cfg_dpm_kernel(const half_t* __restrict__
     }
     float r = a * xv + b * x0;
     if (c != 0.f) r += c * x0_io[i];
+    if (NOISE) {
+      // the three products above are summed as the deterministic instantiation sums them; the noise term goes on top as a rounded
+      // product and an add: d = 0 reproduces the deterministic step bit for bit, whatever (finite) z holds
+#pragma clang fp contract(off)
+      r += d * z[i];
+    }
     x0_io[i] = x0;
     xp[i] = r;
     if (eps_out) eps_out[i] = e;
@@ -641,10 +651,24 @@ extern "C" int skg_cfg_dpmpp2m_step(const void* eps_u, const void* eps_c, int ld
   SKG_REQUIRE(eps_u && eps_c && x && x0_io && x_prev && samples > 0 && HW > 0 && ld >= 4 && alpha_s > 0.f);
   SKG_REQUIRE(vpred == 0 || vpred == 1);
   SKG_REQUIRE(lo_off >= 0 && (lo_off == 0 || ld >= lo_off + 4));
-  hipLaunchKernelGGL(cfg_dpm_kernel, dim3(ew_grid((size_t)samples * 4 * HW)), dim3(256), 0, (hipStream_t)stream,
+  hipLaunchKernelGGL(cfg_dpm_kernel<false>, dim3(ew_grid((size_t)samples * 4 * HW)), dim3(256), 0, (hipStream_t)stream,
                      (const half_t*)eps_u, (const half_t*)eps_c, ld, lo_off, x, x0_io, x_prev, eps_out, samples, HW, g,
-                     alpha_s, sigma_s, a, b, c, vpred);
+                     alpha_s, sigma_s, a, b, c, vpred, (const float*)nullptr, 0.f);
   SKG_CHECK_LAUNCH("skg_cfg_dpmpp2m_step");
+  return SKG_OK;
+}
+
+extern "C" int skg_cfg_dpmpp2m_sde_step(const void* eps_u, const void* eps_c, int ld, int lo_off, const float* x, const float* z,
+                                        float* x0_io, float* x_prev, float* eps_out, int samples, int HW, float g,
+                                        float alpha_s, float sigma_s, float a, float b, float c, float d, int vpred,
+                                        void* stream) {
+  SKG_REQUIRE(eps_u && eps_c && x && z && x0_io && x_prev && samples > 0 && HW > 0 && ld >= 4 && alpha_s > 0.f);
+  SKG_REQUIRE(vpred == 0 || vpred == 1);
+  SKG_REQUIRE(lo_off >= 0 && (lo_off == 0 || ld >= lo_off + 4));
+  hipLaunchKernelGGL(cfg_dpm_kernel<true>, dim3(ew_grid((size_t)samples * 4 * HW)), dim3(256), 0, (hipStream_t)stream,
+                     (const half_t*)eps_u, (const half_t*)eps_c, ld, lo_off, x, x0_io, x_prev, eps_out, samples, HW, g,
+                     alpha_s, sigma_s, a, b, c, vpred, z, d);
+  SKG_CHECK_LAUNCH("skg_cfg_dpmpp2m_sde_step");
   return SKG_OK;
 }
 

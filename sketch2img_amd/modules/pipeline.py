@@ -30,7 +30,7 @@ import numpy as np
 import torch
 
 from ..config import SD15, SD21, UNetConfig, tap_channels
-from ..sampler import DDIMTables, DPMTables, HipSampler, check_eta, check_generators, draw_noise
+from ..sampler import DPM_ALGORITHMS, DDIMTables, DPMTables, HipSampler, check_eta, check_generators, draw_noise
 from .latent_predictor import LatentEdgePredictor, hook_unet
 
 logger = logging.getLogger(__name__)      # (the reference: diffusers.utils.logging.get_logger(__name__), modules/pipeline.py:11)
@@ -439,12 +439,19 @@ class AntiGradientPipeline:
             raise NotImplementedError("DDIM clip_sample=True is not implemented (Stable Diffusion uses clip_sample=False; "
                                       "note that diffusers' DDIMScheduler() default is True)")
         if "DPMSolverMultistep" in name or get("algorithm_type", None) is not None:
-            if get("algorithm_type", "dpmsolver++") != "dpmsolver++" or get("solver_type", "midpoint") != "midpoint":
-                raise NotImplementedError("DPM-Solver: only algorithm_type='dpmsolver++', solver_type='midpoint'")
+            algorithm = get("algorithm_type", "dpmsolver++")
+            if algorithm not in DPM_ALGORITHMS or get("solver_type", "midpoint") != "midpoint":
+                raise NotImplementedError("DPM-Solver: only algorithm_type='dpmsolver++' or 'sde-dpmsolver++', solver_type='midpoint'")
             if get("thresholding", False):
                 raise NotImplementedError("DPM-Solver++ without thresholding only")
+            karras = bool(get("use_karras_sigmas", False))
+            other = [k for k in ("use_lu_lambdas", "use_exponential_sigmas", "use_beta_sigmas", "euler_at_final") if get(k, False)]
+            if other or (karras and get("final_sigmas_type", "zero") != "zero"):
+                raise NotImplementedError(f"DPM-Solver++: {', '.join(other) or 'final_sigmas_type'} is not implemented (uniform "
+                                          "timesteps or use_karras_sigmas with final_sigmas_type='zero')")
             return DPMTables.make(num_inference_steps, get("num_train_timesteps", 1000), get("beta_start", 0.00085),
-                                  get("beta_end", 0.012), get("lower_order_final", True), get("solver_order", 2), vpred)
+                                  get("beta_end", 0.012), get("lower_order_final", True), get("solver_order", 2), vpred,
+                                  karras, algorithm)
         if "DDIM" not in name and not isinstance(sch, (dict, SimpleNamespace)):
             raise NotImplementedError(f"{name}: DDIMScheduler and DPMSolverMultistepScheduler are implemented")
         return DDIMTables.make(num_inference_steps, get("num_train_timesteps", 1000), get("beta_start", 0.00085),

@@ -1052,6 +1052,22 @@ def cfg_dpmpp2m_step(eps_u, eps_c, x, x0_io, samples, HW, g, coeffs: Tuple[float
     return (x_prev, eps_out) if want_eps else x_prev
 
 
+def cfg_dpmpp2m_sde_step(eps_u, eps_c, x, z, x0_io, samples, HW, g, coeffs: Tuple[float, float, float, float, float, float],
+                         want_eps=False, lo_off: int = 0, v_prediction: bool = False):
+    """cfg_dpmpp2m_step with the stochastic solver's noise term: coeffs = DPMTables.coeffs_sde(i, order) = (alpha_s, sigma_s, a, b,
+    c, d), x_prev = a x + b x0 + c x0_before + d z.  z: N(0, 1) drawn by the caller, fp32 and contiguous in x's shape."""
+    _f16(eps_u, eps_c)
+    assert z is not None and z.is_cuda and z.dtype == torch.float32 and z.is_contiguous() and z.shape == x.shape, \
+        "z: contiguous fp32 CUDA tensor of the latents' shape"
+    x_prev = torch.empty_like(x)
+    eps_out = torch.empty_like(x) if want_eps else None
+    al, sg, a, b, c, d = coeffs
+    check(lib.skg_cfg_dpmpp2m_sde_step(_p(eps_u), _p(eps_c), _ld(eps_u), lo_off, _p(x), _p(z), _p(x0_io), _p(x_prev), _p(eps_out),
+                                       samples, HW, g, al, sg, a, b, c, d, int(bool(v_prediction)), _stream()),
+          "skg_cfg_dpmpp2m_sde_step")
+    return (x_prev, eps_out) if want_eps else x_prev
+
+
 def guidance_update(grad, x_in, x_prev, samples, HW, beta):
     """In place: x_prev += alpha * (-grad).  Returns aux [samples,4] = (alpha, ||g||, sqrt2*||dx||, 0)."""
     _f16(grad)

@@ -35,10 +35,12 @@ class DDIMScheduler(_ConfigScheduler):
 class DPMSolverMultistepScheduler(_ConfigScheduler):
     def __init__(self, num_train_timesteps=1000, beta_start=0.00085, beta_end=0.012, beta_schedule="scaled_linear",
                  trained_betas=None, solver_order=2, predict_epsilon=True, thresholding=False,
-                 algorithm_type="dpmsolver++", solver_type="midpoint", lower_order_final=True, **kwargs):
+                 algorithm_type="dpmsolver++", solver_type="midpoint", lower_order_final=True, use_karras_sigmas=False,
+                 **kwargs):
         if beta_schedule != "scaled_linear" or trained_betas is not None:
             raise NotImplementedError("scaled_linear betas (Stable Diffusion) only")
         super().__init__(num_train_timesteps=num_train_timesteps, beta_start=beta_start, beta_end=beta_end,
                          beta_schedule=beta_schedule, trained_betas=trained_betas, solver_order=solver_order,
                          predict_epsilon=predict_epsilon, thresholding=thresholding, algorithm_type=algorithm_type,
-                         solver_type=solver_type, lower_order_final=lower_order_final, **kwargs)
+                         solver_type=solver_type, lower_order_final=lower_order_final, use_karras_sigmas=use_karras_sigmas,
+                         **kwargs)
