@@ -549,6 +549,16 @@ int skg_cfg_dpmpp2m_sde_step(const void* eps_u, const void* eps_c, int ld, int l
  *   x_prev += alpha * g.   aux float [samples][4] receives (alpha, ||g||, ||x_in-x_prev||*sqrt2, 0). */
 int skg_guidance_update(const void* grad, int ld, const float* x_in, float* x_prev, float* aux,
                         int samples, int HW, float beta, void* stream);
+/* img2img start and masked repaint (diffusers' scheduler.add_noise and the legacy inpainting blend) on float NCHW latents
+ * [samples][4][HW]:   r = a*init + s*noise   with (a, s) the schedule level (DDIMTables.level / DPMTables.level).
+ *   mask NULL:  x = r.
+ *   mask:       float [mask_samples][HW], one channel for the four, mask_samples 1 (one mask for every sample) or `samples`;
+ *               x = m*x + (1 - m)*r in place (1 = repaint, 0 = keep the original).
+ * Every product is rounded before its sum: m = 1 leaves x as it is, m = 0 gives the mask-free r, (a, s) = (1, 0) gives init,
+ * each bit for bit.  Any HW (16-byte accesses when HW % 4 == 0 and the operands are 16-byte aligned).  Additive entry point
+ * (SKG_ABI_VERSION unchanged). */
+int skg_latent_renoise(const float* init, const float* noise, const float* mask, int mask_samples, float* x, int samples,
+                       int HW, float a, float s, void* stream);
 
 /* Box calibration (bench.py `config.box_mfma_tflops`; no reference call site - measurement infrastructure): one launch of
  * SKG_BOX_PROBE_WORKGROUPS workgroups x 8 waves, each wave `iters` rounds of 40 register-resident 16x16x32 fp16 MFMAs on

@@ -459,7 +459,68 @@ __global__ __launch_bounds__(256) void guidance_update_kernel(const half_t* __re
   }
 }
 
+// img2img start / masked repaint: r = a*init + s*noise; no mask: x = r, mask: x = m*x + (1 - m)*r in place.  Flat float NCHW
+// [samples][4][HW]; the mask is [mask_samples][HW], one channel for the four (mask_samples 1: one mask for every sample).
+// V = 4: HW % 4 == 0 and 16-byte aligned operands - four consecutive elements share a channel row and four mask cells.
+// Every product is rounded before its sum (no fma), so m = 1 keeps x, m = 0 gives the mask-free r and (a, s) = (1, 0) gives init,
+// each bit for bit on finite operands.
+__device__ __forceinline__ float renoise_one(float iv, float nv, float a, float s) {
+#pragma clang fp contract(off)
+  return a * iv + s * nv;
+}
+
+__device__ __forceinline__ float renoise_blend(float m, float xv, float r) {
+#pragma clang fp contract(off)
+  return m * xv + (1.f - m) * r;
+}
+
+template <int V>
+__global__ __launch_bounds__(256) void latent_renoise_kernel(const float* init, const float* noise, const float* mask,
+                                                             int mask_samples, float* x, int samples, int HW, float a, float s) {
+  const size_t per = (size_t)4 * HW;
+  const size_t total = (size_t)samples * per / V;
+  for (size_t g = (size_t)blockIdx.x * 256 + threadIdx.x; g < total; g += (size_t)gridDim.x * 256) {
+    const size_t i = g * V;
+    size_t mi = 0;
+    if (mask) {
+      const size_t smp = i / per;
+      mi = (mask_samples == 1 ? 0 : smp * (size_t)HW) + (i - smp * per) % (size_t)HW;
+    }
+    if (V == 4) {
+      const float4 iv = *reinterpret_cast<const float4*>(init + i), nv = *reinterpret_cast<const float4*>(noise + i);
+      float4 r = {renoise_one(iv.x, nv.x, a, s), renoise_one(iv.y, nv.y, a, s), renoise_one(iv.z, nv.z, a, s),
+                  renoise_one(iv.w, nv.w, a, s)};
+      if (mask) {
+        const float4 m = *reinterpret_cast<const float4*>(mask + mi), xv = *reinterpret_cast<const float4*>(x + i);
+        r = float4{renoise_blend(m.x, xv.x, r.x), renoise_blend(m.y, xv.y, r.y), renoise_blend(m.z, xv.z, r.z),
+                   renoise_blend(m.w, xv.w, r.w)};
+      }
+      *reinterpret_cast<float4*>(x + i) = r;
+    } else {
+      float r = renoise_one(init[i], noise[i], a, s);
+      if (mask) r = renoise_blend(mask[mi], x[i], r);
+      x[i] = r;
+    }
+  }
+}
+
 }  // namespace
+
+extern "C" int skg_latent_renoise(const float* init, const float* noise, const float* mask, int mask_samples, float* x,
+                                  int samples, int HW, float a, float s, void* stream) {
+  SKG_REQUIRE(init && noise && x && samples > 0 && HW > 0);
+  SKG_REQUIRE(!mask || mask_samples == 1 || mask_samples == samples);
+  const size_t total = (size_t)samples * 4 * HW;
+  const bool vec = HW % 4 == 0 && skg_aligned(init, 16) && skg_aligned(noise, 16) && skg_aligned(x, 16) && (!mask || skg_aligned(mask, 16));
+  if (vec)
+    hipLaunchKernelGGL(latent_renoise_kernel<4>, dim3(ew_grid(total / 4)), dim3(256), 0, (hipStream_t)stream, init, noise, mask,
+                       mask_samples, x, samples, HW, a, s);
+  else
+    hipLaunchKernelGGL(latent_renoise_kernel<1>, dim3(ew_grid(total)), dim3(256), 0, (hipStream_t)stream, init, noise, mask,
+                       mask_samples, x, samples, HW, a, s);
+  SKG_CHECK_LAUNCH("skg_latent_renoise");
+  return SKG_OK;
+}
 
 extern "C" int skg_geglu_fwd(const void* H, int ldh, void* Y, int ldy, int M, int F, int interleaved,
                              void* stream) {

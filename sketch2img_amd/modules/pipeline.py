@@ -30,7 +30,7 @@ import numpy as np
 import torch
 
 from ..config import SD15, SD21, UNetConfig, tap_channels
-from ..sampler import DPM_ALGORITHMS, DDIMTables, DPMTables, HipSampler, check_eta, check_generators, draw_noise
+from ..sampler import DPM_ALGORITHMS, DDIMTables, DPMTables, HipSampler, check_eta, check_generators, draw_noise, start_step
 from .latent_predictor import LatentEdgePredictor, hook_unet
 
 logger = logging.getLogger(__name__)      # (the reference: diffusers.utils.logging.get_logger(__name__), modules/pipeline.py:11)
@@ -326,6 +326,79 @@ class AntiGradientPipeline:
                                   device=gdev, dtype=torch.float32)
         return latents.to(device=device, dtype=torch.float32)       # init_noise_sigma = 1 for DDIM
 
+    # ------------------------------------------------------------------ img2img / masked repaint inputs (host side only)
+    @staticmethod
+    def _pil_to_tensor(images, mode: str, height: int, width: int, what: str) -> torch.Tensor:
+        """One PIL image or a list of them -> float [B, C, height, width] in [0, 1] (torchvision's ToTensor).  No resize: an image
+        of another size is a ValueError."""
+        out = []
+        for im in (images if isinstance(images, (list, tuple)) else [images]):
+            if not hasattr(im, "convert") or not hasattr(im, "size"):
+                raise ValueError(f"`{what}` has to be a tensor, a PIL image or a list of PIL images but holds {type(im)}")
+            if tuple(im.size) != (width, height):
+                raise ValueError(f"`{what}` is {im.size[0]} x {im.size[1]} px but the call samples {width} x {height} px "
+                                 "(width x height): resize it first")
+            a = torch.from_numpy(np.array(im.convert(mode), dtype=np.uint8))
+            out.append((a[..., None] if a.dim() == 2 else a).permute(2, 0, 1).float().div(255))
+        return torch.stack(out)
+
+    def _prepare_image(self, image, S: int, height: int, width: int) -> torch.Tensor:
+        """`image` -> float [1 or S, 3, height, width] in [-1, 1] (pixels, to be encoded) or [1 or S, 4, height/8, width/8]
+        (latents, used as given); anything else is a ValueError."""
+        f = self.vae_scale_factor
+        if torch.is_tensor(image):
+            img = image
+        else:
+            img = (self._pil_to_tensor(image, "RGB", height, width, "image") - 0.5) / 0.5      # ToTensor + Normalize(0.5, 0.5)
+        if img.dim() != 4 or img.shape[0] not in (1, S) or img.shape[1] not in (3, 4) or not img.is_floating_point():
+            raise ValueError(f"`image` has to be a float tensor [1 or {S}, 3, {height}, {width}] in [-1, 1] or latents "
+                             f"[1 or {S}, 4, {height // f}, {width // f}] but is {tuple(img.shape)} {img.dtype}")
+        want = (height, width) if img.shape[1] == 3 else (height // f, width // f)
+        if tuple(img.shape[2:]) != want:
+            raise ValueError(f"`image` with {img.shape[1]} channels has to be {want[0]} x {want[1]} (height x width) but is "
+                             f"{img.shape[2]} x {img.shape[3]}: resize it first")
+        if img.shape[1] == 3 and not self._vae_encodes():
+            raise ValueError("`image` given as pixels needs a VAE with `encode` (pass vae=sketch2img_amd.vae.AutoencoderKL(...) with "
+                             "encoder weights), or pass already-encoded latents [.., 4, height/8, width/8]")
+        return img
+
+    def _prepare_mask(self, mask_image, S: int, height: int, width: int) -> torch.Tensor:
+        """`mask_image` -> float [1 or S, 1, height/8, width/8] in [0, 1], 1 = repaint.  A pixel-resolution mask is reduced by the
+        8 x 8 block mean and stays soft: a latent cell is kept exactly where all of its 64 pixels are 0."""
+        f = self.vae_scale_factor
+        m = mask_image if torch.is_tensor(mask_image) else self._pil_to_tensor(mask_image, "L", height, width, "mask_image")
+        small = (height // f, width // f)
+        if m.dim() != 4 or m.shape[0] not in (1, S) or m.shape[1] != 1 or not m.is_floating_point() \
+                or tuple(m.shape[2:]) not in ((height, width), small):
+            raise ValueError(f"`mask_image` has to be a float tensor [1 or {S}, 1, {height}, {width}] or [1 or {S}, 1, {small[0]}, "
+                             f"{small[1]}] in [0, 1] but is {tuple(m.shape)} {m.dtype}")
+        m = m.float()
+        if tuple(m.shape[2:]) != small:
+            m = torch.nn.functional.avg_pool2d(m, f)
+        return m
+
+    def _vae_encodes(self) -> bool:
+        from ..vae import AutoencoderKL
+        if isinstance(self.vae, AutoencoderKL):
+            return any(k.startswith("encoder.") for k in self.vae.state_dict())
+        return self.vae is not None and hasattr(self.vae, "encode")
+
+    def _encode_image(self, img: torch.Tensor, S: int, height: int, width: int, device, generator) -> torch.Tensor:
+        """Pixels [1 or S, 3, height, width] -> latents [S, 4, height/8, width/8] = latent_dist.sample() * 0.18215 (app.py:109).  The
+        posterior noise is the call's first draw from `generator`, [S, 4, h, w] drawn like the initial latents."""
+        from ..vae import AutoencoderKL
+        img = img.to(device, torch.float32).expand(S, -1, -1, -1)
+        if isinstance(self.vae, AutoencoderKL):
+            self.vae.hip                                        # (raises unless the VAE was moved to the GPU)
+            pn = self.prepare_latents(S, self.unet.in_channels, height, width, torch.float32, device, generator)
+            return self.vae._hip_enc.encode(img, pn, 0.18215)
+        img = img.to(getattr(self.vae, "dtype", img.dtype))
+        if isinstance(generator, (list, tuple)):
+            z = torch.cat([self.vae.encode(img[s:s + 1]).latent_dist.sample(generator[s]) for s in range(S)])
+        else:
+            z = self.vae.encode(img).latent_dist.sample(generator)
+        return z.to(device, torch.float32) * 0.18215
+
     def decode_latents(self, latents):
         """diffusers decode_latents: /0.18215, VAE decode, /2 + 0.5, clamp, NHWC fp32 numpy."""
         if self.vae is None:
@@ -362,7 +435,15 @@ class AntiGradientPipeline:
                  eta: float = 0.0, generator=None, latents: Optional[torch.Tensor] = None,
                  output_type: Optional[str] = "pil", return_dict: bool = True,
                  callback: Optional[Callable[[int, int, torch.Tensor], None]] = None,
-                 callback_steps: Optional[int] = 1, sketch_image=None):
+                 callback_steps: Optional[int] = 1, sketch_image=None, image=None, strength: float = 0.8, mask_image=None):
+        """``image``, ``strength``: img2img (diffusers' StableDiffusionImg2ImgPipeline) - the trajectory starts from the picture,
+        re-noised to schedule entry ``start_step(num_inference_steps, strength)``, and runs the remaining steps.  ``image`` is a
+        float tensor [1 or S, 3, height, width] in [-1, 1], a PIL image or a list of them of exactly width x height (both encoded
+        by the VAE), or latents [1 or S, 4, height/8, width/8] used as given.  ``latents``, if given too, is the noise eps.
+        ``mask_image`` (needs ``image``): float [1 or S, 1, height, width] or [.., height/8, width/8] in [0, 1] or a PIL "L"
+        image, 1 = repaint, 0 = keep the original - the legacy inpainting loop: after every step the kept part is put back from
+        the re-noised original.  Draws from ``generator``, in this order: the VAE posterior noise (pixels only), eps (unless
+        ``latents`` is given), then the per-step noise (eta > 0 or the SDE solver)."""
         height = height or self.unet.config.sample_size * self.vae_scale_factor
         width = width or self.unet.config.sample_size * self.vae_scale_factor
         self.check_inputs(prompt, height, width, callback_steps)
@@ -378,8 +459,21 @@ class AntiGradientPipeline:
             raise ValueError("`sketch_image` (LGP guidance) needs classifier-free guidance: pass guidance_scale > 1")
         check_generators(generator, S)
         self._check_latents_shape(latents, S, self.unet.in_channels, height, width)     # (ahead of the text encoder's device work)
+        img = mask = None
+        first = 0
+        if image is not None:
+            first = start_step(num_inference_steps, strength)
+            img = self._prepare_image(image, S, height, width)
+            if mask_image is not None:
+                mask = self._prepare_mask(mask_image, S, height, width)
+        elif mask_image is not None:
+            raise ValueError("`mask_image` marks the region of `image` to repaint: pass `image` with it")
         ehs = self._encode_prompt(prompt, device, num_images_per_prompt, do_classifier_free_guidance, negative_prompt)
         tab = self._tables(num_inference_steps)
+        init = None
+        if img is not None:
+            init = self._encode_image(img, S, height, width, device, generator) if img.shape[1] == 3 else img
+            init = init.to(device, torch.float32).expand(S, -1, -1, -1).contiguous()
         lat = self.prepare_latents(S, self.unet.in_channels, height, width, torch.float32, device, generator, latents)
 
         net = self.unet.hip
@@ -398,7 +492,8 @@ class AntiGradientPipeline:
         if callback is not None:
             cb = lambda i, t, x: callback(i, t, x) if i % callback_steps == 0 else None
         out = sampler.sample(lat, target, num_inference_steps, guidance_scale, 1.6, callback=cb, tables=tab, eta=eta,
-                             generator=generator, classifier_free=do_classifier_free_guidance)
+                             generator=generator, classifier_free=do_classifier_free_guidance, init_latents=init, start_step=first,
+                             mask=mask)
         self.last_aux = sampler.last_aux
         if lgp is not None:
             self.lgp_model._sync_running_stats()

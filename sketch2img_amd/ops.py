@@ -1077,6 +1077,29 @@ def guidance_update(grad, x_in, x_prev, samples, HW, beta):
     return aux
 
 
+def latent_renoise(init, noise, a: float, s: float, x=None, mask=None):
+    """r = a*init + s*noise on fp32 latents [S, 4, h, w] (scheduler.add_noise at the schedule level (a, s)).  Without a mask: x = r,
+    x allocated when None.  With a mask - fp32 [1 or S, 1, h, w], 1 = repaint, 0 = keep - x is updated in place:
+    x = m*x + (1 - m)*r.  Returns x."""
+    chk = lambda t, what: (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous(), f"{what}: contiguous fp32 CUDA tensor")
+    for t, what in ((init, "init"), (noise, "noise")):
+        ok, msg = chk(t, what)
+        assert ok and t.dim() == 4 and t.shape[1] == 4 and t.shape == init.shape, msg + " [S, 4, h, w]"
+    S, _, h, w = init.shape
+    if x is None:
+        assert mask is None, "latent_renoise: the masked blend updates x in place and needs it"
+        x = torch.empty_like(init)
+    ok, msg = chk(x, "x")
+    assert ok and x.shape == init.shape, msg + " of init's shape"
+    ms = 0
+    if mask is not None:
+        ok, msg = chk(mask, "mask")
+        assert ok and mask.dim() == 4 and tuple(mask.shape[1:]) == (1, h, w), msg + f" [1 or S, 1, {h}, {w}], got {tuple(mask.shape)}"
+        ms = mask.shape[0]
+    check(lib.skg_latent_renoise(_p(init), _p(noise), _p(mask), ms, _p(x), S, h * w, a, s, _stream()), "skg_latent_renoise")
+    return x
+
+
 # ---- sketch generator (anime2sketch.py) ------------------------------------------------------------------------------------
 CONVT_EPI_NONE, CONVT_EPI_TANH = 0, 1
 

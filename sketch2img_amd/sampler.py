@@ -106,6 +106,27 @@ class DDIMTables:
         """get_noise_level's factor sqrt(1 - alphas_cumprod[t]) (modules/pipeline.py:133)."""
         return float((1 - self.alphas_cumprod[t]) ** 0.5)
 
+    def level(self, j: int):
+        """(a, s) of schedule entry j in 0..T as fp32 floats: a latent at entry j is a*x0 + s*eps (scheduler.add_noise at
+        timesteps[j]) - sqrt(abar_t), sqrt(1 - abar_t), the floats coeffs(t) starts with.  Entry T is the clean target (1, 0)."""
+        if j == len(self.timesteps):
+            return 1.0, 0.0
+        a_t = self.alphas_cumprod[int(self.timesteps[j])]
+        return float(a_t ** 0.5), float((1 - a_t) ** 0.5)
+
+
+def start_step(num_inference_steps: int, strength: float) -> int:
+    """The schedule entry an img2img trajectory starts at, diffusers' get_timesteps: init = min(int(T * strength), T) steps run,
+    the last ones of the schedule, so the start is T - init.  strength 1 starts at entry 0 (from a*init + s*eps at that level, not
+    from pure noise); a strength that leaves no step to run is refused."""
+    if not 0.0 <= strength <= 1.0:          # (also refuses nan)
+        raise ValueError(f"The value of strength should in [0.0, 1.0] but is {strength}")
+    T = int(num_inference_steps)
+    init = min(int(T * strength), T)
+    if init == 0:
+        raise ValueError(f"strength = {strength} with {T} inference steps leaves int({T} * {strength}) = 0 steps: no step would run")
+    return T - init
+
 
 DPM_ALGORITHMS = ("dpmsolver++", "sde-dpmsolver++")
 
@@ -202,6 +223,15 @@ class DPMTables:
         al, sg = float(self.alpha_t[t]), float(self.sigma_t[t])
         return al, sg, math.log(al) - math.log(sg)
 
+    def level(self, j: int):
+        """(a, s) of schedule entry j in 0..N as fp32 floats, the first two values of source(j): a latent at entry j is
+        a*x0 + s*eps.  Entry N is the clean target (1, 0) - the uniform schedule's source(N) is the table at t = 0, which the final
+        step's x_prev is not quite (its noise is dropped, as diffusers' inpainting puts back the un-noised original)."""
+        if j == len(self.timesteps):
+            return 1.0, 0.0
+        al, sg, _ = self.source(j)
+        return _f32(al), _f32(sg)
+
     def _coeffs_karras(self, i: int, order: int):
         """coeffs() from the sigmas, float64 until the final cast (the kernel takes fp32 scalars).  The last step targets sigma = 0:
         x_prev = x0 by definition, no exp / log is evaluated there."""
@@ -260,12 +290,13 @@ def guided_step(i: int, T: int) -> bool:
 
 
 def graph_key(tab, shape, unguided: bool, guidance_scale: float, beta: float, share_cfg_prefix: bool, eta: float = 0.0,
-              classifier_free: bool = True) -> tuple:
+              classifier_free: bool = True, start_step: int = 0, masked: bool = False) -> tuple:
     """Everything that is baked into the kernel arguments of a captured set of steps: the schedule (timesteps AND the table values
     the per-step coefficients come from - two schedulers may share timesteps and differ in betas / final alpha), the prediction
     type, shapes, the guidance constants (v_prediction was missing -> a stale graph would have been replayed), eta (the
     step kernel and its sigma / c_dir), whether the UNet runs the CFG-doubled batch or the cond rows alone, and for DPM-Solver++
-    the sigma spacing with its per-step sigmas and the algorithm type (ODE or SDE step kernel)."""
+    the sigma spacing with its per-step sigmas and the algorithm type (ODE or SDE step kernel); for img2img the entry the captured
+    steps start at and whether each of them ends with the masked blend."""
     acp = tab.alphas_cumprod
     sigmas = getattr(tab, "sigmas", None)
     return (type(tab).__name__, tuple(int(t) for t in tab.timesteps), tuple(shape), bool(unguided),
@@ -273,7 +304,7 @@ def graph_key(tab, shape, unguided: bool, guidance_scale: float, beta: float, sh
             float(getattr(tab, "final_alpha_cumprod", 0.0)), int(acp.numel()), float(acp.double().sum()), float(acp[0]), float(acp[-1]),
             getattr(tab, "solver_order", 0), getattr(tab, "lower_order_final", None), float(eta), bool(classifier_free),
             bool(getattr(tab, "use_karras_sigmas", False)), getattr(tab, "algorithm_type", None),
-            None if sigmas is None else tuple(float(s) for s in sigmas))
+            None if sigmas is None else tuple(float(s) for s in sigmas), int(start_step), bool(masked))
 
 
 def draws_noise(tab, eta: float) -> bool:
@@ -288,6 +319,7 @@ class HipSampler:
     ~900 launches of a few microseconds each and the Python / ctypes launch path, not the GPU, sets the pace."""
 
     _eta_ignored_logged = False               # "eta is ignored by DPM-Solver++" is said once per process, at debug level
+    _unguided_start_logged = False            # so is "an img2img start in the second half of the schedule runs no guided step"
 
     def __init__(self, unet: HipUNet, lgp: Optional[HipLGP] = None, use_graphs: bool = False):
         self.unet, self.lgp, self.use_graphs = unet, lgp, use_graphs
@@ -395,13 +427,36 @@ class HipSampler:
                guidance_scale: float = 7.5, beta: float = 1.6,
                callback: Optional[Callable[[int, int, torch.Tensor], None]] = None,
                tables=None, graphs: Optional[bool] = None, eta: float = 0.0, generator=None,
-               classifier_free: bool = True) -> torch.Tensor:
+               classifier_free: bool = True, init_latents: Optional[torch.Tensor] = None, start_step: int = 0,
+               mask: Optional[torch.Tensor] = None) -> torch.Tensor:
         """eta, generator: DDIM's stochastic step (DDIMTables.coeffs_eta, draw_noise); a generator list holds one per sample.
         DPM-Solver++ ignores eta; its "sde-dpmsolver++" tables draw from `generator` in the same way, once per step.
-        classifier_free=False: no CFG - the context prepared on the UNet holds the S cond rows - and no LGP guidance."""
+        classifier_free=False: no CFG - the context prepared on the UNet holds the S cond rows - and no LGP guidance.
+        init_latents (fp32 [S,4,h,w]), start_step: img2img.  latents0 is then the noise draw eps, the trajectory starts at
+        a*init + s*eps with (a, s) = tab.level(start_step) and runs the entries start_step .. T-1 of the full-length schedule
+        (the DPM-Solver++ history starts empty: the first executed step is first order).  eps is the LGP's noise argument, and
+        which steps are guided is still decided by the absolute entry i against the full T.  last_aux has one entry per executed
+        step and callback(i, t, x) counts i from 0 over them.
+        mask (fp32 [1 or S,1,h,w], 1 = repaint, 0 = keep; needs init_latents): every executed step i ends - after the scheduler
+        step and the guidance update - with x = m*x + (1 - m)*(a*init + s*eps) at tab.level(i + 1), the same eps every step; the
+        last blend puts back the clean init.  The mask plays no part in the LGP loss."""
         dev = self.unet.dev
         tab = tables or DDIMTables.make(num_inference_steps)
         eta = check_eta(eta)
+        T = len(tab.timesteps)
+        start_step = int(start_step)
+        if mask is not None and init_latents is None:
+            raise ValueError("`mask` blends the trajectory with a re-noised original: pass `init_latents` with it")
+        if init_latents is None and start_step != 0:
+            raise ValueError(f"start_step = {start_step} needs `init_latents`: a trajectory from pure noise starts at entry 0")
+        if not 0 <= start_step < T:
+            raise ValueError(f"start_step has to be in [0, {T - 1}] for {T} inference steps but is {start_step}")
+        if init_latents is not None and tuple(init_latents.shape) != tuple(latents0.shape):
+            raise ValueError(f"init_latents shape {tuple(init_latents.shape)} differs from the latents' {tuple(latents0.shape)}")
+        if mask is not None and (mask.dim() != 4 or mask.shape[0] not in (1, latents0.shape[0])
+                                 or tuple(mask.shape[1:]) != (1,) + tuple(latents0.shape[2:])):
+            raise ValueError(f"mask shape {tuple(mask.shape)}: expected (1 or {latents0.shape[0]}, 1, {latents0.shape[2]}, "
+                             f"{latents0.shape[3]})")
         if eta > 0.0 and not isinstance(tab, DDIMTables):
             # DPM-Solver++ has no eta (diffusers' prepare_extra_step_kwargs drops the argument for it): no noise is drawn either
             if not HipSampler._eta_ignored_logged:
@@ -418,36 +473,61 @@ class HipSampler:
         if target is not None and tuple(target.shape[-2:]) != tuple(x.shape[-2:]):
             raise ValueError(f"target spatial shape {tuple(target.shape[-2:])} differs from the latents' {tuple(x.shape[-2:])}")
         tgt = None if target is None else target.to(dev, torch.float32).expand_as(x).contiguous()
+        init = m = None
+        if init_latents is not None:
+            init = init_latents.to(dev, torch.float32).contiguous()
+            if mask is not None:
+                m = mask.to(dev, torch.float32).expand(x.shape[0], -1, -1, -1).contiguous()
+            if tgt is not None and self.lgp is not None and not guided_step(start_step, T) and not HipSampler._unguided_start_logged:
+                HipSampler._unguided_start_logged = True
+                logger.debug("start_step = %d of %d lies in the second half of the schedule: no step of this trajectory is guided",
+                             start_step, T)
+            x = ops.latent_renoise(init, noise, *tab.level(start_step))      # scheduler.add_noise; `noise` stays the draw eps
         self.unet.prepare_timesteps(tab.timesteps.tolist())
         self.last_aux = []
         self.reset_history()
         if (self.use_graphs if graphs is None else graphs) and callback is None:
-            x = self._sample_graphed(x, tgt, tab, guidance_scale, beta, eta, generator, classifier_free)
+            x = self._sample_graphed(x, tgt, tab, guidance_scale, beta, eta, generator, classifier_free,
+                                     noise=None if init is None else noise, init=init, mask=m, start=start_step)
         else:
-            for i, t in enumerate(tab.timesteps.tolist()):
+            steps = tab.timesteps.tolist()
+            for n, i in enumerate(range(start_step, T)):
                 x, _, aux = self.step(x, noise, tgt, tab, i, guidance_scale, beta, eta=eta, generator=generator,
                                       classifier_free=classifier_free)
+                if m is not None:
+                    ops.latent_renoise(init, noise, *tab.level(i + 1), x=x, mask=m)
                 self.last_aux.append(aux)
                 if callback is not None:
-                    callback(i, t, x)
+                    callback(n, steps[i], x)
         self.last_latents = x
         return x
 
     # ------------------------------------------------------------------------------------------ hipGraph replay
     def _sample_graphed(self, x: torch.Tensor, tgt: Optional[torch.Tensor], tab, guidance_scale: float, beta: float,
-                        eta: float = 0.0, generator=None, classifier_free: bool = True):
+                        eta: float = 0.0, generator=None, classifier_free: bool = True, noise: Optional[torch.Tensor] = None,
+                        init: Optional[torch.Tensor] = None, mask: Optional[torch.Tensor] = None, start: int = 0):
         """Captures (first call for a given schedule / shape) and replays one hipGraph per step.  Every launch of a
         step goes to torch's current stream, which is the capturing stream inside ``torch.cuda.graph``; nothing on the
         step path allocates outside torch's (graph-private) pool or synchronises with the host.
         Noised steps (draws_noise: eta > 0, or the stochastic DPM-Solver++): the set owns a static [T, S, 4, h, w] noise buffer,
         each captured step reads its slice; all T draws of a trajectory are made here, once, in step order (draw_noise) -
         before the warm-up pass of a new set, which reads the buffer too and so consumes no generator state - and copied in
-        before the first replay."""
+        before the first replay.
+        img2img (init given: x is the start a*init + s*eps already, `noise` the draw eps, `start` the first entry): only the
+        executed steps start .. T-1 are captured and only their noise is drawn; with a mask each captured step ends with the blend,
+        which reads the set's static `init` and `mask` buffers - refilled before each replay like `ts` - and `ns`, which holds eps."""
         T = len(tab.timesteps)
         inj = self.unet.inject
-        key = graph_key(tab, x.shape, tgt is None, guidance_scale, beta, self.share_cfg_prefix, eta, classifier_free)
-        zall = torch.stack([draw_noise(x.shape, generator, x.device) for _ in range(T)]) if draws_noise(tab, eta) else None
-        step_kw = lambda zs, i: dict(eta=eta, z=None if zs is None else zs[i], classifier_free=classifier_free)
+        key = graph_key(tab, x.shape, tgt is None, guidance_scale, beta, self.share_cfg_prefix, eta, classifier_free, start,
+                        mask is not None)
+        if noise is None:
+            noise = x                                             # a trajectory from pure noise: modules/pipeline.py:75
+        zall = torch.stack([draw_noise(x.shape, generator, x.device) for _ in range(start, T)]) if draws_noise(tab, eta) else None
+        step_kw = lambda zs, i: dict(eta=eta, z=None if zs is None else zs[i - start], classifier_free=classifier_free)
+
+        def blend(xn, ent_init, ent_mask, ns, i):
+            if ent_mask is not None:
+                ops.latent_renoise(ent_init, ns, *tab.level(i + 1), x=xn, mask=ent_mask)
         # What a captured step points at besides the static latents: the text context's K / V (prepare_context builds a
         # NEW dict per prompt) and the injector's per-image K / V (set_state / set_res_samples build a new dict per sketch)
         # and scale.  The entry keeps STRONG references to those objects and is valid only while the pipeline still holds
@@ -468,18 +548,23 @@ class HipSampler:
             ts = None if tgt is None else torch.empty_like(tgt)
             x0b = torch.zeros_like(x)
             zs = None if zall is None else zall.clone()
+            ins = None if mask is None else torch.empty_like(init)
+            ms = None if mask is None else torch.empty_like(mask)
             # one eager pass first: the per-timestep bias vectors and every lazily built per-image buffer must exist before
             # a capture.  The split-K workspace of the captured launches is the set's own (allocated above, outside the
             # capture); scratch buffers first touched inside the capture come from the set's private pool.
-            xs.copy_(x); ns.copy_(x)
+            xs.copy_(x); ns.copy_(noise)
             if ts is not None:
                 ts.copy_(tgt)
+            if ms is not None:
+                ins.copy_(init); ms.copy_(mask)
             saved = None if self.lgp is None else [[r.clone() for r in self.lgp.running_mean], [r.clone() for r in self.lgp.running_var],
                                                    tuple(self.lgp.num_batches_tracked)]
             self._x0_before, self._seen = x0b, 0
             w = xs.clone()
-            for i in range(T):
+            for i in range(start, T):
                 w, _, _ = self.step(w, ns, ts, tab, i, guidance_scale, beta, **step_kw(zs, i))
+                blend(w, ins, ms, ns, i)
             if saved is not None:       # the warm-up pass is not part of the trajectory: undo its BatchNorm side effects
                 for l in range(4):
                     self.lgp.running_mean[l].copy_(saved[0][l]); self.lgp.running_var[l].copy_(saved[1][l])
@@ -488,21 +573,24 @@ class HipSampler:
             pool = torch.cuda.graph_pool_handle()
             graphs, auxs = [], []
             self._x0_before, self._seen = x0b, 0
-            for i in range(T):
+            for i in range(start, T):
                 g = torch.cuda.CUDAGraph()
                 with torch.cuda.graph(g, pool=pool), ops.private_buffers(owner):
                     xn, _, aux = self.step(xs, ns, ts, tab, i, guidance_scale, beta, **step_kw(zs, i))
+                    blend(xn, ins, ms, ns, i)
                     xs.copy_(xn)
                 graphs.append(g)
                 auxs.append(aux)
             if saved is not None:       # captures do not execute, but keep the Python-side counters where they were
                 self.lgp.num_batches_tracked = list(saved[2])
-            ent = self._graphs[key] = dict(graphs=graphs, auxs=auxs, xs=xs, ns=ns, ts=ts, x0b=x0b, zs=zs, owner=owner,
+            ent = self._graphs[key] = dict(graphs=graphs, auxs=auxs, xs=xs, ns=ns, ts=ts, x0b=x0b, zs=zs, init=ins, mask=ms, owner=owner,
                                            ctx=self.unet.ctx, inject=inj, per_image=None if inj is None else inj.per_image,
                                            scale=None if inj is None else inj.scale)
-        ent["xs"].copy_(x); ent["ns"].copy_(x)
+        ent["xs"].copy_(x); ent["ns"].copy_(noise)
         if tgt is not None:
             ent["ts"].copy_(tgt)
+        if mask is not None:
+            ent["init"].copy_(init); ent["mask"].copy_(mask)
         ent["x0b"].zero_()
         if zall is not None:
             ent["zs"].copy_(zall)
