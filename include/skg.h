@@ -452,7 +452,7 @@ int skg_lgp_mse_seed(const void* out, int ldo, const float* target, void* dOut, 
 
 /* ---- LGP training (trainer.py:208-252: forward taps -> LGP -> MSE -> backward with weight gradients -> optimizer) --
  * The reference trains with accelerate fp16 autocast + bitsandbytes AdamW8bit; here: fp16 compute with a static loss
- * scale, fp32 master weights, plain AdamW.  Weight gradients are GEMMs on transposed operands (skg_transpose_f16 +
+ * scale, fp32 master weights, plain AdamW (8-bit moments: skg_adamw8_step below).  Weight gradients are GEMMs on transposed operands (skg_transpose_f16 +
  * skg_gemm_f16 with SKG_EPI_OUT_F32); these are the remaining pieces. */
 /* out[c] = scale * sum_m X[m][c]  (bias gradients).  scratch: skg_colsum_scratch_floats(C) floats. */
 size_t skg_colsum_scratch_floats(int C);
@@ -485,6 +485,25 @@ int skg_nonfinite_flag(const float* x, size_t n, float* flag, int reset, void* s
 int skg_adamw_step_guarded(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, void* param_f16, size_t n,
                            float lr, float beta1, float beta2, float eps, float weight_decay, int step,
                            float inv_grad_scale, const float* skip_flag, void* stream);
+
+/* ---- 8-bit AdamW state (sketch2img_amd/flat_adamw.py state_bits = 8; the reference's bitsandbytes AdamW8bit, restated from
+ * Dettmers et al., "8-bit Optimizers via Block-wise Quantization": DESIGN.md section 15) -----------------
+ * One row of the block table: `len` <= 2048 consecutive elements of ONE tensor, starting `off` elements into param / grad /
+ * param_f16 and `state_off` elements into the state arrays - state1 / state2 when is8 != 0, exp_avg32 / exp_avg_sq32 when
+ * is8 == 0 (a tensor below min_8bit_size keeps fp32 moments).  off and state_off are multiples of 8. */
+typedef struct SkgAdamw8Row {
+  long long off, len, state_off, is8;
+} SkgAdamw8Row;
+/* One AdamW step (skg_adamw_step's arithmetic on fp32 values) over `nrows` table rows in one launch.  8-bit rows: exp_avg =
+ * qmap1[state1] * absmax1[row], exp_avg_sq = qmap2[state2] * absmax2[row] are dequantised, updated, param / param_f16
+ * (optional) written from the fresh fp32 moments, then absmax := max |.| over the row and code := #{ j : mid[j] < x / absmax }
+ * (the zero code where absmax == 0).  qtab (device, 1024 floats): qmap1[256], its thresholds mid1[j] = 0.5f * (q[j] + q[j + 1])
+ * in [0, 255) and one unused float, qmap2[256], mid2 likewise.  absmax1 / absmax2: one float per table row.  skip (optional,
+ * device): non-zero -> nothing is touched (skg_adamw_step_guarded's flag).  nrows == 0: nothing to do. */
+int skg_adamw8_step(float* param, const float* grad, void* param_f16, unsigned char* state1, unsigned char* state2,
+                    float* absmax1, float* absmax2, float* exp_avg32, float* exp_avg_sq32, const SkgAdamw8Row* rows, int nrows,
+                    const float* qtab, float lr, float beta1, float beta2, float eps, float weight_decay, int step,
+                    float inv_grad_scale, const float* skip, void* stream);
 
 /* ---- sampler elementwise -------------------------------------------------------------------------
  * CFG combine + DDIM step (eta = 0) on float NCHW latents:

@@ -30,7 +30,8 @@ LIB_PATH = os.environ.get("SKG_LIB") or os.path.join(_HERE, "libskg.so")
 # that lacks it fails the export check below): skg_cfg_ddim_eta_step, the DDIM step with the eta > 0 noise term;
 # skg_nonfinite_flag and skg_adamw_step_guarded, the dynamic loss scale's verdict and its guarded optimizer step;
 # skg_cfg_dpmpp2m_sde_step, the DPM-Solver++ 2M step with the noise term of algorithm_type "sde-dpmsolver++";
-# skg_latent_renoise, the img2img start a*init + s*noise and the masked-repaint blend
+# skg_latent_renoise, the img2img start a*init + s*noise and the masked-repaint blend; skg_adamw8_step, AdamW on block-wise
+# quantised 8-bit moments (flat_adamw.FlatAdamW state_bits = 8)
 ABI_VERSION = 6
 
 # spec letters: p = device/host pointer, i = int, f = float, u = unsigned, z = size_t (return only)
@@ -117,6 +118,8 @@ SIGNATURES = {
     "skg_adamw_step_guarded": ("i", "pppppzfffffifpp"),
     # img2img start / masked repaint (sampler.py init_latents, mask): additive entry point, same ABI version
     "skg_latent_renoise": ("i", "pppipiiffp"),
+    # 8-bit AdamW state (flat_adamw.py state_bits = 8): additive entry point, same ABI version
+    "skg_adamw8_step": ("i", "ppppppppppipfffffifpp"),
 }
 
 _CT = {"p": ctypes.c_void_p, "i": ctypes.c_int, "f": ctypes.c_float, "u": ctypes.c_uint,

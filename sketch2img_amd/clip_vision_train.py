@@ -53,7 +53,9 @@ def flat_order(cfg: CLIPVisionConfig):
 class HipClipTowerTrainer(FlatAdamW):
     def __init__(self, cfg: CLIPVisionConfig, state_dict: Dict[str, torch.Tensor], device="cuda", lr: float = 2e-4,
                  betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 1e-2, warmup_steps: int = 150,
-                 total_steps: int = 10000, num_cycles: int = 1, seam_scale: float = SEAM_SCALE):
+                 total_steps: int = 10000, num_cycles: int = 1, seam_scale: float = SEAM_SCALE, state_bits: int = 32,
+                 min_8bit_size: int = 4096):
+        # state_bits / min_8bit_size: FlatAdamW's (8: block-wise quantised m / v, the reference's AdamW8bit)
         self.cfg = cfg
         self.seam_scale = float(seam_scale)
         assert math.frexp(self.seam_scale)[0] == 0.5, "the seam scale must be a power of two"
@@ -62,7 +64,7 @@ class HipClipTowerTrainer(FlatAdamW):
         shapes = clip_vision_param_shapes(cfg)
         super().__init__([(k, shapes[k]) for k in flat_order(cfg)], strip_prefix(state_dict), device, lr, betas, eps, weight_decay,
                          lambda s: cosine_with_restarts(s, warmup_steps, total_steps, num_cycles),
-                         LOSS_SCALE * self.seam_scale, frozen=_FROZEN)
+                         LOSS_SCALE * self.seam_scale, frozen=_FROZEN, state_bits=state_bits, min_8bit_size=min_8bit_size)
         # the fused views: q, k, v of a layer are adjacent and unpadded (D * D and D are multiples of 8)
         self.fused: Dict[str, Tuple[int, torch.Size]] = {}
         for l in range(cfg.num_hidden_layers):

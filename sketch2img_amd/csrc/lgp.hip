@@ -600,26 +600,198 @@ __global__ __launch_bounds__(256) void mse_train_kernel(const half_t* __restrict
   if (threadIdx.x == 0) loss_part[s] = acc / n;       // the caller sums the S partials (fixed order)
 }
 
-// AdamW (decoupled weight decay), fp32 master weights + fp16 working copy; g is the loss-scaled gradient.
+// The hyper-parameters of one AdamW step as the kernels take them (bc1 / bc2: the bias corrections 1 - beta^step).
+struct AdamwArgs {
+  float lr, b1, b2, eps, wd, bc1, bc2, inv_scale;
+};
+
+// One element of AdamW (decoupled weight decay): m, v in -> m', v' out, returns the new master weight.  The body of adamw_kernel
+// and of adamw8_kernel: every multiply-add that is fused is written as an fma and nothing else may be contracted, so the rounding
+// does not depend on the kernel the compiler inlines it into (the five fused forms are the ones adamw_kernel always had).
+__device__ __forceinline__ float adamw_update(float pi, float g, float& m, float& v, const AdamwArgs& a) {
+#pragma clang fp contract(off)
+  const float gi = g * a.inv_scale;
+  const float mi = __builtin_fmaf(a.b1, m, (1.f - a.b1) * gi);
+  const float vi = __builtin_fmaf(a.b2, v, gi * ((1.f - a.b2) * gi));
+  m = mi;
+  v = vi;
+  const float decay = __builtin_fmaf(-a.lr, a.wd, 1.f);
+  const float upd = (a.lr * (mi / a.bc1)) / (sqrtf(vi / a.bc2) + a.eps);
+  return __builtin_fmaf(decay, pi, -upd);
+}
+
+// AdamW, fp32 master weights + fp16 working copy; g is the loss-scaled gradient.
 // GUARDED: *skip (the loss scaler's verdict, written earlier on the stream by nonfinite_flag_kernel) != 0 -> nothing is touched;
 // otherwise the same body, so the two instantiations contract alike and agree to the bit.
 template <bool GUARDED>
 __global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, const float* __restrict__ g,
                                                     float* __restrict__ m, float* __restrict__ v,
-                                                    half_t* __restrict__ p16, size_t n, float lr, float b1, float b2,
-                                                    float eps, float wd, float bc1, float bc2, float inv_scale,
+                                                    half_t* __restrict__ p16, size_t n, const AdamwArgs a,
                                                     const float* __restrict__ skip) {
   if (GUARDED && *skip != 0.f) return;
   for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) {
-    const float gi = g[i] * inv_scale;
-    const float mi = b1 * m[i] + (1.f - b1) * gi;
-    const float vi = b2 * v[i] + (1.f - b2) * gi * gi;
+    float mi = m[i], vi = v[i];
+    const float w = adamw_update(p[i], g[i], mi, vi, a);
     m[i] = mi;
     v[i] = vi;
-    float w = p[i] * (1.f - lr * wd);
-    w -= lr * (mi / bc1) / (sqrtf(vi / bc2) + eps);
     p[i] = w;
     if (p16) p16[i] = (half_t)w;
+  }
+}
+
+// ---- 8-bit AdamW state (block-wise dynamic quantisation: DESIGN.md section 15) ---------------------------------------
+// qtab: 4 x 256 floats - the signed map (m), its 255 thresholds mid[j] = 0.5f * (q[j] + q[j + 1]) (+ one unused slot), the
+// unsigned map (v), its thresholds; built once on the host, copied to LDS as they are.
+// A quantisation block is at most 2048 elements = 256 lanes x 8.
+constexpr int Q8_ZERO1 = 127, Q8_ZERO2 = 0;
+
+// code = #{ j : mid[j] < x }, mid ascending, 255 entries: 8 halvings, every index read lies in [0, 254] whatever x is (NaN: 0)
+__device__ __forceinline__ unsigned q8_code(const float* mid, float x) {
+  unsigned lo = 0;
+#pragma unroll
+  for (unsigned s = 128; s > 0; s >>= 1)
+    if (mid[lo + s - 1] < x) lo += s;
+  return lo;
+}
+
+__device__ __forceinline__ float q8_div(float s, float a) {
+#pragma clang fp contract(off)
+  return s / a;                          // correctly rounded (hipcc's default for fp32 division)
+}
+
+// One 256-thread workgroup per row of the block table (grid-strided), 8 consecutive elements per lane.  A row is
+// (offset into p / g / p16, length <= 2048, offset into the state arrays, 8-bit or fp32), four int64: at most 2048 elements of ONE
+// tensor, so the lanes beyond `len` touch nothing - not the padding between tensors either.  8-bit rows: dequantise m, v
+// (q[code] * absmax), adamw_update, write p / p16 from the fresh fp32 m', v', then the block's new absmax (wave shuffle + a 4-entry
+// LDS exchange, double-buffered over the rows so that one barrier per row suffices) and the new codes.  fp32 rows (tensors below
+// min_8bit_size): adamw_kernel's arithmetic on the compact m32 / v32 arrays.  All stores are vector stores from the lanes.
+__global__ __launch_bounds__(256) void adamw8_kernel(float* __restrict__ p, const float* __restrict__ g,
+                                                     half_t* __restrict__ p16, unsigned char* __restrict__ c1,
+                                                     unsigned char* __restrict__ c2, float* __restrict__ am1,
+                                                     float* __restrict__ am2, float* __restrict__ m32,
+                                                     float* __restrict__ v32, const long long* __restrict__ rows, int nrows,
+                                                     const float* __restrict__ qtab, const AdamwArgs a,
+                                                     const float* __restrict__ skip) {
+  __shared__ float sq[1024];
+  __shared__ float red[2][2][4];
+  if (skip && *skip != 0.f) return;
+  for (int i = threadIdx.x; i < 1024; i += 256) sq[i] = qtab[i];
+  __syncthreads();
+  const float* q1 = sq;
+  const float* mid1 = sq + 256;
+  const float* q2 = sq + 512;
+  const float* mid2 = sq + 768;
+  const int lane8 = threadIdx.x * 8, wave = threadIdx.x >> 6;
+  int par = 0;
+  for (int r = blockIdx.x; r < nrows; r += gridDim.x) {
+    const long long off = rows[4 * (size_t)r] + lane8, len = rows[4 * (size_t)r + 1];
+    const long long soff = rows[4 * (size_t)r + 2] + lane8;
+    const bool is8 = rows[4 * (size_t)r + 3] != 0;
+    const long long left = len - lane8;
+    const int nv = left >= 8 ? 8 : (left > 0 ? (int)left : 0);      // this lane's elements: 8, or the row's short tail, or none
+    const bool full = nv == 8;
+    float gi[8], pi[8], mi[8], vi[8];
+    unsigned char k1[8], k2[8];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) gi[e] = pi[e] = mi[e] = vi[e] = 0.f, k1[e] = k2[e] = 0;
+    if (full) {
+      const float4 g0 = *reinterpret_cast<const float4*>(g + off), g1 = *reinterpret_cast<const float4*>(g + off + 4);
+      const float4 p0 = *reinterpret_cast<const float4*>(p + off), p1 = *reinterpret_cast<const float4*>(p + off + 4);
+      gi[0] = g0.x, gi[1] = g0.y, gi[2] = g0.z, gi[3] = g0.w, gi[4] = g1.x, gi[5] = g1.y, gi[6] = g1.z, gi[7] = g1.w;
+      pi[0] = p0.x, pi[1] = p0.y, pi[2] = p0.z, pi[3] = p0.w, pi[4] = p1.x, pi[5] = p1.y, pi[6] = p1.z, pi[7] = p1.w;
+      if (is8) {
+        const uint2 u1 = *reinterpret_cast<const uint2*>(c1 + soff), u2 = *reinterpret_cast<const uint2*>(c2 + soff);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          k1[e] = (unsigned char)(u1.x >> (8 * e)), k1[4 + e] = (unsigned char)(u1.y >> (8 * e));
+          k2[e] = (unsigned char)(u2.x >> (8 * e)), k2[4 + e] = (unsigned char)(u2.y >> (8 * e));
+        }
+      } else {
+        const float4 m0 = *reinterpret_cast<const float4*>(m32 + soff), m1 = *reinterpret_cast<const float4*>(m32 + soff + 4);
+        const float4 v0 = *reinterpret_cast<const float4*>(v32 + soff), v1 = *reinterpret_cast<const float4*>(v32 + soff + 4);
+        mi[0] = m0.x, mi[1] = m0.y, mi[2] = m0.z, mi[3] = m0.w, mi[4] = m1.x, mi[5] = m1.y, mi[6] = m1.z, mi[7] = m1.w;
+        vi[0] = v0.x, vi[1] = v0.y, vi[2] = v0.z, vi[3] = v0.w, vi[4] = v1.x, vi[5] = v1.y, vi[6] = v1.z, vi[7] = v1.w;
+      }
+    } else {
+#pragma unroll
+      for (int e = 0; e < 8; ++e)
+        if (e < nv) {
+          gi[e] = g[off + e];
+          pi[e] = p[off + e];
+          if (is8) k1[e] = c1[soff + e], k2[e] = c2[soff + e];
+          else mi[e] = m32[soff + e], vi[e] = v32[soff + e];
+        }
+    }
+    if (is8) {
+      const float a1 = am1[r], a2 = am2[r];
+#pragma unroll
+      for (int e = 0; e < 8; ++e) mi[e] = q1[k1[e]] * a1, vi[e] = q2[k2[e]] * a2;
+    }
+    float w[8];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) w[e] = adamw_update(pi[e], gi[e], mi[e], vi[e], a);
+    if (full) {
+      *reinterpret_cast<float4*>(p + off) = make_float4(w[0], w[1], w[2], w[3]);
+      *reinterpret_cast<float4*>(p + off + 4) = make_float4(w[4], w[5], w[6], w[7]);
+      if (p16) {
+        half8_t h;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) h[e] = (half_t)w[e];
+        st_half8(p16 + off, h);
+      }
+    } else {
+#pragma unroll
+      for (int e = 0; e < 8; ++e)
+        if (e < nv) {
+          p[off + e] = w[e];
+          if (p16) p16[off + e] = (half_t)w[e];
+        }
+    }
+    if (!is8) {                          // (block-uniform: the barrier below is reached by all lanes or by none)
+      if (full) {
+        *reinterpret_cast<float4*>(m32 + soff) = make_float4(mi[0], mi[1], mi[2], mi[3]);
+        *reinterpret_cast<float4*>(m32 + soff + 4) = make_float4(mi[4], mi[5], mi[6], mi[7]);
+        *reinterpret_cast<float4*>(v32 + soff) = make_float4(vi[0], vi[1], vi[2], vi[3]);
+        *reinterpret_cast<float4*>(v32 + soff + 4) = make_float4(vi[4], vi[5], vi[6], vi[7]);
+      } else {
+#pragma unroll
+        for (int e = 0; e < 8; ++e)
+          if (e < nv) m32[soff + e] = mi[e], v32[soff + e] = vi[e];
+      }
+      continue;
+    }
+    // the block's new absmax, exact: lanes without elements contribute 0 (the update of an all-zero element was discarded)
+    float x1 = 0.f, x2 = 0.f;
+#pragma unroll
+    for (int e = 0; e < 8; ++e)
+      if (e < nv) x1 = fmaxf(x1, fabsf(mi[e])), x2 = fmaxf(x2, fabsf(vi[e]));
+    x1 = wave_max(x1);
+    x2 = wave_max(x2);
+    if ((threadIdx.x & 63) == 0) red[par][0][wave] = x1, red[par][1][wave] = x2;
+    __syncthreads();
+    const float n1 = fmaxf(fmaxf(red[par][0][0], red[par][0][1]), fmaxf(red[par][0][2], red[par][0][3]));
+    const float n2 = fmaxf(fmaxf(red[par][1][0], red[par][1][1]), fmaxf(red[par][1][2], red[par][1][3]));
+    if (threadIdx.x == 0) am1[r] = n1, am2[r] = n2;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      k1[e] = (unsigned char)(n1 == 0.f ? Q8_ZERO1 : q8_code(mid1, q8_div(mi[e], n1)));
+      k2[e] = (unsigned char)(n2 == 0.f ? Q8_ZERO2 : q8_code(mid2, q8_div(vi[e], n2)));
+    }
+    if (full) {
+      uint2 u1 = make_uint2(0, 0), u2 = make_uint2(0, 0);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        u1.x |= (unsigned)k1[e] << (8 * e), u1.y |= (unsigned)k1[4 + e] << (8 * e);
+        u2.x |= (unsigned)k2[e] << (8 * e), u2.y |= (unsigned)k2[4 + e] << (8 * e);
+      }
+      *reinterpret_cast<uint2*>(c1 + soff) = u1;
+      *reinterpret_cast<uint2*>(c2 + soff) = u2;
+    } else {
+#pragma unroll
+      for (int e = 0; e < 8; ++e)
+        if (e < nv) c1[soff + e] = k1[e], c2[soff + e] = k2[e];
+    }
+    par ^= 1;                            // (only where a barrier was passed: two 8-bit rows in a row never share a buffer)
   }
 }
 
@@ -839,7 +1011,7 @@ extern "C" int skg_adamw_step(float* param, const float* grad, float* exp_avg, f
   SKG_REQUIRE(param && grad && exp_avg && exp_avg_sq && n > 0 && step >= 1 && lr >= 0.f);
   const float bc1 = 1.f - powf(beta1, (float)step), bc2 = 1.f - powf(beta2, (float)step);
   hipLaunchKernelGGL(adamw_kernel<false>, dim3(ew_grid(n)), dim3(256), 0, (hipStream_t)stream, param, grad, exp_avg,
-                     exp_avg_sq, (half_t*)param_f16, n, lr, beta1, beta2, eps, weight_decay, bc1, bc2, inv_grad_scale,
+                     exp_avg_sq, (half_t*)param_f16, n, AdamwArgs{lr, beta1, beta2, eps, weight_decay, bc1, bc2, inv_grad_scale},
                      (const float*)nullptr);
   SKG_CHECK_LAUNCH("skg_adamw_step");
   return SKG_OK;
@@ -851,9 +1023,29 @@ extern "C" int skg_adamw_step_guarded(float* param, const float* grad, float* ex
   SKG_REQUIRE(param && grad && exp_avg && exp_avg_sq && skip_flag && n > 0 && step >= 1 && lr >= 0.f);
   const float bc1 = 1.f - powf(beta1, (float)step), bc2 = 1.f - powf(beta2, (float)step);
   hipLaunchKernelGGL(adamw_kernel<true>, dim3(ew_grid(n)), dim3(256), 0, (hipStream_t)stream, param, grad, exp_avg,
-                     exp_avg_sq, (half_t*)param_f16, n, lr, beta1, beta2, eps, weight_decay, bc1, bc2, inv_grad_scale,
+                     exp_avg_sq, (half_t*)param_f16, n, AdamwArgs{lr, beta1, beta2, eps, weight_decay, bc1, bc2, inv_grad_scale},
                      skip_flag);
   SKG_CHECK_LAUNCH("skg_adamw_step_guarded");
+  return SKG_OK;
+}
+
+extern "C" int skg_adamw8_step(float* param, const float* grad, void* param_f16, unsigned char* state1, unsigned char* state2,
+                               float* absmax1, float* absmax2, float* exp_avg32, float* exp_avg_sq32, const SkgAdamw8Row* rows,
+                               int nrows, const float* qtab, float lr, float beta1, float beta2, float eps, float weight_decay,
+                               int step, float inv_grad_scale, const float* skip, void* stream) {
+  SKG_REQUIRE(param && grad && state1 && state2 && absmax1 && absmax2 && exp_avg32 && exp_avg_sq32 && rows && qtab);
+  SKG_REQUIRE(nrows >= 0 && step >= 1 && lr >= 0.f);
+  SKG_REQUIRE(skg_aligned(param, 16) && skg_aligned(grad, 16) && skg_aligned(param_f16, 16) && skg_aligned(state1, 8) &&
+              skg_aligned(state2, 8) && skg_aligned(exp_avg32, 16) && skg_aligned(exp_avg_sq32, 16) && skg_aligned(rows, 8));
+  if (nrows == 0) return SKG_OK;
+  static_assert(sizeof(SkgAdamw8Row) == 4 * sizeof(long long), "a table row is four int64");
+  const float bc1 = 1.f - powf(beta1, (float)step), bc2 = 1.f - powf(beta2, (float)step);
+  // 2048 workgroups: more than are resident at once (the chip takes them in as others finish; a grid of exactly the resident ones
+  // measured the same), each walks its share of the rows
+  hipLaunchKernelGGL(adamw8_kernel, dim3(nrows < 2048 ? nrows : 2048), dim3(256), 0, (hipStream_t)stream, param, grad,
+                     (half_t*)param_f16, state1, state2, absmax1, absmax2, exp_avg32, exp_avg_sq32, (const long long*)rows,
+                     nrows, qtab, AdamwArgs{lr, beta1, beta2, eps, weight_decay, bc1, bc2, inv_grad_scale}, skip);
+  SKG_CHECK_LAUNCH("skg_adamw8_step");
   return SKG_OK;
 }
 

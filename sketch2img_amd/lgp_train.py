@@ -35,10 +35,12 @@ TRAINABLE = [f"layers.{i}.{n}" for i in (0, 2, 3, 5, 6, 8, 9, 11, 12) for n in (
 class HipLGPTrainer(FlatAdamW):
     def __init__(self, state_dict: Dict[str, torch.Tensor], tap_channels: Sequence[int], device="cuda",
                  lr: float = 2e-4, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 1e-2,
-                 warmup_steps: int = 150):
+                 warmup_steps: int = 150, state_bits: int = 32, min_8bit_size: int = 4096):
+        # state_bits / min_8bit_size: FlatAdamW's (8: block-wise quantised m / v, the reference's AdamW8bit)
         # the master vector is in the reference's state_dict order (weights, biases of the 5 Linear and 4 BN)
         super().__init__([(k, state_dict[k].shape) for k in TRAINABLE], state_dict, device, lr, betas, eps, weight_decay,
-                         lambda s: constant_with_warmup(s, warmup_steps), LOSS_SCALE)
+                         lambda s: constant_with_warmup(s, warmup_steps), LOSS_SCALE, state_bits=state_bits,
+                         min_8bit_size=min_8bit_size)
         dev = self.dev
         self.tap_channels = list(tap_channels)
         self.E = sum(tap_channels)

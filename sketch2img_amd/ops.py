@@ -916,6 +916,25 @@ def adamw_step_guarded(param, grad, exp_avg, exp_avg_sq, param_f16, lr, beta1, b
                                      eps, weight_decay, step, inv_grad_scale, _p(skip_flag), _stream()), "skg_adamw_step_guarded")
 
 
+def adamw8_step(param, grad, param_f16, state1, state2, absmax1, absmax2, exp_avg32, exp_avg_sq32, rows, qtab, lr, beta1, beta2,
+                eps, weight_decay, step: int, inv_grad_scale: float = 1.0, skip_flag=None):
+    """One AdamW step on block-wise quantised 8-bit moments (skg_adamw8_step; flat_adamw.FlatAdamW builds every operand): rows is
+    the int64 [R, 4] block table (offset, length <= 2048, state offset, 8-bit or fp32), state1 / state2 the uint8 codes, absmax1 /
+    absmax2 one float per row, exp_avg32 / exp_avg_sq32 the compact fp32 moments of the small tensors, qtab the 4 x 256 maps and
+    thresholds.  skip_flag (nonfinite_flag's float): non-zero -> nothing is touched."""
+    n, R = param.numel(), rows.shape[0]
+    assert param.dtype == grad.dtype == absmax1.dtype == absmax2.dtype == exp_avg32.dtype == exp_avg_sq32.dtype == torch.float32
+    assert qtab.dtype == torch.float32 and qtab.numel() == 1024 and qtab.is_contiguous() and grad.numel() == n
+    assert state1.dtype == state2.dtype == torch.uint8 and state1.numel() == state2.numel()
+    assert rows.dtype == torch.int64 and rows.dim() == 2 and rows.shape[1] == 4 and rows.is_contiguous()
+    assert absmax1.numel() == absmax2.numel() == max(R, 1) and exp_avg32.numel() == exp_avg_sq32.numel()
+    assert param_f16 is None or (param_f16.dtype == torch.float16 and param_f16.numel() == n)
+    assert skip_flag is None or (skip_flag.dtype == torch.float32 and skip_flag.numel() == 1)
+    check(lib.skg_adamw8_step(_p(param), _p(grad), _p(param_f16), _p(state1), _p(state2), _p(absmax1), _p(absmax2), _p(exp_avg32),
+                              _p(exp_avg_sq32), _p(rows), R, _p(qtab), lr, beta1, beta2, eps, weight_decay, step, inv_grad_scale,
+                              _p(skip_flag), _stream()), "skg_adamw8_step")
+
+
 def nonfinite_flag(x, flag, reset: bool = False):
     """flag (one fp32 element on x's device) = 1.0 if the dense fp32 tensor x holds an inf or a NaN, else untouched; reset zeroes
     it first.  Queued on the current stream: nothing waits."""

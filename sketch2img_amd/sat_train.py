@@ -92,10 +92,13 @@ def add_noise(latents: torch.Tensor, noise: torch.Tensor, timesteps: Sequence[in
 class HipSatTrainer(FlatAdamW):
     def __init__(self, cfg: UNetConfig, state_dict: Dict[str, torch.Tensor], device="cuda", lr: float = 2e-4,
                  betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 1e-2, warmup_steps: int = 150,
-                 total_steps: int = 10000, num_cycles: int = 1, scale: float = 1.0):
+                 total_steps: int = 10000, num_cycles: int = 1, scale: float = 1.0, state_bits: int = 32,
+                 min_8bit_size: int = 4096):
+        # state_bits / min_8bit_size: FlatAdamW's (8: block-wise quantised m / v, the reference's AdamW8bit)
         # the master vector is in the checkpoint's key order: state_dict() is the reference's sketch_attn_model.pt
         super().__init__(list(param_shapes(cfg).items()), state_dict, device, lr, betas, eps, weight_decay,
-                         lambda s: cosine_with_restarts(s, warmup_steps, total_steps, num_cycles), LOSS_SCALE)
+                         lambda s: cosine_with_restarts(s, warmup_steps, total_steps, num_cycles), LOSS_SCALE,
+                         state_bits=state_bits, min_8bit_size=min_8bit_size)
         self.cfg = cfg
         self.injector = HipClipInjectorTrain(cfg, self.w16, self.grad_view, self.dev)
         self.injector.set_scale(scale)
