@@ -31,7 +31,7 @@ LIB_PATH = os.environ.get("SKG_LIB") or os.path.join(_HERE, "libskg.so")
 # skg_nonfinite_flag and skg_adamw_step_guarded, the dynamic loss scale's verdict and its guarded optimizer step;
 # skg_cfg_dpmpp2m_sde_step, the DPM-Solver++ 2M step with the noise term of algorithm_type "sde-dpmsolver++";
 # skg_latent_renoise, the img2img start a*init + s*noise and the masked-repaint blend; skg_adamw8_step, AdamW on block-wise
-# quantised 8-bit moments (flat_adamw.FlatAdamW state_bits = 8)
+# quantised 8-bit moments (flat_adamw.FlatAdamW state_bits = 8); skg_attn_fwd_variant, which instantiation skg_attn_fwd runs
 ABI_VERSION = 6
 
 # spec letters: p = device/host pointer, i = int, f = float, u = unsigned, z = size_t (return only)
@@ -64,6 +64,7 @@ SIGNATURES = {
     "skg_geglu_fwd": ("i", "pipiiiip"),
     "skg_geglu_bwd": ("i", "pipipiiiip"),
     "skg_attn_fwd": ("i", "pipipipipiiiiiifup"),
+    "skg_attn_fwd_variant": ("i", "iiiiiiup"),
     "skg_attn_bwd_delta": ("i", "pipipiiiip"),
     "skg_attn_bwd_dq": ("i", "pipipipipippppiiiiiiifp"),
     "skg_attn_bwd_dkv": ("i", "pipipipipppipiiiiiiifp"),

@@ -1436,56 +1436,41 @@ __global__ __launch_bounds__(256) void attn_delta_kernel(const half_t* __restric
 // So QT 3 runs d = 40 where the launch has >= 1024 workgroups of 192 queries, d = 64 stays at QT 2 with ONE register prefetch
 // set (152 VGPRs = three waves per SIMD instead of two: + 8...15 %).  SKG_ATTN_VAR: 12 = QT 2 everywhere (round 3's
 // dispatch), 9 / 8 = QT 3 at d = 40 / QT 4 at d = 64 whatever the size, 7 = the two-set form at d = 64 (tools/attn_var_bench.py).
-inline int attn_var();
-template <int KS, int ND, bool VROW>
-static void attn_fwd_launch_qt(AttnParams& p, hipStream_t st) {
-  const int var = attn_var();
-  const long rows = (long)p.heads * p.batch;
-  if constexpr (ND == 3) {
-    if (var == 9 || (var == 0 && skg_cdiv(p.Nq, 192) * rows >= 1024)) {
-      p.nx = skg_cdiv(p.Nq, 192);
-      hipLaunchKernelGGL((attn_fwd_kernel<KS, ND, 3, false, 2 | (3 << 2), VROW>), dim3((unsigned)(p.nx * rows)), dim3(256), 0, st, p);
-      return;
-    }
-  } else if constexpr (VROW) {      // (the transposed-V form of this instantiation spills 5 registers: row-major V only)
-    if (var == 8) {      // (opt-in: + 5 % on the kernel alone at 9 480 tokens, nothing end to end on config 5)
-      p.nx = skg_cdiv(p.Nq, 256);
-      hipLaunchKernelGGL((attn_fwd_kernel<KS, ND, 4, false, 2 | (2 << 2), VROW>), dim3((unsigned)(p.nx * rows)), dim3(256), 0, st, p);
-      return;
-    }
-  }
-  p.nx = skg_cdiv(p.Nq, 128);
-  const dim3 grid((unsigned)(p.nx * rows));
-  if (ND == 4 && var != 7)
-    hipLaunchKernelGGL((attn_fwd_kernel<KS, ND, 2, false, 2 | (3 << 2), VROW>), grid, dim3(256), 0, st, p);
-  else
-    hipLaunchKernelGGL((attn_fwd_kernel<KS, ND, 2, false, 0, VROW>), grid, dim3(256), 0, st, p);
-}
-#define SKG_ATTN_VARIANTS(KS_, ND_, grid2, VROW_) attn_fwd_launch_qt<KS_, ND_, VROW_>(p, st)
-
-// forward: two query tiles per wave (128 queries per workgroup) except at d = 160 (register budget)
-#define SKG_ATTN_FWD_DISPATCH(grid1, grid2, VROW_)                                                                 \
-  switch (p.dh) {                                                                                                  \
-    case 16: hipLaunchKernelGGL((attn_fwd_kernel<1, 1, 2, false, 0, VROW_>), grid2, dim3(256), 0, st, p); break;   \
-    case 32: hipLaunchKernelGGL((attn_fwd_kernel<1, 2, 2, false, 0, VROW_>), grid2, dim3(256), 0, st, p); break;   \
-    case 40: SKG_ATTN_VARIANTS(2, 3, grid2, VROW_); break;                                                         \
-    case 64: SKG_ATTN_VARIANTS(2, 4, grid2, VROW_); break;                                                         \
-    case 80: hipLaunchKernelGGL((attn_fwd_kernel<3, 5, 2, false, 0, VROW_>), grid2, dim3(256), 0, st, p); break;   \
-    case 160: hipLaunchKernelGGL((attn_fwd_kernel<5, 10, 1, false, 0, VROW_>), grid1, dim3(256), 0, st, p); break; \
-    default: return SKG_E_UNSUPPORTED;                                                                             \
-  }
-
-#define SKG_ATTN_FWD_CAUSAL_DISPATCH(grid2)                                                               \
-  switch (p.dh) {                                                                                        \
-    case 16: hipLaunchKernelGGL((attn_fwd_kernel<1, 1, 2, true>), grid2, dim3(256), 0, st, p); break;    \
-    case 32: hipLaunchKernelGGL((attn_fwd_kernel<1, 2, 2, true>), grid2, dim3(256), 0, st, p); break;    \
-    case 64: hipLaunchKernelGGL((attn_fwd_kernel<2, 4, 2, true>), grid2, dim3(256), 0, st, p); break;    \
-    default: return SKG_E_UNSUPPORTED;                                                                   \
-  }
-
 inline int attn_var() {
   static const int v = getenv("SKG_ATTN_VAR") ? atoi(getenv("SKG_ATTN_VAR")) : 0;
   return v;
+}
+inline bool attn_no_short() {
+  static const bool v = getenv("SKG_NO_ATTN_SHORT") != nullptr;        // A/B switch
+  return v;
+}
+
+// The streaming kernel of a plan (below) with QT query tiles per wave: two (128 queries per workgroup) except at d = 160
+// (register budget), three / four at d = 40 / 64 where the plan says so
+template <bool VROW>
+static int attn_fwd_launch_stream(const AttnParams& p, int QT, bool two_sets, dim3 grid, hipStream_t st) {
+  switch (p.dh) {
+    case 16: hipLaunchKernelGGL((attn_fwd_kernel<1, 1, 2, false, 0, VROW>), grid, dim3(256), 0, st, p); break;
+    case 32: hipLaunchKernelGGL((attn_fwd_kernel<1, 2, 2, false, 0, VROW>), grid, dim3(256), 0, st, p); break;
+    case 40:
+      if (QT == 3) hipLaunchKernelGGL((attn_fwd_kernel<2, 3, 3, false, 2 | (3 << 2), VROW>), grid, dim3(256), 0, st, p);
+      else hipLaunchKernelGGL((attn_fwd_kernel<2, 3, 2, false, 0, VROW>), grid, dim3(256), 0, st, p);
+      break;
+    case 64:
+      if constexpr (VROW) {      // (the transposed-V form of this instantiation spills 5 registers: row-major V only)
+        if (QT == 4) {
+          hipLaunchKernelGGL((attn_fwd_kernel<2, 4, 4, false, 2 | (2 << 2), VROW>), grid, dim3(256), 0, st, p);
+          break;
+        }
+      }
+      if (two_sets) hipLaunchKernelGGL((attn_fwd_kernel<2, 4, 2, false, 0, VROW>), grid, dim3(256), 0, st, p);
+      else hipLaunchKernelGGL((attn_fwd_kernel<2, 4, 2, false, 2 | (3 << 2), VROW>), grid, dim3(256), 0, st, p);
+      break;
+    case 80: hipLaunchKernelGGL((attn_fwd_kernel<3, 5, 2, false, 0, VROW>), grid, dim3(256), 0, st, p); break;
+    case 160: hipLaunchKernelGGL((attn_fwd_kernel<5, 10, 1, false, 0, VROW>), grid, dim3(256), 0, st, p); break;
+    default: return SKG_E_UNSUPPORTED;
+  }
+  return SKG_OK;
 }
 
 // kv8: kv_stride % 8 == 0 - only the transposed V^T operand needs it (16-byte loads along the key axis start at b * kv_stride).
@@ -1496,113 +1481,157 @@ inline bool common_ok(int batch, int heads, int Nq, int Nkv, int kv_stride, int 
   return batch > 0 && heads > 0 && Nq > 0 && Nkv > 0 && kv_stride >= Nkv && (!kv8 || kv_stride % 8 == 0) && dh % 8 == 0;
 }
 
+// THE dispatch rule of skg_attn_fwd: which instantiation a call runs and how many queries one workgroup of it covers.  The
+// launcher switches on the plan and skg_attn_fwd_variant reports it, so the two cannot disagree.
+//   code  1000 + QT  attn_fwd_kernel with QT query tiles per wave       2000 + QT  its causal instantiation
+//         3000 + NT  attn_fwd_short_kernel with NT 16-key score tiles   5000 + waves per workgroup: attn_fwd8_kernel (lab builds)
+//         negative   SKG_E_*: what skg_attn_fwd returns for these arguments once its pointers and pitches pass
+//   qpw   queries per workgroup: 64 QT, or the short-key kernel's query chunk
+//   two_sets  d = 64, QT 2: two register prefetch sets (SKG_ATTN_VAR = 7) instead of the shipped one
+struct AttnFwdPlan { int code, qpw; bool two_sets; };
+AttnFwdPlan attn_fwd_plan(int batch, int heads, int Nq, int Nkv, int kv_stride, int dh, unsigned flags) {
+  const bool causal = flags & SKG_ATTN_CAUSAL, vrow = flags & SKG_ATTN_ROWV, resident = flags & SKG_ATTN_RESIDENT_KV;
+  if ((flags & ~(SKG_ATTN_CAUSAL | SKG_ATTN_ROWV | SKG_ATTN_RESIDENT_KV)) || (causal && vrow) || (resident && !vrow) ||
+      !common_ok(batch, heads, Nq, Nkv, kv_stride, dh, !vrow))
+    return {SKG_E_BADARG, 0, false};
+  const long pairs = (long)heads * batch;
+  const bool short_dh = dh == 40 || dh == 64 || dh == 80 || dh == 160;
+  // queries per workgroup of the short-key kernel: ~1024+ workgroups where the launch has them, a multiple of 64
+  long qch = (pairs * Nq / 1024 + 63) / 64 * 64;
+  qch = qch > 512 ? 512 : qch;
+  // short key sequences (the 77 text tokens of every cross-attention): the LDS-resident kernel, HBM-bound; at least 64 queries
+  if (vrow && !causal && kv_stride <= 80 && !attn_no_short() && short_dh) return {3005, (int)(qch < 64 ? 64 : qch), false};
+  // SKG_ATTN_RESIDENT_KV (a hint: cross-attention over a long prompt's 81 ... 240 keys): the same kernel with 10 / 15 score tiles
+  // where K and V of one (row, head) fit the 160 KB of LDS - not d = 160 above 160 keys; everything else runs as without the flag.
+  // One staging pass of up to 240 K / V rows per workgroup: at least 128 queries behind it where the launch has them
+  const int rtiles = kv_stride <= 160 ? 10 : 15;
+  if (resident && kv_stride > 80 && kv_stride <= 240 && !attn_no_short() && short_dh && (dh != 160 || rtiles == 10))
+    return {3000 + rtiles, (int)(qch < 128 ? 128 : qch), false};
+#if defined(SKG_LAB) || defined(SKG_PHASES)
+  // lab / probe builds only: the withdrawn 8-wave formulation (attn_fwd8_kernel) for the self-attention of the 64 x 64 / 32 x 32
+  // levels, on request (SKG_ATTN8 = 1: one 8-wave workgroup per CU, 2: three 4-wave ones; SKG_NO_ATTN8 overrides)
+  static const bool no8 = getenv("SKG_NO_ATTN8") != nullptr || getenv("SKG_ATTN8") == nullptr;
+  static const int form8 = getenv("SKG_ATTN8") ? atoi(getenv("SKG_ATTN8")) : 0;
+  if (vrow && !causal && !no8 && (dh == 40 || dh == 64) && (long)skg_cdiv(Nq, 256) * pairs >= 192)
+    return {form8 == 2 ? 5004 : 5008, form8 == 2 ? 128 : 256, false};
+#endif
+  if (causal) {
+    if (dh == 160) return {SKG_E_BADARG, 0, false};
+    if (dh != 16 && dh != 32 && dh != 64) return {SKG_E_UNSUPPORTED, 0, false};
+    return {2002, 128, false};
+  }
+  const int var = attn_var();
+  switch (dh) {
+    case 16: case 32: case 80: return {1002, 128, false};
+    case 160: return {1001, 64, false};
+    case 40:      // QT 3 where the launch has >= 1024 workgroups of 192 queries (the measurements above attn_var)
+      if (var == 9 || (var == 0 && skg_cdiv(Nq, 192) * pairs >= 1024)) return {1003, 192, false};
+      return {1002, 128, false};
+    case 64:      // QT 4: opt-in, row-major V (+ 5 % on the kernel alone at 9 480 tokens, nothing end to end on config 5)
+      if (vrow && var == 8) return {1004, 256, false};
+      return {1002, 128, var == 7};
+    default: return {SKG_E_UNSUPPORTED, 0, false};
+  }
+}
+
 }  // namespace
+
+extern "C" int skg_attn_fwd_variant(int batch, int heads, int Nq, int Nkv, int kv_stride, int dh, unsigned flags,
+                                    int* queries_per_workgroup) {
+  const AttnFwdPlan plan = attn_fwd_plan(batch, heads, Nq, Nkv, kv_stride, dh, flags);
+  if (plan.code >= 0 && queries_per_workgroup) *queries_per_workgroup = plan.qpw;
+  return plan.code;
+}
 
 // SKG_ATTN_ROWV: V handed over ROW-MAJOR ([batch * kv_stride][ldvt], e.g. the third column block of a fused QKV projection) - the
 // kernel reads its fragments through the LDS transpose read, no V^T copy is needed; SKG_ATTN_CAUSAL: key j <= query i only
 extern "C" int skg_attn_fwd(const void* Q, int ldq, const void* K, int ldk, const void* Vt, int ldvt, void* O,
                             int ldo, float* lse, int batch, int heads, int Nq, int Nkv, int kv_stride, int dh,
                             float scale, unsigned flags, void* stream) {
-  const bool causal = flags & SKG_ATTN_CAUSAL, vrow = flags & SKG_ATTN_ROWV, resident = flags & SKG_ATTN_RESIDENT_KV;
-  SKG_REQUIRE(!(flags & ~(SKG_ATTN_CAUSAL | SKG_ATTN_ROWV | SKG_ATTN_RESIDENT_KV)) && !(causal && vrow) && (!resident || vrow));
-  SKG_REQUIRE(Q && K && Vt && O && common_ok(batch, heads, Nq, Nkv, kv_stride, dh, !vrow));
+  // (the plan refuses what the flags and the shape rule out - the same SKG_E_BADARG the pointer and pitch checks give)
+  SKG_REQUIRE(Q && K && Vt && O);
   SKG_REQUIRE(ldq % 8 == 0 && ldk % 8 == 0 && ldvt % 8 == 0 && ldo % 4 == 0);
   SKG_REQUIRE(skg_aligned(Q, 16) && skg_aligned(K, 16) && skg_aligned(Vt, 16) && skg_aligned(O, 8));
+  const AttnFwdPlan plan = attn_fwd_plan(batch, heads, Nq, Nkv, kv_stride, dh, flags);
+  if (plan.code < 0) return plan.code;
   AttnParams p{};
   p.Q = (const half_t*)Q; p.ldq = ldq; p.K = (const half_t*)K; p.ldk = ldk; p.Vt = (const half_t*)Vt; p.ldvt = ldvt;
   p.O = (half_t*)O; p.ldo = ldo; p.lse = lse;
   p.batch = batch; p.heads = heads; p.Nq = Nq; p.Nkv = Nkv; p.kv_stride = kv_stride; p.dh = dh; p.scale = scale;
   hipStream_t st = (hipStream_t)stream;
-  // short key sequences (the 77 text tokens of every cross-attention): the LDS-resident kernel, HBM-bound
-  static const bool no_short = getenv("SKG_NO_ATTN_SHORT") != nullptr;        // A/B switch
-  if (vrow && !causal && kv_stride <= 80 && !no_short && (dh == 40 || dh == 64 || dh == 80 || dh == 160)) {
-    // queries per workgroup: ~1024+ workgroups where the launch has them, at least 64, a multiple of 64
-    long qch = ((long)heads * batch * Nq / 1024 + 63) / 64 * 64;
-    qch = qch < 64 ? 64 : (qch > 512 ? 512 : qch);
-    p.nx = skg_cdiv(Nq, (int)qch);
-    dim3 gs((unsigned)p.nx * heads * batch);
-    switch (dh) {
-      case 40: hipLaunchKernelGGL((attn_fwd_short_kernel<2, 3>), gs, dim3(256), 0, st, p, (int)qch); break;
-      case 64: hipLaunchKernelGGL((attn_fwd_short_kernel<2, 4>), gs, dim3(256), 0, st, p, (int)qch); break;
-      case 80: hipLaunchKernelGGL((attn_fwd_short_kernel<3, 5>), gs, dim3(256), 0, st, p, (int)qch); break;
-      default: hipLaunchKernelGGL((attn_fwd_short_kernel<5, 10>), gs, dim3(256), 0, st, p, (int)qch); break;
-    }
-    SKG_CHECK_LAUNCH("skg_attn_fwd (short keys)");
-    return SKG_OK;
-  }
-  // SKG_ATTN_RESIDENT_KV (a hint: cross-attention over a long prompt's 81 ... 240 keys): the same kernel with 10 / 15 score tiles
-  // where K and V of one (row, head) fit the 160 KB of LDS - not d = 160 above 160 keys; everything else runs as without the flag
-  const int rtiles = kv_stride <= 160 ? 10 : 15;
-  if (resident && kv_stride > 80 && kv_stride <= 240 && !no_short && (dh == 40 || dh == 64 || dh == 80 || (dh == 160 && rtiles == 10))) {
-    // one staging pass of up to 240 K / V rows per workgroup: at least 128 queries behind it where the launch has them
-    long qch = ((long)heads * batch * Nq / 1024 + 63) / 64 * 64;
-    qch = qch < 128 ? 128 : (qch > 512 ? 512 : qch);
-    p.nx = skg_cdiv(Nq, (int)qch);
-    dim3 gs((unsigned)p.nx * heads * batch);
-    if (rtiles == 10) {
+  p.nx = skg_cdiv(Nq, plan.qpw);
+  const dim3 grid((unsigned)p.nx * heads * batch);
+  const int qch = plan.qpw;
+  switch (plan.code) {
+    case 3005:
       switch (dh) {
-        case 40: hipLaunchKernelGGL((attn_fwd_short_kernel<2, 3, 10>), gs, dim3(256), 0, st, p, (int)qch); break;
-        case 64: hipLaunchKernelGGL((attn_fwd_short_kernel<2, 4, 10>), gs, dim3(256), 0, st, p, (int)qch); break;
-        case 80: hipLaunchKernelGGL((attn_fwd_short_kernel<3, 5, 10>), gs, dim3(256), 0, st, p, (int)qch); break;
-        default: hipLaunchKernelGGL((attn_fwd_short_kernel<5, 10, 10>), gs, dim3(256), 0, st, p, (int)qch); break;
+        case 40: hipLaunchKernelGGL((attn_fwd_short_kernel<2, 3>), grid, dim3(256), 0, st, p, qch); break;
+        case 64: hipLaunchKernelGGL((attn_fwd_short_kernel<2, 4>), grid, dim3(256), 0, st, p, qch); break;
+        case 80: hipLaunchKernelGGL((attn_fwd_short_kernel<3, 5>), grid, dim3(256), 0, st, p, qch); break;
+        default: hipLaunchKernelGGL((attn_fwd_short_kernel<5, 10>), grid, dim3(256), 0, st, p, qch); break;
       }
-    } else {
+      SKG_CHECK_LAUNCH("skg_attn_fwd (short keys)");
+      return SKG_OK;
+    case 3010:
       switch (dh) {
-        case 40: hipLaunchKernelGGL((attn_fwd_short_kernel<2, 3, 15>), gs, dim3(256), 0, st, p, (int)qch); break;
-        case 64: hipLaunchKernelGGL((attn_fwd_short_kernel<2, 4, 15>), gs, dim3(256), 0, st, p, (int)qch); break;
-        default: hipLaunchKernelGGL((attn_fwd_short_kernel<3, 5, 15>), gs, dim3(256), 0, st, p, (int)qch); break;
+        case 40: hipLaunchKernelGGL((attn_fwd_short_kernel<2, 3, 10>), grid, dim3(256), 0, st, p, qch); break;
+        case 64: hipLaunchKernelGGL((attn_fwd_short_kernel<2, 4, 10>), grid, dim3(256), 0, st, p, qch); break;
+        case 80: hipLaunchKernelGGL((attn_fwd_short_kernel<3, 5, 10>), grid, dim3(256), 0, st, p, qch); break;
+        default: hipLaunchKernelGGL((attn_fwd_short_kernel<5, 10, 10>), grid, dim3(256), 0, st, p, qch); break;
       }
-    }
-    SKG_CHECK_LAUNCH("skg_attn_fwd (resident keys)");
-    return SKG_OK;
-  }
+      SKG_CHECK_LAUNCH("skg_attn_fwd (resident keys)");
+      return SKG_OK;
+    case 3015:
+      switch (dh) {
+        case 40: hipLaunchKernelGGL((attn_fwd_short_kernel<2, 3, 15>), grid, dim3(256), 0, st, p, qch); break;
+        case 64: hipLaunchKernelGGL((attn_fwd_short_kernel<2, 4, 15>), grid, dim3(256), 0, st, p, qch); break;
+        default: hipLaunchKernelGGL((attn_fwd_short_kernel<3, 5, 15>), grid, dim3(256), 0, st, p, qch); break;
+      }
+      SKG_CHECK_LAUNCH("skg_attn_fwd (resident keys)");
+      return SKG_OK;
 #if defined(SKG_LAB) || defined(SKG_PHASES)
-  // lab / probe builds only: the withdrawn 8-wave formulation (attn_fwd8_kernel) for the self-attention of the 64 x 64 / 32 x 32
-  // levels, on request (SKG_ATTN8 = 1: one 8-wave workgroup per CU, 2: three 4-wave ones; SKG_NO_ATTN8 overrides)
-  static const bool no8 = getenv("SKG_NO_ATTN8") != nullptr || getenv("SKG_ATTN8") == nullptr;
-  static const int form8 = getenv("SKG_ATTN8") ? atoi(getenv("SKG_ATTN8")) : 0;      // 1: one 8-wave workgroup per CU, 2: three 4-wave ones
-  if (vrow && !causal && !no8 && (dh == 40 || dh == 64) && (long)skg_cdiv(Nq, 256) * heads * batch >= 192) {
-    const int qpw = form8 == 2 ? 128 : 256;
-    p.nx = skg_cdiv(Nq, qpw);
-    dim3 g8((unsigned)p.nx * heads * batch);
+    case 5004: case 5008: {
 #ifdef SKG_PHASES
-    static const int probe8 = getenv("SKG_ATTN8_PROBE") ? atoi(getenv("SKG_ATTN8_PROBE")) : 0;
-    if (probe8 && dh == 40 && form8 == 2) {
-      switch (probe8) {
-        case 1: hipLaunchKernelGGL((attn_fwd8_kernel<3, 3, true, 4, 3, 1>), g8, dim3(256), 0, st, p); break;
-        case 2: hipLaunchKernelGGL((attn_fwd8_kernel<3, 3, true, 4, 3, 2>), g8, dim3(256), 0, st, p); break;
-        case 4: hipLaunchKernelGGL((attn_fwd8_kernel<3, 3, true, 4, 3, 4>), g8, dim3(256), 0, st, p); break;
-        case 8: hipLaunchKernelGGL((attn_fwd8_kernel<3, 3, true, 4, 3, 8>), g8, dim3(256), 0, st, p); break;
-        case 12: hipLaunchKernelGGL((attn_fwd8_kernel<3, 3, true, 4, 3, 12>), g8, dim3(256), 0, st, p); break;
-        case 16: hipLaunchKernelGGL((attn_fwd8_kernel<3, 3, true, 4, 3, 16>), g8, dim3(256), 0, st, p); break;
-        case 28: hipLaunchKernelGGL((attn_fwd8_kernel<3, 3, true, 4, 3, 28>), g8, dim3(256), 0, st, p); break;
-        case 29: hipLaunchKernelGGL((attn_fwd8_kernel<3, 3, true, 4, 3, 29>), g8, dim3(256), 0, st, p); break;
-        default: hipLaunchKernelGGL((attn_fwd8_kernel<3, 3, true, 4, 3, 30>), g8, dim3(256), 0, st, p); break;
+      static const int probe8 = getenv("SKG_ATTN8_PROBE") ? atoi(getenv("SKG_ATTN8_PROBE")) : 0;
+      if (probe8 && dh == 40 && plan.code == 5004) {
+        switch (probe8) {
+          case 1: hipLaunchKernelGGL((attn_fwd8_kernel<3, 3, true, 4, 3, 1>), grid, dim3(256), 0, st, p); break;
+          case 2: hipLaunchKernelGGL((attn_fwd8_kernel<3, 3, true, 4, 3, 2>), grid, dim3(256), 0, st, p); break;
+          case 4: hipLaunchKernelGGL((attn_fwd8_kernel<3, 3, true, 4, 3, 4>), grid, dim3(256), 0, st, p); break;
+          case 8: hipLaunchKernelGGL((attn_fwd8_kernel<3, 3, true, 4, 3, 8>), grid, dim3(256), 0, st, p); break;
+          case 12: hipLaunchKernelGGL((attn_fwd8_kernel<3, 3, true, 4, 3, 12>), grid, dim3(256), 0, st, p); break;
+          case 16: hipLaunchKernelGGL((attn_fwd8_kernel<3, 3, true, 4, 3, 16>), grid, dim3(256), 0, st, p); break;
+          case 28: hipLaunchKernelGGL((attn_fwd8_kernel<3, 3, true, 4, 3, 28>), grid, dim3(256), 0, st, p); break;
+          case 29: hipLaunchKernelGGL((attn_fwd8_kernel<3, 3, true, 4, 3, 29>), grid, dim3(256), 0, st, p); break;
+          default: hipLaunchKernelGGL((attn_fwd8_kernel<3, 3, true, 4, 3, 30>), grid, dim3(256), 0, st, p); break;
+        }
+        SKG_CHECK_LAUNCH("skg_attn_fwd (8 waves, probe)");
+        return SKG_OK;
       }
-      SKG_CHECK_LAUNCH("skg_attn_fwd (8 waves, probe)");
+#endif
+      if (plan.code == 5004) {
+        if (dh == 40) hipLaunchKernelGGL((attn_fwd8_kernel<3, 3, true, 4, 3>), grid, dim3(256), 0, st, p);
+        else hipLaunchKernelGGL((attn_fwd8_kernel<4, 4, false, 4, 2>), grid, dim3(256), 0, st, p);
+      } else {
+        if (dh == 40) hipLaunchKernelGGL((attn_fwd8_kernel<3, 3, true>), grid, dim3(512), 0, st, p);
+        else hipLaunchKernelGGL((attn_fwd8_kernel<4, 4, false>), grid, dim3(512), 0, st, p);
+      }
+      SKG_CHECK_LAUNCH("skg_attn_fwd (8 waves)");
       return SKG_OK;
     }
 #endif
-    if (form8 == 2) {
-      if (dh == 40) hipLaunchKernelGGL((attn_fwd8_kernel<3, 3, true, 4, 3>), g8, dim3(256), 0, st, p);
-      else hipLaunchKernelGGL((attn_fwd8_kernel<4, 4, false, 4, 2>), g8, dim3(256), 0, st, p);
-    } else {
-      if (dh == 40) hipLaunchKernelGGL((attn_fwd8_kernel<3, 3, true>), g8, dim3(512), 0, st, p);
-      else hipLaunchKernelGGL((attn_fwd8_kernel<4, 4, false>), g8, dim3(512), 0, st, p);
+    case 2002:
+      switch (dh) {
+        case 16: hipLaunchKernelGGL((attn_fwd_kernel<1, 1, 2, true>), grid, dim3(256), 0, st, p); break;
+        case 32: hipLaunchKernelGGL((attn_fwd_kernel<1, 2, 2, true>), grid, dim3(256), 0, st, p); break;
+        default: hipLaunchKernelGGL((attn_fwd_kernel<2, 4, 2, true>), grid, dim3(256), 0, st, p); break;
+      }
+      break;
+    default: {      // 1000 + QT
+      const int rc = (flags & SKG_ATTN_ROWV) ? attn_fwd_launch_stream<true>(p, plan.code - 1000, plan.two_sets, grid, st)
+                                             : attn_fwd_launch_stream<false>(p, plan.code - 1000, plan.two_sets, grid, st);
+      if (rc != SKG_OK) return rc;
     }
-    SKG_CHECK_LAUNCH("skg_attn_fwd (8 waves)");
-    return SKG_OK;
-  }
-#endif
-  p.nx = skg_cdiv(Nq, dh == 160 ? 64 : 128);       // query tiles per workgroup: see SKG_ATTN_FWD_DISPATCH
-  dim3 grid((unsigned)p.nx * heads * batch);
-  if (causal) {
-    SKG_REQUIRE(dh != 160 && !vrow);
-    SKG_ATTN_FWD_CAUSAL_DISPATCH(grid);
-  } else if (vrow) {
-    SKG_ATTN_FWD_DISPATCH(grid, grid, true);
-  } else {
-    SKG_ATTN_FWD_DISPATCH(grid, grid, false);
   }
   SKG_CHECK_LAUNCH("skg_attn_fwd");
   return SKG_OK;

@@ -724,6 +724,17 @@ def attn_fwd(Q, K, Vt, batch, heads, Nq, Nkv, kv_stride, dh, scale, out=None, wa
     return (out, lse) if want_lse else out
 
 
+def attn_fwd_variant(batch, heads, Nq, Nkv, kv_stride, dh, causal=False, v_rows=False, resident_kv=False):
+    """skg_attn_fwd_variant: (instantiation code, queries per workgroup) of the attn_fwd call with these arguments - 1000 + QT the
+    streaming kernel, 2000 + QT causal, 3000 + NT the LDS-resident kernel.  No launch, no GPU; raises SkgError where attn_fwd would."""
+    qpw = ctypes.c_int(0)
+    flags = (ATTN_CAUSAL if causal else 0) | (ATTN_ROWV if v_rows else 0) | (ATTN_RESIDENT_KV if resident_kv else 0)
+    code = lib.skg_attn_fwd_variant(batch, heads, Nq, Nkv, kv_stride, dh, flags, ctypes.addressof(qpw))
+    if code < 0:
+        check(code, "skg_attn_fwd_variant")
+    return code, qpw.value
+
+
 def attn_bwd_delta(O, dO, batch, heads, Nq, dh):
     _f16(O, dO)
     delta = torch.empty(batch, heads, Nq, device=O.device, dtype=torch.float32)

@@ -20,12 +20,17 @@ source, the source wins.  What the kernels round (everything else is an fp32 MFM
     k~ = fp16(fp32(k) * fp32(scale * log2e)),  P = exp2(q . k~ - fp32(lse * log2e))         the UNROUNDED q
     dS = fp16(P * (dO . v - delta)),  dK = fp16((dS^T . q) * fp32(scale)),  dV = fp16(fp16(P)^T . dO)
 
+`exact_forward` is softmax(q k^T scale) v in fp64 on the same fp16 inputs, `emulate_forward` the forward's emulation against it (E,
+E_row as below, D_lse = max |lse - lse64|); `FWD_CASES` are the smallest launches that reach every instantiation skg_attn_fwd
+dispatches to, each with the code skg_attn_fwd_variant must report for it, and three input classes (unit, peaked, selector).
 `exact` is the closed form of the gradients of softmax(q k^T scale) v in fp64 on the same fp16 inputs.  `emulate` returns, per
 output, the emulation, the exact value, E (whole-tensor relative distance of the emulation from exact) and E_row (max over the rows
 of the [batch * N, heads * dh] tensor of ||row difference|| / rms row norm of the exact tensor): the kernels' own rounding noise,
 against which the GPU tests bound the kernels (factor 2, the convention of tests/test_gpu_sat_train.py).
 
-The module also holds the inputs both test files share: the parity cases (`SHAPES`, `case`) and the exact-answer probes."""
+The module also holds the inputs the test files share: the parity cases (`SHAPES`, `FWD_CASES`, `case`) and the exact-answer probes
+of the backward and of the forward."""
+import collections
 import math
 
 import numpy as np
@@ -84,10 +89,13 @@ def _nlse(lse):
     return (-lse.float() * torch.tensor(LOG2E32)).double()
 
 
-def forward(q, k, v, heads, scale, denom_fp16=False):
-    """-> (O fp16 [B, Nq, C], lse fp32 [B, heads, Nq]) as skg_attn_fwd stores them."""
+def forward(q, k, v, heads, scale, denom_fp16=False, causal=False):
+    """-> (O fp16 [B, Nq, C], lse fp32 [B, heads, Nq]) as skg_attn_fwd stores them.  causal: key j > query i is masked before the
+    maximum (the kernel writes -1e30 over the score: exp2 gives an exact 0)."""
     qt, kh, vh = _heads(_prescale(q, scale), heads), _heads(k, heads), _heads(v, heads)
     s = qt @ kh.transpose(-1, -2)
+    if causal:
+        s = s.masked_fill(_causal_mask(s.shape[-2], s.shape[-1]), float("-inf"))
     m = s.amax(-1, keepdim=True)
     e = torch.exp2(s - m)
     p16 = _r16(e)
@@ -178,12 +186,12 @@ def probe_cols(dh):
     return [0, 7, 16, 33, dh - 1]
 
 
-def probe_q(dh, heads, Nq):
+def probe_q(dh, heads, Nq, B=PROBE_B):
     """The probes' random Q: magnitudes in [0.5, 2), random signs, so that no expected dK element is near the fp16 subnormals."""
     g = torch.Generator().manual_seed(11)
     C = heads * dh
-    mag = 0.5 + 1.5 * torch.rand(PROBE_B, Nq, C, generator=g)
-    sign = torch.where(torch.rand(PROBE_B, Nq, C, generator=g) < 0.5, -1.0, 1.0)
+    mag = 0.5 + 1.5 * torch.rand(B, Nq, C, generator=g)
+    sign = torch.where(torch.rand(B, Nq, C, generator=g) < 0.5, -1.0, 1.0)
     return (mag * sign).half()
 
 
@@ -274,11 +282,248 @@ def probe_sweep(kind, dh, Nq, Nkv):
     return out
 
 
-def probe_check(got, want, what):
+def probe_check(got, want, what, tol=PROBE_TOL):
     """Analytic zeros exactly 0.0; the rest within PROBE_TOL of the expected value (one fp16 rounding of dS, one of the store)."""
-    got, want = got.detach().double().cpu(), want.double()
+    got = got.detach().double()
+    want = want.double().to(got.device)
     zero = want == 0
-    assert bool((got[zero] == 0).all()), f"{what}: {int((got[zero] != 0).sum())} analytic zeros are not 0.0"
-    bad = (got - want).abs() > PROBE_TOL * want.abs()
+    stray = zero & (got != 0)
+    assert not bool(stray.any()), (f"{what}: {int(stray.sum())} analytic zeros are not 0.0, first at {tuple(int(i) for i in stray.nonzero()[0])}: "
+                                   f"got {float(got[stray][0])}")
+    bad = (got - want).abs() > tol * want.abs()
     assert not bool(bad.any()), (f"{what}: {int(bad.sum())} elements off, first at {tuple(int(i) for i in bad.nonzero()[0])}: "
                                  f"got {float(got[bad][0])} want {float(want[bad][0])}")
+
+
+# ---------------------------------------------------------------------------------------------- forward: parity cases
+# skg_attn_fwd picks its instantiation from the size of the launch (attention.hip: attn_fwd_plan), so every case names the code
+# skg_attn_fwd_variant must report for it (1000 + QT streaming, 2000 + QT causal, 3000 + NT LDS-resident) and the queries one
+# workgroup covers; a case that lands elsewhere is a failed test.
+CAUSAL, ROWV, RESIDENT = 1, 2, 4               # include/skg.h SKG_ATTN_*
+FwdCase = collections.namedtuple("FwdCase", "name dh heads B Nq Nkv kvs flags classes variant qpw")
+_UP, _UPS, _U, _US = ("unit", "peaked"), ("unit", "peaked", "selector"), ("unit",), ("unit", "selector")
+FWD_CASES = [FwdCase(*c) for c in [
+    # -- streaming kernel, row-major V: the geometry of SHAPES where it stays on this kernel (a residue of 1 past the 128 / 64-query
+    #    workgroup, a ragged last key tile), 80 head columns with more than 80 key slots, 257 keys = five key tiles
+    ("rowv16", 16, 4, 2, 129, 65, 72, ROWV, _UPS, 1002, 128),
+    ("rowv32", 32, 3, 3, 17, 129, 136, ROWV, _UPS, 1002, 128),
+    ("rowv40", 40, 4, 2, 65, 193, 200, ROWV, _UPS, 1002, 128),
+    ("rowv64", 64, 3, 2, 65, 129, 136, ROWV, _UPS, 1002, 128),            # the 2 | (3 << 2) instantiation (one register set)
+    ("rowv80", 80, 4, 2, 65, 129, 136, ROWV, _UPS, 1002, 128),
+    ("rowv160", 160, 4, 2, 65, 96, 96, ROWV, _UP, 1001, 64),
+    ("rowv32_t5", 32, 3, 2, 129, 257, 264, ROWV, _UPS, 1002, 128),        # DEEP: the two-register-set ring wraps
+    ("rowv64_t5", 64, 3, 2, 129, 257, 264, ROWV, _US, 1002, 128),
+    ("rowv40_t5", 40, 4, 2, 129, 257, 264, ROWV, _US, 1002, 128),
+    # -- streaming kernel, V^T (kv_stride % 8 == 0)
+    ("vt16", 16, 4, 2, 129, 65, 72, 0, _UP, 1002, 128),
+    ("vt32", 32, 3, 3, 17, 129, 136, 0, _UP, 1002, 128),
+    ("vt40_77", 40, 4, 2, 129, 77, 80, 0, _UPS, 1002, 128),               # the ONES path at <= 80 keys
+    ("vt40", 40, 4, 2, 65, 193, 200, 0, _UP, 1002, 128),
+    ("vt64", 64, 3, 2, 65, 129, 136, 0, _UP, 1002, 128),
+    ("vt80", 80, 4, 2, 64, 65, 72, 0, _UPS, 1002, 128),
+    ("vt160", 160, 4, 2, 65, 96, 96, 0, _UP, 1001, 64),
+    ("vt80_t5", 80, 4, 2, 65, 257, 264, 0, _US, 1002, 128),               # DEEP
+    ("vt16_t5", 16, 4, 2, 129, 257, 264, 0, _US, 1002, 128),
+    # -- QT 3 (dh 40, >= 1024 workgroups of 192 queries) with no environment variable.  1537 = 8 * 192 + 1: the last workgroup
+    #    holds one query; 1585 = 8 * 192 + 49: its wave 1 starts at query 48
+    ("qt3_xcd", 40, 8, 16, 1537, 193, 200, ROWV, _US, 1003, 192),         # 128 pairs: XCD block map on
+    ("qt3_xcd_vt", 40, 8, 16, 1537, 193, 200, 0, _U, 1003, 192),
+    ("qt3_plain", 40, 5, 26, 1537, 129, 136, ROWV, _U, 1003, 192),        # 130 pairs: XCD map off
+    ("qt3_wave", 40, 8, 16, 1585, 129, 136, ROWV, _U, 1003, 192),
+    # -- short-key kernel (row-major V, <= 80 key slots): query chunks 64, 192 (three tiles per wave, last chunk one query), 512
+    ("short40_q64", 40, 4, 2, 129, 77, 80, ROWV, _UPS, 3005, 64),
+    ("short40_q192", 40, 8, 16, 1537, 77, 80, ROWV, _US, 3005, 192),
+    ("short40_q512", 40, 8, 16, 4097, 77, 80, ROWV, _U, 3005, 512),
+    ("short64_q128", 64, 5, 16, 1537, 77, 80, ROWV, _US, 3005, 128),
+    ("short80_q128", 80, 4, 16, 2049, 77, 80, ROWV, _U, 3005, 128),
+    ("short160_q128", 160, 3, 8, 2817, 77, 80, ROWV, _U, 3005, 128),
+    ("short160_k45", 160, 3, 2, 45, 45, 45, ROWV, _UP, 3005, 64),         # <= 64 keys (the short_rows mask), dense, no multiple of 8
+    ("short40_k50", 40, 8, 2, 200, 50, 56, ROWV, _UPS, 3005, 64),
+    ("short40_k80", 40, 4, 2, 129, 80, 80, ROWV, _UPS, 3005, 64),         # no dead register
+    # -- LDS-resident kernel behind the flag: NT 10 (150 keys: tile 9 ragged; 160: none) and NT 15 (231 keys in 232 slots;
+    #    200: tile 12 ragged, tiles 13 and 14 dead)
+    ("res10_40", 40, 4, 2, 129, 150, 152, ROWV | RESIDENT, _UPS, 3010, 128),
+    ("res10_64", 64, 3, 2, 129, 160, 160, ROWV | RESIDENT, _UPS, 3010, 128),
+    ("res10_80", 80, 4, 2, 129, 150, 152, ROWV | RESIDENT, _UPS, 3010, 128),
+    ("res10_160", 160, 3, 2, 129, 160, 160, ROWV | RESIDENT, _UP, 3010, 128),
+    ("res10_40_q256", 40, 8, 16, 2049, 150, 152, ROWV | RESIDENT, _U, 3010, 256),
+    ("res15_40", 40, 4, 2, 129, 231, 232, ROWV | RESIDENT, _UPS, 3015, 128),
+    ("res15_64", 64, 3, 2, 129, 231, 232, ROWV | RESIDENT, _UPS, 3015, 128),
+    ("res15_80", 80, 4, 2, 129, 231, 232, ROWV | RESIDENT, _UPS, 3015, 128),
+    ("res15_40_q192", 40, 8, 16, 1537, 200, 200, ROWV | RESIDENT, _U, 3015, 192),
+    ("res_160_stream", 160, 3, 2, 65, 231, 232, ROWV | RESIDENT, _UP, 1001, 64),      # does not fit the LDS: runs as without the flag
+    # -- causal (V^T): 80 rows / 77 keys (the text encoder), a residue of 1 with two key tiles, 257 keys in 264 rows (five tiles)
+    ("causal16_80", 16, 4, 2, 80, 77, 80, CAUSAL, _UP, 2002, 128),
+    ("causal32_80", 32, 3, 2, 80, 77, 80, CAUSAL, _UP, 2002, 128),
+    ("causal64_80", 64, 3, 2, 80, 77, 80, CAUSAL, _UP, 2002, 128),
+    ("causal16_129", 16, 4, 2, 129, 129, 136, CAUSAL, _UP, 2002, 128),
+    ("causal32_129", 32, 3, 2, 129, 129, 136, CAUSAL, _UP, 2002, 128),
+    ("causal64_129", 64, 3, 2, 129, 129, 136, CAUSAL, _UP, 2002, 128),
+    ("causal16_264", 16, 4, 2, 264, 257, 264, CAUSAL, _UP, 2002, 128),
+    ("causal32_264", 32, 3, 2, 264, 257, 264, CAUSAL, _UP, 2002, 128),
+    ("causal64_264", 64, 3, 2, 264, 257, 264, CAUSAL, _UP, 2002, 128),
+]]
+FWD_BY_NAME = {c.name: c for c in FWD_CASES}
+FWD_PARAMS = [(c.name, cls) for c in FWD_CASES for cls in c.classes]
+# every product instantiation of skg_attn_fwd as (variant, dh, V row-major): what the table has to reach
+FWD_REQUIRED = ({(1002, d, r) for d in (16, 32, 40, 64, 80) for r in (False, True)} | {(1001, 160, False), (1001, 160, True)} |
+                {(1003, 40, False), (1003, 40, True)} | {(2002, d, False) for d in (16, 32, 64)} |
+                {(3005, d, True) for d in (40, 64, 80, 160)} | {(3010, d, True) for d in (40, 64, 80, 160)} |
+                {(3015, d, True) for d in (40, 64, 80)})
+SELECTOR_K, SELECTOR_Q, SELECTOR_COLS = 8.0, 1.0, 8
+
+
+def fwd_denom_fp16(variant, dh):
+    """The denominator sums the fp16 P exactly in the dh = 40 instantiations of attn_fwd_kernel (ONES: l is a row of the P.V MFMA),
+    whatever the key count and the V form; the LDS-resident kernel sums the unrounded exp2."""
+    return variant // 1000 == 1 and dh == 40
+
+
+def selector_keys(B, Nkv):
+    """The dominant key of every batch row: first key tile for row 0, a middle tile for row 1, the last (ragged) tile for the rest."""
+    nt = (Nkv + 63) // 64
+    return [3 if b == 0 else min(64 * (nt // 2) + 5, Nkv - 1) if b == 1 else max(Nkv - 2, 64 * (nt - 1)) for b in range(B)]
+
+
+def fwd_inputs(c, cls):
+    """fp16 q [B, Nq, C], k, v [B, Nkv, C] of one case and input class (fixed seeds)."""
+    q, k, v, _ = case(c.dh, c.heads, c.B, c.Nq, c.Nkv)
+    if cls == "unit":
+        return q, k, v
+    if cls == "peaked":                         # scores with sigma ~ 4 nat: a few keys dominate (x 4 is exact in fp16)
+        return (q.float() * 4.0).half(), k, v
+    assert cls == "selector"
+    # K = 0 except one key per batch row with 8.0 in the first 8 columns of every head, Q = 1.0 there: that key's score is
+    # 64 scale log2e in the log2 domain, every other one exactly 0 - the streaming kernel re-bases its reference maximum at the
+    # tile that holds the key (tile 0, a middle one, the last one) and nowhere else
+    qs = torch.zeros(c.B, c.Nq, c.heads, c.dh, dtype=torch.float16)
+    qs[..., :SELECTOR_COLS] = SELECTOR_Q
+    ks = torch.zeros(c.B, c.Nkv, c.heads, c.dh, dtype=torch.float16)
+    for b, js in enumerate(selector_keys(c.B, c.Nkv)):
+        ks[b, js, :, :SELECTOR_COLS] = SELECTOR_K
+    return qs.view(c.B, c.Nq, -1), ks.view(c.B, c.Nkv, -1), v
+
+
+def _causal_mask(Nq, Nkv):
+    return torch.arange(Nkv)[None, :] > torch.arange(Nq)[:, None]
+
+
+def exact_forward(q, k, v, heads, scale, causal=False):
+    """fp64 softmax(q k^T scale) v on the same fp16 inputs -> (O [B, Nq, C], lse [B, heads, Nq])."""
+    qh, kh, vh = (_heads(t, heads) for t in (q, k, v))
+    s = qh @ kh.transpose(-1, -2) * scale
+    if causal:
+        s = s.masked_fill(_causal_mask(s.shape[-2], s.shape[-1]), float("-inf"))
+    return _rows(torch.softmax(s, dim=-1) @ vh), torch.logsumexp(s, dim=-1)
+
+
+def emulate_forward(q, k, v, heads, scale, causal=False, denom_fp16=False):
+    """-> dict(o_emu fp16, o_exact fp64, E, E_row (`distances`), lse_emu fp32, lse_exact fp64, D_lse = max |lse_emu - lse_exact|)."""
+    o, lse = forward(q, k, v, heads, scale, denom_fp16, causal)
+    oe, le = exact_forward(q, k, v, heads, scale, causal)
+    E, E_row = distances(o, oe)
+    return dict(o_emu=o, o_exact=oe, E=E, E_row=E_row, lse_emu=lse, lse_exact=le, D_lse=float((lse.double() - le).abs().max()))
+
+
+def emulate_case(c, cls):
+    q, k, v = fwd_inputs(c, cls)
+    return (q, k, v), emulate_forward(q, k, v, c.heads, c.dh ** -0.5, bool(c.flags & CAUSAL), fwd_denom_fp16(c.variant, c.dh))
+
+
+def selector_margin(c):
+    """log2-domain distance of the selector key's score from every other key's, from fp64 scores on the selector inputs (min over rows)."""
+    q, k, _ = fwd_inputs(c, "selector")
+    s = _heads(q, c.heads) @ _heads(k, c.heads).transpose(-1, -2) * (c.dh ** -0.5 * 1.4426950408889634)
+    top = s.topk(2, dim=-1).values
+    return float((top[..., 0] - top[..., 1]).min())
+
+
+# ---------------------------------------------------------------------------------------------- forward: exact-answer probes
+# K = 0: every probability is exactly 1, the denominator the exact integer Nkv (causal: i + 1) and the numerator exact in fp32, so a
+# stored value is one fp32 reciprocal and one fp16 rounding from the closed form: one fp16 unit in the last place (2^-10 relative);
+# lse within 4 fp32 units of ln n.  (name, dh, heads, B, Nq, Nkv, kvs, flags, variant, qpw); batch row b carries (b + 1) x.
+FWD_PROBE_TOL = 2.0 ** -10
+FwdProbe = collections.namedtuple("FwdProbe", "name dh heads B Nq Nkv kvs flags variant qpw")
+FWD_PROBES = [FwdProbe(*g) for g in [
+    ("rowv16", 16, 4, 2, 200, 77, 80, ROWV, 1002, 128), ("rowv32", 32, 3, 2, 77, 200, 208, ROWV, 1002, 128),
+    ("rowv40", 40, 8, 2, 77, 200, 208, ROWV, 1002, 128), ("vt40", 40, 8, 2, 200, 77, 80, 0, 1002, 128),
+    ("rowv64", 64, 5, 2, 77, 200, 208, ROWV, 1002, 128), ("vt64", 64, 5, 2, 200, 77, 80, 0, 1002, 128),
+    ("rowv80", 80, 4, 2, 77, 200, 208, ROWV, 1002, 128), ("vt80", 80, 4, 2, 200, 77, 80, 0, 1002, 128),
+    ("rowv160", 160, 8, 2, 77, 200, 208, ROWV, 1001, 64), ("vt160", 160, 8, 2, 200, 77, 80, 0, 1001, 64),
+    ("qt3", 40, 8, 16, 1537, 1537, 1537, ROWV, 1003, 192),
+    ("short40", 40, 8, 2, 200, 77, 80, ROWV, 3005, 64), ("short64", 64, 5, 2, 200, 77, 80, ROWV, 3005, 64),
+    ("short80", 80, 4, 2, 200, 77, 80, ROWV, 3005, 64), ("short160", 160, 8, 2, 200, 77, 80, ROWV, 3005, 64),
+    ("short40_q512", 40, 8, 16, 4097, 77, 80, ROWV, 3005, 512),
+    ("res10_40", 40, 8, 2, 200, 150, 152, ROWV | RESIDENT, 3010, 128), ("res10_160", 160, 8, 2, 200, 150, 152, ROWV | RESIDENT, 3010, 128),
+    ("res15_64", 64, 5, 2, 77, 200, 208, ROWV | RESIDENT, 3015, 128), ("res15_80", 80, 4, 2, 200, 231, 232, ROWV | RESIDENT, 3015, 128),
+]]
+FWD_CAUSAL_PROBES = [FwdProbe(*g) for g in [
+    ("causal16", 16, 4, 2, 200, 200, 200, CAUSAL, 2002, 128), ("causal32", 32, 3, 2, 80, 77, 80, CAUSAL, 2002, 128),
+    ("causal64", 64, 5, 2, 200, 200, 200, CAUSAL, 2002, 128), ("causal64_264", 64, 3, 2, 264, 257, 264, CAUSAL, 2002, 128),
+]]
+
+
+def probe_fwd_keys(Nkv):
+    """probe_keys plus the last key, and the positions around the 192-query / 192-key marks and key 1536 of the QT 3 launch."""
+    return sorted(set(probe_keys(Nkv)) | {x for x in (191, 192, 1536) if x < Nkv} | {Nkv - 1})
+
+
+def probe_fwd_sweep(dh, Nkv):
+    """(js, c): every key position once, the columns cycling (each of the five appears: there are at least six key positions)."""
+    cols = [c for c in probe_cols(dh) if c < dh]
+    return [(js, cols[i % len(cols)]) for i, js in enumerate(probe_fwd_keys(Nkv))]
+
+
+def _probe_fwd_lse(g, causal=False):
+    n = torch.arange(1, g.Nq + 1).clamp(max=g.Nkv).double() if causal else torch.full((g.Nq,), float(g.Nkv), dtype=torch.float64)
+    return n.log()[None, None, :].expand(g.B, g.heads, g.Nq)
+
+
+def probe_fwd_onehot(g, js, c, q=None):
+    """K = 0, any Q, V one-hot (key js, column c of every head, value b + 1): O[q][c] = (b + 1) / Nkv for every query, every other
+    element exactly 0, lse = ln Nkv."""
+    C = g.heads * g.dh
+    q = probe_q(g.dh, g.heads, g.Nq, g.B) if q is None else q
+    v = _one_hot(g.B, g.Nkv, g.heads, g.dh, js, c, 1.0)
+    want = torch.zeros(g.B, g.Nq, g.heads, g.dh, dtype=torch.float64)
+    for b in range(g.B):
+        want[b, :, :, c] = (b + 1) / g.Nkv
+    return dict(q=q, k=torch.zeros(g.B, g.Nkv, C, dtype=torch.float16), v=v, o=want.view(g.B, g.Nq, C), lse=_probe_fwd_lse(g))
+
+
+def probe_fwd_coded(g, c, q=None):
+    """K = 0, V = (b + 1) code_j in column c: O[q][c] = (b + 1) mean code, every other element exactly 0.  A lost or doubled key, or
+    a ragged-tile mask off by one, moves the mean."""
+    C = g.heads * g.dh
+    q = probe_q(g.dh, g.heads, g.Nq, g.B) if q is None else q
+    code = key_code(g.Nkv)
+    v = torch.zeros(g.B, g.Nkv, g.heads, g.dh, dtype=torch.float16)
+    want = torch.zeros(g.B, g.Nq, g.heads, g.dh, dtype=torch.float64)
+    for b in range(g.B):
+        v[b, :, :, c] = ((b + 1) * code).half()[:, None]
+        want[b, :, :, c] = (b + 1) * float(code.mean())
+    return dict(q=q, k=torch.zeros(g.B, g.Nkv, C, dtype=torch.float16), v=v.view(g.B, g.Nkv, C), o=want.view(g.B, g.Nq, C),
+                lse=_probe_fwd_lse(g))
+
+
+def probe_fwd_causal(g, js, c, q=None):
+    """Causal, K = 0, V one-hot (key js, column c, value b + 1): query i sees keys 0 .. min(i, Nkv - 1), so O[i][c] = (b + 1) / (i + 1)
+    for i >= js (/ Nkv from query Nkv on) and exactly 0 for i < js; lse[i] = ln(i + 1).  A mask off by one flips an exact zero."""
+    p = probe_fwd_onehot(g, js, c, q)
+    n = torch.arange(1, g.Nq + 1).clamp(max=g.Nkv).double()
+    want = torch.zeros(g.B, g.Nq, g.heads, g.dh, dtype=torch.float64)
+    for b in range(g.B):
+        want[b, js:, :, c] = ((b + 1) / n[js:])[:, None]
+    p.update(o=want.view(g.B, g.Nq, g.heads * g.dh), lse=_probe_fwd_lse(g, causal=True))
+    return p
+
+
+def probe_fwd_check(o, lse, p, what):
+    """O: analytic zeros exactly 0.0, the rest within one fp16 unit in the last place; lse within 4 fp32 units of ln n.  The message
+    names the first wrong (batch row, query, column) / (batch row, head, query)."""
+    probe_check(o, p["o"], f"{what} O", tol=FWD_PROBE_TOL)
+    got = lse.detach().double()
+    want, ulp = p["lse"].to(got.device), torch.from_numpy(np.spacing(p["lse"].float().numpy())).double().to(got.device)
+    bad = (got - want).abs() > 4 * ulp
+    assert not bool(bad.any()), (f"{what} lse: {int(bad.sum())} entries off, first at (b, head, query) = "
+                                 f"{tuple(int(i) for i in bad.nonzero()[0])}: got {float(got[bad][0])} want {float(want[bad][0])}")

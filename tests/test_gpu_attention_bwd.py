@@ -62,8 +62,9 @@ def _dkv(ops, Q, K, V, dO, lse, delta, B, heads, Nq, Nkv, kvs, dh, scale):
 def _reference(dh, heads, B, Nq, Nkv, e):
     """Inputs, emulation and exact gradients of one case: computed once, shared, never written to."""
     q, k, v, do = ae.case(dh, heads, B, Nq, Nkv, 2.0 ** e)
-    kvs = ae.kv_stride_of(dh, Nkv)
-    return (q, k, v, do), ae.emulate(q, k, v, do, heads, dh ** -0.5, denom_fp16=(dh == 40 and kvs > 80))
+    from sketch2img_amd import ops
+    variant, _ = ops.attn_fwd_variant(B, heads, Nq, Nkv, ae.kv_stride_of(dh, Nkv), dh, v_rows=True)      # the forward _parity runs
+    return (q, k, v, do), ae.emulate(q, k, v, do, heads, dh ** -0.5, denom_fp16=ae.fwd_denom_fp16(variant, dh))
 
 
 def _parity(ops, dh, heads, B, Nq, Nkv, e):

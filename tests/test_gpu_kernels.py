@@ -935,6 +935,8 @@ def test_attention_forward(ops, dh, heads, Nq, Nkv):
     vp = torch.zeros(B, kvs, C, dtype=torch.float16); vp[:, :Nkv] = v
     Q, K, V = q.reshape(B * Nq, C).to(d), kp.reshape(B * kvs, C).to(d), vp.reshape(B * kvs, C).to(d)
     o, lse = ops.attn_fwd(Q, K, ops.transpose(V), B, heads, Nq, Nkv, kvs, dh, scale, want_lse=True)
+    # B = 2 keeps every launch here under the 1024 workgroups QT 3 needs: the streaming kernel at two query tiles per wave (one at d = 160)
+    assert ops.attn_fwd_variant(B, heads, Nq, Nkv, kvs, dh) == ((1001, 64) if dh == 160 else (1002, 128))
     ro, rl = ref_attention(q.float(), k.float(), v.float(), heads, scale)
     r, _ = report(f"attn fwd dh{dh} {Nq}x{Nkv}", o.float().cpu().view(B, Nq, C), ro)
     # P is rounded to fp16 before the PV product (like every fp16 flash kernel): ~1e-3 relative
@@ -946,13 +948,16 @@ def test_attention_forward(ops, dh, heads, Nq, Nkv):
     if kvs <= 80 and dh in (40, 64, 80, 160):
         # short key sequences (the 77 text tokens) with row-major V take the LDS-resident kernel (attn_fwd_short_kernel):
         # another kernel, so not bit-equal to the flash kernel - checked against the reference like it, and deterministic
+        assert ops.attn_fwd_variant(B, heads, Nq, Nkv, kvs, dh, v_rows=True)[0] == 3005
         assert report(f"attn fwd short-key kernel dh{dh} {Nq}x{Nkv}", o2.float().cpu().view(B, Nq, C), ro)[0] < 2e-3
         assert report("attn lse short-key kernel", lse2.cpu(), rl)[1] < 2e-3
         o3, lse3 = ops.attn_fwd(Q, K, V, B, heads, Nq, Nkv, kvs, dh, scale, want_lse=True, v_rows=True)
         assert torch.equal(o2, o3) and torch.equal(lse2, lse3)
     else:
-        # every other shape: the same 4-wave flash kernel as the transposed-copy path (QT 3 at d = 40 on large maps), fed through
-        # ds_read_b64_tr_b16.  (The 8-wave formulation of round 4, attn_fwd8_kernel, left the product: lab build + SKG_ATTN8 only.)
+        # every other shape: the same 4-wave flash kernel as the transposed-copy path (QT 2 also at d = 40, 4096 tokens: 352 workgroups
+        # of 192 queries; QT 3 takes 1024 - tests/test_gpu_attention_fwd.py runs it), fed through ds_read_b64_tr_b16.  (The 8-wave
+        # formulation of round 4, attn_fwd8_kernel, left the product: lab build + SKG_ATTN8 only.)
+        assert ops.attn_fwd_variant(B, heads, Nq, Nkv, kvs, dh, v_rows=True) == ops.attn_fwd_variant(B, heads, Nq, Nkv, kvs, dh)
         assert torch.equal(o2, o) and torch.equal(lse2, lse)
 
 
@@ -995,13 +1000,15 @@ def test_attention_forward_strided_qkv_and_online_rescale(ops):
 
 
 def test_attention_forward_large_map_online_rescale_and_structure(ops):
-    """The self-attention kernel of the large maps (attn_fwd_kernel<2, 3, 3>: three query tiles per wave at d = 40; row-major V):
-    (a) spiked keys in late tiles force the reference maximum to move (the rescale branch); (b) structured probes with
+    """The d = 40 self-attention kernel on a large map, row-major V.  B = 2 makes 256 workgroups of 192 queries, under the 1024 at which
+    the launcher takes three query tiles per wave, so this runs attn_fwd_kernel<2, 3, 2> (QT 2: asserted below); the QT 3 instantiation of
+    the 64 x 64 level is under tests/test_gpu_attention_fwd.py.  (a) spiked keys in late tiles force the reference maximum to move (the rescale branch); (b) structured probes with
     exact answers: K = 0 makes the softmax uniform, V = one-hot on single keys / single head columns, so every output
     is an exactly known value - a lost k-step, a wrong key <-> k-slot map or a wrong V row permutation shows as an O(1) error."""
     B, heads, dh, N = 2, 8, 40, 3072
     C = heads * dh
     d = dev()
+    assert ops.attn_fwd_variant(B, heads, N, N, N, dh, v_rows=True) == (1002, 128)
     qkv = rnd(B * N, 3 * C, seed=1)
     qkv[B * N // 2 + 2900, C:2 * C] *= 12.0          # one key with a huge norm in the 46th kv tile of row 1
     qkv[1700, C:2 * C] *= -9.0

@@ -143,6 +143,15 @@ def test_folded_entry_points_keep_their_twins_preconditions():
     # -- both attention-forward flags, or an unknown one, stay a refusal
     fwd = lambda flags: lib.skg_attn_fwd(16, 8, 16, 8, 16, 8, 16, 8, None, 1, 1, 8, 8, 8, 24, 1.0, flags, None)
     assert fwd(3) == -1 and fwd(4) == -1 and fwd(1) == -2 and fwd(2) == -2
+    # -- and the dispatch query answers with the code skg_attn_fwd gives for the same shape and flags (it takes no pointers)
+    var = lambda flags, dh=24, Nkv=8, kvs=8, batch=1: lib.skg_attn_fwd_variant(batch, 1, 8, Nkv, kvs, dh, flags, None)
+    assert var(3) == -1 and var(4) == -1 and var(1) == -2 and var(2) == -2 and var(0) == -2 and var(8) == -1
+    assert var(0, dh=40, Nkv=9) == -1 and var(0, dh=40, batch=0) == -1 and var(0, dh=44) == -1          # kv_stride < Nkv, batch, dh % 8
+    assert var(0, dh=40, Nkv=7, kvs=7) == -1 and var(2, dh=40, Nkv=7, kvs=7) == 3005                    # only V^T needs kv_stride % 8
+    assert var(1, dh=160) == -1 and var(1, dh=40) == -2 and var(1, dh=80) == -2 and var(1, dh=64) == 2002   # causal: dh 16 / 32 / 64
+    causal = lambda dh: lib.skg_attn_fwd(16, 8, 16, 8, 16, 8, 16, 8, None, 1, 1, 8, 8, 8, dh, 1.0, 1, None)
+    assert causal(160) == -1 and causal(40) == -2 and causal(80) == -2
+    assert var(0, dh=160) == 1001 and var(6, dh=160, Nkv=200, kvs=200) == 1001 and var(6, dh=80, Nkv=200, kvs=200) == 3015
     # -- dQ: delta, or O and delta_out
     dq = lambda O, delta, dout: lib.skg_attn_bwd_dq(16, 24, 16, 24, 16, 24, 16, 24, O, 24, 16, delta, dout, 16, 24, 1, 1, 64, 77, 80,
                                                     24, 1.0, None)
