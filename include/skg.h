@@ -652,6 +652,19 @@ size_t skg_layernorm_param_scratch_floats(int C);
 int skg_layernorm_param_grads(const void* X, int ldx, const void* dY, int lddy, int M, int C, const float* stats, float scale,
                               int accumulate, float* dgamma, float* dbeta, float* scratch, void* stream);
 
+/* ---- ControlNet hint encoder: the small-channel 3x3 convolutions (csrc/condembed.hip) ---------------------------------------
+ * Additive entry point (SKG_ABI_VERSION unchanged).  The first three layers of diffusers' ControlNetConditioningEmbedding run at
+ * the pixel resolution with 3 and 16 input channels, which skg_conv3x3_f16 (Cin % 32 == 0) does not take:
+ *   Y[(b, oy, ox)][n] = act(bias[n] + sum_{ky,kx,c} X[b][stride*oy + ky - 1][stride*ox + kx - 1][c] * W[n][ky][kx][c])   (0 outside)
+ * Cin == 3:  X is the picture as it is, float [B][3][IH][IW] (ldx ignored), rounded to fp16 on the way into the MFMA;
+ *            Wp [Cout][64] fp16, Wp[n][(3 ky + kx) * 4 + c], every other column zero.
+ * Cin == 16: X fp16 [B*IH*IW][ldx >= 16] (ldx % 8 == 0, 16-byte aligned); Wp [Cout][160] fp16, Wp[n][(3 ky + kx) * 16 + c],
+ *            columns 144 .. 159 zero.       (sketch2img_amd.packs.pack_conv_small makes both.)
+ * Cout 16 or 32; stride 1, or 2 with even IH and IW (OH = IH / stride); Y fp16 [B*OH*OW][ldy >= Cout], ldy % 4 == 0, 8-byte
+ * aligned; bias [Cout] fp16 or NULL; silu != 0: act = SiLU, else the identity.  fp32 accumulation, one rounding. */
+int skg_conv3x3_small_f16(const void* X, int ldx, const void* Wp, void* Y, int ldy, int B, int IH, int IW, int Cin, int Cout,
+                          int stride, const void* bias, int silu, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

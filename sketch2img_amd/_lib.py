@@ -31,7 +31,8 @@ LIB_PATH = os.environ.get("SKG_LIB") or os.path.join(_HERE, "libskg.so")
 # skg_nonfinite_flag and skg_adamw_step_guarded, the dynamic loss scale's verdict and its guarded optimizer step;
 # skg_cfg_dpmpp2m_sde_step, the DPM-Solver++ 2M step with the noise term of algorithm_type "sde-dpmsolver++";
 # skg_latent_renoise, the img2img start a*init + s*noise and the masked-repaint blend; skg_adamw8_step, AdamW on block-wise
-# quantised 8-bit moments (flat_adamw.FlatAdamW state_bits = 8); skg_attn_fwd_variant, which instantiation skg_attn_fwd runs
+# quantised 8-bit moments (flat_adamw.FlatAdamW state_bits = 8); skg_attn_fwd_variant, which instantiation skg_attn_fwd runs;
+# skg_conv3x3_small_f16, the 3- and 16-channel convolutions of the ControlNet hint encoder
 ABI_VERSION = 6
 
 # spec letters: p = device/host pointer, i = int, f = float, u = unsigned, z = size_t (return only)
@@ -121,6 +122,8 @@ SIGNATURES = {
     "skg_latent_renoise": ("i", "pppipiiffp"),
     # 8-bit AdamW state (flat_adamw.py state_bits = 8): additive entry point, same ABI version
     "skg_adamw8_step": ("i", "ppppppppppipfffffifpp"),
+    # ControlNet hint encoder (controlnet.py): the small-channel 3x3 convolutions, additive entry point, same ABI version
+    "skg_conv3x3_small_f16": ("i", "pippiiiiiiipip"),
 }
 
 _CT = {"p": ctypes.c_void_p, "i": ctypes.c_int, "f": ctypes.c_float, "u": ctypes.c_uint,

@@ -172,7 +172,12 @@ def _config_from_folder(path: Optional[str]) -> UNetConfig:
     cj = os.path.join(path, "unet", "config.json")
     if not os.path.exists(cj):
         return SD15
-    c = json.load(open(cj))
+    return _config_from_json(json.load(open(cj)), "unet/config.json")
+
+
+def _config_from_json(c: dict, what: str) -> UNetConfig:
+    """UNetConfig from the fields of a diffusers config.json (`what` names the file in the error): UNet2DConditionModel's, or the
+    fields a ControlNetModel's config shares with it (it has no up blocks: their default stands)."""
     boc = tuple(c.get("block_out_channels", SD15.block_out_channels))
     ahd = c.get("attention_head_dim", 8)            # diffusers' "attention_head_dim" is a head COUNT for these models
     heads = tuple(ahd) if isinstance(ahd, (list, tuple)) else (int(ahd),) * len(boc)
@@ -194,7 +199,7 @@ def _config_from_folder(path: Optional[str]) -> UNetConfig:
     if len(heads) != len(boc) or len(boc) != 4:
         unsupported.append(f"block_out_channels {boc} / attention_head_dim {ahd}")
     if unsupported:
-        raise NotImplementedError("unet/config.json asks for features outside the SD1.x / SD2.x UNet this package "
+        raise NotImplementedError(f"{what} asks for features outside the SD1.x / SD2.x UNet this package "
                                   "implements: " + "; ".join(unsupported))
     return UNetConfig(in_channels=c.get("in_channels", 4), out_channels=c.get("out_channels", 4), block_out_channels=boc,
                       layers_per_block=c.get("layers_per_block", 2), cross_attention_dim=c.get("cross_attention_dim", 768),
@@ -377,6 +382,41 @@ class AntiGradientPipeline:
             m = torch.nn.functional.avg_pool2d(m, f)
         return m
 
+    def _check_control(self, controlnet, control_image, scale, start, end, sketch_image, S: int, height: int, width: int):
+        """The ControlNet arguments of __call__, checked before any device work -> the control picture as a float tensor
+        [1 or S, 3, height, width] in [0, 1], or None without a ControlNet."""
+        if isinstance(controlnet, (list, tuple)):
+            raise NotImplementedError("a list of ControlNets (diffusers' MultiControlNetModel) is not implemented: pass one ControlNetModel")
+        if (controlnet is None) != (control_image is None):
+            raise ValueError("`controlnet` and `control_image` go together: " +
+                             ("`control_image` needs the `controlnet` that reads it" if controlnet is None else
+                              "`controlnet` needs a `control_image`"))
+        if controlnet is None:
+            return None
+        from ..controlnet import ControlNetModel
+        if not isinstance(controlnet, ControlNetModel):
+            raise ValueError(f"`controlnet` has to be a sketch2img_amd.controlnet.ControlNetModel but is {type(controlnet)}")
+        if sketch_image is not None:
+            raise ValueError("`sketch_image` (LGP guidance) cannot be combined with a ControlNet: the guidance gradient would need the "
+                             "ControlNet's backward")
+        if getattr(self.unet, "_hip", None) is not None and self.unet._hip.inject is not None:
+            raise NotImplementedError("a ControlNet together with a SatMixin injector on the UNet is not implemented")
+        if controlnet.cfg != self.unet.cfg:
+            raise ValueError(f"`controlnet` was built for {controlnet.cfg}, the pipeline's UNet is {self.unet.cfg}")
+        if isinstance(scale, (list, tuple)) or not float(scale) == float(scale):
+            raise ValueError(f"`controlnet_conditioning_scale` has to be one number but is {scale!r}")
+        if not 0.0 <= float(start) <= float(end) <= 1.0:
+            raise ValueError(f"`control_guidance_start` / `control_guidance_end` have to satisfy 0 <= start <= end <= 1 but are "
+                             f"{start} / {end}")
+        img = control_image if torch.is_tensor(control_image) else self._pil_to_tensor(control_image, "RGB", height, width, "control_image")
+        if img.dim() != 4 or img.shape[0] not in (1, S) or img.shape[1] != 3 or not img.is_floating_point():
+            raise ValueError(f"`control_image` has to be a float tensor [1 or {S}, 3, {height}, {width}] in [0, 1] but is "
+                             f"{tuple(img.shape)} {img.dtype}")
+        if tuple(img.shape[2:]) != (height, width):
+            raise ValueError(f"`control_image` has to be {height} x {width} (height x width) but is {img.shape[2]} x {img.shape[3]}: "
+                             "resize it first")
+        return img.float()
+
     def _vae_encodes(self) -> bool:
         from ..vae import AutoencoderKL
         if isinstance(self.vae, AutoencoderKL):
@@ -435,8 +475,17 @@ class AntiGradientPipeline:
                  eta: float = 0.0, generator=None, latents: Optional[torch.Tensor] = None,
                  output_type: Optional[str] = "pil", return_dict: bool = True,
                  callback: Optional[Callable[[int, int, torch.Tensor], None]] = None,
-                 callback_steps: Optional[int] = 1, sketch_image=None, image=None, strength: float = 0.8, mask_image=None):
-        """``image``, ``strength``: img2img (diffusers' StableDiffusionImg2ImgPipeline) - the trajectory starts from the picture,
+                 callback_steps: Optional[int] = 1, sketch_image=None, image=None, strength: float = 0.8, mask_image=None,
+                 controlnet=None, control_image=None, controlnet_conditioning_scale: float = 1.0,
+                 control_guidance_start: float = 0.0, control_guidance_end: float = 1.0):
+        """``controlnet``, ``control_image``: ControlNet conditioning (diffusers' StableDiffusionControlNetPipeline) - a
+        ``sketch2img_amd.controlnet.ControlNetModel`` and its control picture (line art, scribble, canny edges ...): a float tensor
+        [1 or S, 3, height, width] in [0, 1], a PIL image or a list of them of exactly width x height; one picture is shared by all
+        S samples.  ``controlnet_conditioning_scale`` multiplies the residuals; ``control_guidance_start`` / ``_end`` is diffusers'
+        window in fractions of the executed steps - the steps outside it run without the ControlNet.  Composes with ``image`` /
+        ``mask_image``; not with ``sketch_image`` (the guidance gradient would need the ControlNet's backward) and not with a
+        SatMixin injector on the UNet.  With ``guidance_scale <= 1`` the ControlNet runs the S cond rows.
+        ``image``, ``strength``: img2img (diffusers' StableDiffusionImg2ImgPipeline) - the trajectory starts from the picture,
         re-noised to schedule entry ``start_step(num_inference_steps, strength)``, and runs the remaining steps.  ``image`` is a
         float tensor [1 or S, 3, height, width] in [-1, 1], a PIL image or a list of them of exactly width x height (both encoded
         by the VAE), or latents [1 or S, 4, height/8, width/8] used as given.  ``latents``, if given too, is the noise eps.
@@ -459,6 +508,8 @@ class AntiGradientPipeline:
             raise ValueError("`sketch_image` (LGP guidance) needs classifier-free guidance: pass guidance_scale > 1")
         check_generators(generator, S)
         self._check_latents_shape(latents, S, self.unet.in_channels, height, width)     # (ahead of the text encoder's device work)
+        cimg = self._check_control(controlnet, control_image, controlnet_conditioning_scale, control_guidance_start,
+                                   control_guidance_end, sketch_image, S, height, width)
         img = mask = None
         first = 0
         if image is not None:
@@ -478,6 +529,13 @@ class AntiGradientPipeline:
 
         net = self.unet.hip
         net.prepare_context(ehs)
+        control = None
+        if cimg is not None:
+            from ..controlnet import Control
+            cnet = controlnet.to(device).hip
+            cnet.prepare_context(ehs)
+            hint = cnet.hint_rows(cnet.embed(cimg), cimg.shape[0], ehs.shape[0])
+            control = Control(cnet, hint, controlnet_conditioning_scale, control_guidance_start, control_guidance_end)
         lgp = None
         target = None
         if sketch_image is not None:
@@ -493,7 +551,7 @@ class AntiGradientPipeline:
             cb = lambda i, t, x: callback(i, t, x) if i % callback_steps == 0 else None
         out = sampler.sample(lat, target, num_inference_steps, guidance_scale, 1.6, callback=cb, tables=tab, eta=eta,
                              generator=generator, classifier_free=do_classifier_free_guidance, init_latents=init, start_step=first,
-                             mask=mask)
+                             mask=mask, **({} if control is None else {"control": control}))
         self.last_aux = sampler.last_aux
         if lgp is not None:
             self.lgp_model._sync_running_stats()

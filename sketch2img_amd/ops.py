@@ -319,6 +319,34 @@ def conv3x3(X: torch.Tensor, Wp: torch.Tensor, rows: int, IH: int, IW: int, mode
     return out if part is None else (out, part)
 
 
+def conv3x3_small(X: torch.Tensor, Wp: torch.Tensor, B: int, IH: int, IW: int, stride: int = 1, out: Optional[torch.Tensor] = None, *,
+                  bias=None, silu: bool = False):
+    """The small-channel 3x3 convolution of the ControlNet hint encoder (skg_conv3x3_small_f16): X the fp32 NCHW picture
+    [B, 3, IH, IW] (contiguous, read as it is) or an fp16 [B*IH*IW, 16] view; Wp = packs.pack_conv_small (Cout 16 or 32); stride 1
+    or 2 (even IH, IW).  -> fp16 [B*OH*OW, Cout] with bias and, with silu, the SiLU applied in registers."""
+    if X.dtype == torch.float32:
+        if X.dim() != 4 or tuple(X.shape) != (B, 3, IH, IW) or not X.is_contiguous() or not X.is_cuda:
+            raise ValueError(f"conv3x3_small: a contiguous fp32 CUDA picture [{B}, 3, {IH}, {IW}] expected, got {tuple(X.shape)}")
+        Cin, ldx = 3, 0
+    else:
+        _f16(X)
+        if X.dim() != 2 or tuple(X.shape) != (B * IH * IW, 16):
+            raise ValueError(f"conv3x3_small: an fp16 [{B * IH * IW}, 16] view expected, got {tuple(X.shape)}")
+        Cin, ldx = 16, _ld(X)
+    _f16(Wp, bias, out)
+    Cout = Wp.shape[0]
+    if stride not in (1, 2) or (stride == 2 and (IH % 2 or IW % 2)):
+        raise ValueError(f"conv3x3_small: stride 1, or 2 on an even map, expected (stride {stride}, {IH} x {IW})")
+    assert Wp.is_contiguous() and Wp.shape[1] == (64 if Cin == 3 else 160) and (bias is None or bias.shape == (Cout,))
+    M = B * (IH // stride) * (IW // stride)
+    if out is None:
+        out = torch.empty(M, Cout, device=X.device, dtype=torch.float16)
+    assert out.shape == (M, Cout)
+    check(lib.skg_conv3x3_small_f16(_p(X), ldx, _p(Wp), _p(out), _ld(out), B, IH, IW, Cin, Cout, stride, _p(bias), int(silu), _stream()),
+          "skg_conv3x3_small_f16")
+    return out
+
+
 def conv3x3_sc(X: torch.Tensor, X2: torch.Tensor, Wcat: torch.Tensor, rows: int, IH: int, IW: int, out: Optional[torch.Tensor] = None, *,
                bias=None, relu: bool = False, gn_groups: Optional[int] = None, out_lo=None):
     """conv2 + conv_shortcut of a ResnetBlock as ONE implicit GEMM (skg_conv3x3_sc_f16): X [rows*IH*IW, Cin] the 3x3 input,

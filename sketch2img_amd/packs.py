@@ -34,6 +34,18 @@ def pack_conv(w: torch.Tensor, dev, cin_pad: int = 0, cout_pad: int = 0) -> torc
     return _h(p.reshape(p.shape[0], -1), dev)
 
 
+def pack_conv_small(w: torch.Tensor, dev) -> torch.Tensor:
+    """Pack of a 3x3 convolution with 3 or 16 input channels for ops.conv3x3_small (csrc/condembed.hip): [Cout, 3, 3, 3] ->
+    [Cout][16 tap slots][4] (channel 3 and the slots 9 .. 15 zero), [Cout, 16, 3, 3] -> [Cout][10 tap slots][16] (slot 9 zero)."""
+    co, ci = w.shape[:2]
+    if ci not in (3, 16) or tuple(w.shape[2:]) != (3, 3):
+        raise ValueError(f"pack_conv_small: a [Cout, 3 or 16, 3, 3] weight expected, got {tuple(w.shape)}")
+    slots, cp = (16, 4) if ci == 3 else (10, 16)
+    p = torch.zeros(co, slots, cp, dtype=torch.float32)
+    p[:, :9, :ci] = w.detach().float().cpu().permute(0, 2, 3, 1).reshape(co, 9, ci)
+    return _h(p.reshape(co, -1), dev)
+
+
 def pack_conv_wino(w: torch.Tensor, dev, dgrad: bool = False) -> torch.Tensor:
     """Winograd F(2x2, 3x3) weight pack of a 3x3 convolution [Cout, Cin, 3, 3] -> U [Cout, 16 * Cin] fp16: U = G g G^T per (cout, cin),
     formed in fp32 and rounded once; component c = 4 i + j at columns [c Cin, (c + 1) Cin) (ops.conv3x3_wino, csrc/wino.hip).

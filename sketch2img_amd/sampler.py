@@ -341,13 +341,16 @@ class HipSampler:
     @torch.no_grad()
     def step(self, x: torch.Tensor, noise: torch.Tensor, target: Optional[torch.Tensor], tab,
              i: int, guidance_scale: float, beta: float, want_eps: bool = False, eta: float = 0.0, generator=None,
-             z: Optional[torch.Tensor] = None, classifier_free: bool = True):
+             z: Optional[torch.Tensor] = None, classifier_free: bool = True, control=None):
         """One iteration of the loop for S samples.  x fp32 [S,4,h,w] on the device -> x_{t-1}.
         eta > 0 (DDIM only; DPM-Solver++ has no eta): the step adds sigma_t z, z = `z` if given (fp32, x's shape, on the device:
         the hipGraph path's static slice) else one draw_noise(x.shape, generator) after the UNet evaluation.  The stochastic
         DPM-Solver++ (tab.algorithm_type "sde-dpmsolver++") takes its z the same way, on every step, the last one included.
         classifier_free=False (the reference's guidance_scale <= 1): the UNet evaluates the S cond rows alone (prepare_context got S
-        rows) and the step kernels take that one tensor as both CFG operands with g = 1 - u + 1 (u - u) is u exactly."""
+        rows) and the step kernels take that one tensor as both CFG operands with g = 1 - u + 1 (u - u) is u exactly.
+        control (a controlnet.Control whose net has the context of the same rows): the ControlNet trunk runs on the UNet's input -
+        all rows, with the control's hint - and its residuals join the UNet's skips and mid block (HipUNet.forward(control=)).
+        Not on a guided step.  Whether a step lies in the control's window is the caller's decision (sample)."""
         S, _, h, w = x.shape
         hw = h * w
         T = len(tab.timesteps)
@@ -355,6 +358,8 @@ class HipSampler:
         guided = guided_step(i, T) and target is not None and self.lgp is not None
         if guided and not classifier_free:
             raise ValueError("LGP guidance differentiates the cond half of a CFG-doubled batch: classifier_free=False has none")
+        if guided and control is not None:
+            raise ValueError("a ControlNet on a guided step: the guidance gradient would need the trunk's backward")
         x32 = ops.nchw_to_nhwc((torch.cat([x, x]) if classifier_free else x).contiguous(), CIN_PAD)
         stash = Stash() if guided else None
         # (the two CFG halves of x32 are the same latents: the text-independent front of the UNet runs once)
@@ -383,8 +388,13 @@ class HipSampler:
                 branch["done"] = torch.cuda.Event()
                 branch["done"].record(self._side)
 
-        eps, taps = self.unet.forward(x32, t, 2 * S if classifier_free else S, h, stash, want_taps=guided,
-                                      shared_input=self.share_cfg_prefix and classifier_free, on_taps=on_taps if fork else None, W=w)
+        rows = 2 * S if classifier_free else S
+        ctl = None
+        if control is not None:
+            ctl = (control.net.forward(x32, t, rows, h, w, control.hint), control.net.zero_convs, control.scale)
+        eps, taps = self.unet.forward(x32, t, rows, h, stash, want_taps=guided,
+                                      shared_input=self.share_cfg_prefix and classifier_free, on_taps=on_taps if fork else None, W=w,
+                                      **({} if ctl is None else {"control": ctl}))
         fork = fork and "done" in branch          # (a forward that never reached the hook runs the branch in line)
         eu, ec, lo_off = ops.eps_halves(eps, S, hw)      # (accuracy mode: eps is a (hi, lo) pair, combined in fp32 by the step kernel)
         if not classifier_free:
@@ -428,8 +438,11 @@ class HipSampler:
                callback: Optional[Callable[[int, int, torch.Tensor], None]] = None,
                tables=None, graphs: Optional[bool] = None, eta: float = 0.0, generator=None,
                classifier_free: bool = True, init_latents: Optional[torch.Tensor] = None, start_step: int = 0,
-               mask: Optional[torch.Tensor] = None) -> torch.Tensor:
-        """eta, generator: DDIM's stochastic step (DDIMTables.coeffs_eta, draw_noise); a generator list holds one per sample.
+               mask: Optional[torch.Tensor] = None, control=None) -> torch.Tensor:
+        """control (controlnet.Control): ControlNet conditioning on the executed steps n of N = T - start_step that lie in its window
+        (diffusers' control_guidance_start / _end: not n / N < start, not (n + 1) / N > end); the other steps make the uncontrolled
+        launches.  Not together with a sketch target, nor with an injector on the UNet.
+        eta, generator: DDIM's stochastic step (DDIMTables.coeffs_eta, draw_noise); a generator list holds one per sample.
         DPM-Solver++ ignores eta; its "sde-dpmsolver++" tables draw from `generator` in the same way, once per step.
         classifier_free=False: no CFG - the context prepared on the UNet holds the S cond rows - and no LGP guidance.
         init_latents (fp32 [S,4,h,w]), start_step: img2img.  latents0 is then the noise draw eps, the trajectory starts at
@@ -466,6 +479,11 @@ class HipSampler:
         if not classifier_free and target is not None:
             raise ValueError("classifier_free=False (guidance_scale <= 1) cannot be combined with a sketch target: the LGP guidance "
                              "differentiates the cond half of a CFG-doubled batch (the reference fails in this mode too)")
+        if control is not None and target is not None:
+            raise ValueError("ControlNet conditioning cannot be combined with a sketch target: the LGP guidance gradient would need "
+                             "the ControlNet trunk's backward")
+        if control is not None and self.unet.inject is not None:
+            raise NotImplementedError("ControlNet conditioning together with a SatMixin injector on the UNet is not implemented")
         if draws_noise(tab, eta):
             check_generators(generator, latents0.shape[0])
         x = latents0.to(dev, torch.float32).contiguous()
@@ -484,16 +502,20 @@ class HipSampler:
                              start_step, T)
             x = ops.latent_renoise(init, noise, *tab.level(start_step))      # scheduler.add_noise; `noise` stays the draw eps
         self.unet.prepare_timesteps(tab.timesteps.tolist())
+        if control is not None:
+            control.net.prepare_timesteps(tab.timesteps.tolist())
         self.last_aux = []
         self.reset_history()
         if (self.use_graphs if graphs is None else graphs) and callback is None:
             x = self._sample_graphed(x, tgt, tab, guidance_scale, beta, eta, generator, classifier_free,
-                                     noise=None if init is None else noise, init=init, mask=m, start=start_step)
+                                     noise=None if init is None else noise, init=init, mask=m, start=start_step,
+                                     **({} if control is None else {"control": control}))
         else:
             steps = tab.timesteps.tolist()
             for n, i in enumerate(range(start_step, T)):
+                ckw = {"control": control} if control is not None and control.active(n, T - start_step) else {}
                 x, _, aux = self.step(x, noise, tgt, tab, i, guidance_scale, beta, eta=eta, generator=generator,
-                                      classifier_free=classifier_free)
+                                      classifier_free=classifier_free, **ckw)
                 if m is not None:
                     ops.latent_renoise(init, noise, *tab.level(i + 1), x=x, mask=m)
                 self.last_aux.append(aux)
@@ -505,7 +527,7 @@ class HipSampler:
     # ------------------------------------------------------------------------------------------ hipGraph replay
     def _sample_graphed(self, x: torch.Tensor, tgt: Optional[torch.Tensor], tab, guidance_scale: float, beta: float,
                         eta: float = 0.0, generator=None, classifier_free: bool = True, noise: Optional[torch.Tensor] = None,
-                        init: Optional[torch.Tensor] = None, mask: Optional[torch.Tensor] = None, start: int = 0):
+                        init: Optional[torch.Tensor] = None, mask: Optional[torch.Tensor] = None, start: int = 0, control=None):
         """Captures (first call for a given schedule / shape) and replays one hipGraph per step.  Every launch of a
         step goes to torch's current stream, which is the capturing stream inside ``torch.cuda.graph``; nothing on the
         step path allocates outside torch's (graph-private) pool or synchronises with the host.
@@ -515,15 +537,25 @@ class HipSampler:
         before the first replay.
         img2img (init given: x is the start a*init + s*eps already, `noise` the draw eps, `start` the first entry): only the
         executed steps start .. T-1 are captured and only their noise is drawn; with a mask each captured step ends with the blend,
-        which reads the set's static `init` and `mask` buffers - refilled before each replay like `ts` - and `ns`, which holds eps."""
+        which reads the set's static `init` and `mask` buffers - refilled before each replay like `ts` - and `ns`, which holds eps.
+        control: the ControlNet launches of the steps inside the control's window are captured with the rest; they read the set's
+        static hint buffer (refilled before each replay: another control image of the same size replays the same set); the key
+        holds "controlled", the scale, the window and the hint's shape, and the set is valid only for the same engine and the
+        text context it was captured with."""
         T = len(tab.timesteps)
         inj = self.unet.inject
         key = graph_key(tab, x.shape, tgt is None, guidance_scale, beta, self.share_cfg_prefix, eta, classifier_free, start,
                         mask is not None)
+        if control is not None:      # (an uncontrolled call keeps the key - and the launches - it had)
+            key = key + control.key()
         if noise is None:
             noise = x                                             # a trajectory from pure noise: modules/pipeline.py:75
         zall = torch.stack([draw_noise(x.shape, generator, x.device) for _ in range(start, T)]) if draws_noise(tab, eta) else None
-        step_kw = lambda zs, i: dict(eta=eta, z=None if zs is None else zs[i - start], classifier_free=classifier_free)
+        def step_kw(zs, i, ctl=None):
+            kw = dict(eta=eta, z=None if zs is None else zs[i - start], classifier_free=classifier_free)
+            if ctl is not None and ctl.active(i - start, T - start):
+                kw["control"] = ctl
+            return kw
 
         def blend(xn, ent_init, ent_mask, ns, i):
             if ent_mask is not None:
@@ -534,7 +566,8 @@ class HipSampler:
         # the very same ones - ids alone could be recycled after the old objects were freed.
         ent = self._graphs.get(key)
         if ent is not None and not (ent["ctx"] is self.unet.ctx and ent["inject"] is inj and
-                                    (inj is None or (ent["per_image"] is inj.per_image and ent["scale"] == inj.scale))):
+                                    (inj is None or (ent["per_image"] is inj.per_image and ent["scale"] == inj.scale)) and
+                                    (control is None or (ent["cnet"] is control.net and ent["cctx"] is control.net.ctx))):
             del self._graphs[key]          # stale: prompt, sketch or scale changed since the capture
             ent = None
         if ent is not None:
@@ -550,6 +583,7 @@ class HipSampler:
             zs = None if zall is None else zall.clone()
             ins = None if mask is None else torch.empty_like(init)
             ms = None if mask is None else torch.empty_like(mask)
+            cs = None if control is None else control.with_hint(control.hint.clone())      # (the set's static hint buffer)
             # one eager pass first: the per-timestep bias vectors and every lazily built per-image buffer must exist before
             # a capture.  The split-K workspace of the captured launches is the set's own (allocated above, outside the
             # capture); scratch buffers first touched inside the capture come from the set's private pool.
@@ -563,7 +597,7 @@ class HipSampler:
             self._x0_before, self._seen = x0b, 0
             w = xs.clone()
             for i in range(start, T):
-                w, _, _ = self.step(w, ns, ts, tab, i, guidance_scale, beta, **step_kw(zs, i))
+                w, _, _ = self.step(w, ns, ts, tab, i, guidance_scale, beta, **step_kw(zs, i, cs))
                 blend(w, ins, ms, ns, i)
             if saved is not None:       # the warm-up pass is not part of the trajectory: undo its BatchNorm side effects
                 for l in range(4):
@@ -576,7 +610,7 @@ class HipSampler:
             for i in range(start, T):
                 g = torch.cuda.CUDAGraph()
                 with torch.cuda.graph(g, pool=pool), ops.private_buffers(owner):
-                    xn, _, aux = self.step(xs, ns, ts, tab, i, guidance_scale, beta, **step_kw(zs, i))
+                    xn, _, aux = self.step(xs, ns, ts, tab, i, guidance_scale, beta, **step_kw(zs, i, cs))
                     blend(xn, ins, ms, ns, i)
                     xs.copy_(xn)
                 graphs.append(g)
@@ -585,13 +619,16 @@ class HipSampler:
                 self.lgp.num_batches_tracked = list(saved[2])
             ent = self._graphs[key] = dict(graphs=graphs, auxs=auxs, xs=xs, ns=ns, ts=ts, x0b=x0b, zs=zs, init=ins, mask=ms, owner=owner,
                                            ctx=self.unet.ctx, inject=inj, per_image=None if inj is None else inj.per_image,
-                                           scale=None if inj is None else inj.scale)
+                                           scale=None if inj is None else inj.scale, control=cs,
+                                           cnet=None if control is None else control.net, cctx=None if control is None else control.net.ctx)
         ent["xs"].copy_(x); ent["ns"].copy_(noise)
         if tgt is not None:
             ent["ts"].copy_(tgt)
         if mask is not None:
             ent["init"].copy_(init); ent["mask"].copy_(mask)
         ent["x0b"].zero_()
+        if control is not None:
+            ent["control"].hint.copy_(control.hint)
         if zall is not None:
             ent["zs"].copy_(zall)
         S = x.shape[0]

@@ -119,7 +119,60 @@ def _unet_state_dict(cfg: UNetConfig, seed: int, shapes) -> Dict[str, torch.Tens
     return sd
 
 
-LGP_LIN, LGP_BN, LGP_HIDDEN = (0, 3, 6, 9, 12), (2, 5, 8, 11), (512, 256, 128, 64)
+# ------------------------------------------------------------------------- ControlNet (controlnet.py)
+CONTROLNET_WEIGHT_SEED = 20261021
+COND_EMBED_CHANNELS = (16, 32, 96, 256)      # diffusers' conditioning_embedding_out_channels default
+
+
+def controlnet_num_residuals(cfg: UNetConfig) -> int:
+    """n: the skips of the UNet's down path (conv_in's output, every layer's, every downsampler's) - one zero convolution each."""
+    nb = len(cfg.block_out_channels)
+    return 1 + sum(cfg.layers_per_block + (1 if i < nb - 1 else 0) for i in range(nb))
+
+
+def controlnet_residual_channels(cfg: UNetConfig) -> Tuple[int, ...]:
+    """Channels of the n skips in production order."""
+    boc, nb = cfg.block_out_channels, len(cfg.block_out_channels)
+    ch = [boc[0]]
+    for i, c in enumerate(boc):
+        ch += [c] * (cfg.layers_per_block + (1 if i < nb - 1 else 0))
+    return tuple(ch)
+
+
+def controlnet_param_shapes(cfg: UNetConfig, cond_channels: Tuple[int, ...] = COND_EMBED_CHANNELS,
+                            conditioning_channels: int = 3) -> "OrderedDict[str, tuple]":
+    """diffusers ControlNetModel state_dict keys -> shapes: the UNet's encoder (conv_in, time_embedding, down_blocks, mid_block),
+    the hint encoder controlnet_cond_embedding (conv_in, blocks.0 .. 5 - alternately stride 1 and 2 -, conv_out) and the zero
+    convolutions controlnet_down_blocks.0 .. n-1 / controlnet_mid_block (1x1)."""
+    if len(cond_channels) != 4:
+        raise ValueError(f"conditioning_embedding_out_channels: four entries expected, got {tuple(cond_channels)}")
+    s: "OrderedDict[str, tuple]" = OrderedDict(
+        (k, v) for k, v in unet_param_shapes(cfg).items() if k.split(".")[0] in ("conv_in", "time_embedding", "down_blocks", "mid_block"))
+    e, cc = "controlnet_cond_embedding", tuple(cond_channels)
+    s[e + ".conv_in.weight"] = (cc[0], conditioning_channels, 3, 3); s[e + ".conv_in.bias"] = (cc[0],)
+    for i in range(3):
+        s[f"{e}.blocks.{2 * i}.weight"] = (cc[i], cc[i], 3, 3); s[f"{e}.blocks.{2 * i}.bias"] = (cc[i],)
+        s[f"{e}.blocks.{2 * i + 1}.weight"] = (cc[i + 1], cc[i], 3, 3); s[f"{e}.blocks.{2 * i + 1}.bias"] = (cc[i + 1],)
+    s[e + ".conv_out.weight"] = (cfg.block_out_channels[0], cc[3], 3, 3); s[e + ".conv_out.bias"] = (cfg.block_out_channels[0],)
+    for k, c in enumerate(controlnet_residual_channels(cfg)):
+        s[f"controlnet_down_blocks.{k}.weight"] = (c, c, 1, 1); s[f"controlnet_down_blocks.{k}.bias"] = (c,)
+    cm = cfg.block_out_channels[-1]
+    s["controlnet_mid_block.weight"] = (cm, cm, 1, 1); s["controlnet_mid_block.bias"] = (cm,)
+    return s
+
+
+def controlnet_state_dict(cfg: UNetConfig, seed: int = CONTROLNET_WEIGHT_SEED,
+                          cond_channels: Tuple[int, ...] = COND_EMBED_CHANNELS) -> Dict[str, torch.Tensor]:
+    """Seeded synthetic ControlNet weights by the UNet's recipe.  The "zero" convolutions are NOT zero (a trained net's are not
+    either): a control that did nothing could not be told from one that was never applied."""
+    shapes = controlnet_param_shapes(cfg, cond_channels)
+    if sum(math.prod(s) for s in shapes.values()) > 100_000_000:
+        tag = hashlib.sha256(repr((cfg, seed, sorted(shapes.items()))).encode()).hexdigest()[:16]
+        return _disk_cached(f"controlnet_{tag}", lambda: _unet_state_dict(cfg, seed, shapes))
+    return _unet_state_dict(cfg, seed, shapes)
+
+
+LGP_LIN, LGP_BN, LGP_HIDDEN =(0, 3, 6, 9, 12), (2, 5, 8, 11), (512, 256, 128, 64)
 
 
 def lgp_state_dict(input_dim: int = 9320, output_dim: int = 4, seed: int = WEIGHT_SEED,

@@ -842,13 +842,25 @@ class HipUNet:
             raise NotImplementedError(f"non-square latents {sz}: both sides must be multiples of {f}")
 
     # ------------------------------------------------------------------ forward
-    def _conv_gn(self, x, w, bkey: str, rows: int, sz: Tuple[int, int], mode: int, out):
+    def _conv_gn(self, x, w, bkey: str, rows: int, sz: Tuple[int, int], mode: int, out, residual=None):
         """A convolution (x, w: see _operand) whose output may leave GroupNorm partial sums behind: -> (out, the sums or None).  out: an
         fp16 view, a Pair (the pair epilogue), or None (a fresh fp16 tensor); the sums come with it where the level of the OUTPUT takes
-        its statistics from the producers (_gn_from_producer)."""
+        its statistics from the producers (_gn_from_producer).  residual: added in the epilogue (a ControlNet trunk's hint)."""
         osz = _half(sz) if mode == ops.CONV_S2 else sz
         gn = (osz[0] * osz[1], self.cfg.norm_groups) if self._gn_from_producer(rows, osz[0] * osz[1], w.shape[0]) else None
-        return _produce("conv3x3", x, w, rows, *sz, mode, out=out, bias=self.W[bkey], gn=gn)
+        return _produce("conv3x3", x, w, rows, *sz, mode, out=out, bias=self.W[bkey], gn=gn, residual=residual)
+
+    def _add_control(self, dst, feat: torch.Tensor, zero_conv: Tuple[torch.Tensor, torch.Tensor], scale: float):
+        """dst += scale * (feat . Wz^T + b): one zero convolution of a ControlNet, scaled by the conditioning scale and added to a skip
+        (or to the mid block's output) IN PLACE - one GEMM launch whose residual is its own output, dst being a strided view inside a
+        concat buffer or a Pair of them (the pair epilogue; feat stays a plain fp16 operand).  Safe: every epilogue of gemm.hip /
+        gemm2.hip / gemm8.hip, the split-K reduce included, reads a residual element in the thread that then writes that element, and
+        no thread reads an element another one writes (ControlNet)."""
+        Wz, b = zero_conv
+        if feat.shape[0] != _hi(dst).shape[0] or Wz.shape != (_hi(dst).shape[1], feat.shape[1]):
+            raise ValueError(f"control residual {tuple(feat.shape)} / zero convolution {tuple(Wz.shape)} do not fit the skip "
+                             f"{tuple(_hi(dst).shape)}: the ControlNet was built for another UNet config, batch or latent size")
+        _produce("gemm", feat, Wz, out=dst, bias=b, residual=dst, alpha=float(scale))
 
     def _upsample(self, p: str, h, rows: int, sz: Tuple[int, int], out):
         """The nearest-2x upsampler convolution `p` of an up block: h (fp16: the block lies in the plain zone, or a Pair) -> out (the
@@ -877,7 +889,8 @@ class HipUNet:
 
     def forward(self, x32: torch.Tensor, t, rows: int, H: int, stash: Optional[Stash] = None,
                 want_taps: bool = True, want_eps: bool = True, down_only: bool = False, shared_input: bool = False,
-                on_taps: Optional[Callable] = None, W: Optional[int] = None, diff_from: Optional[int] = None):
+                on_taps: Optional[Callable] = None, W: Optional[int] = None, diff_from: Optional[int] = None,
+                through_mid: bool = False, hint: Optional[torch.Tensor] = None, control=None):
         """x32: fp16 [rows*H*W, 32] (latent channels zero-padded; W defaults to H).  Returns (eps [rows*H*W, 8] or None,
         taps: list of 9 (tensor [rows*s*s, C], s)) - on a non-square map (tensor [rows*sh*sw, C], (sh, sw)).
 
@@ -904,6 +917,18 @@ class HipUNet:
         the trainers' batch (backward_eps then differentiates all of them); odd row counts are fine.  An explicit value also selects
         the split / fused stashing launches whatever the parity of rows.  Not with shared_input (ValueError).
 
+        through_mid (with down_only; the walk of a ControlNet trunk, controlnet.HipControlNet): the down path continued through
+        mid_block -> (the list of all skips in production order, tensors [rows*sh*sw, C]; the mid block's output).  hint (down_only
+        walks): fp16 [rows*H*W, C0], added to conv_in's output in its epilogue - diffusers' `sample = conv_in(sample) + cond`.
+
+        control = (features, zero_convs, scale): the residuals of a ControlNet - features the n + 1 tensors a through_mid walk
+        returns (skips, then mid), zero_convs n + 1 pairs (weight [C, C], bias [C]) fp16, the last for the mid block.  Behind
+        mid_block every skip k becomes skip_k + scale (F_k Wz_k^T + b_k) and the mid block's output the same with the last pair
+        (_add_control: one in-place GEMM each).  The adds wait for mid_block because the last skip is also mid_block's INPUT (one
+        buffer; diffusers adds to copies), which the control must not reach.  The producers' GroupNorm partial sums of the skips
+        describe them before the add and are dropped: the up path's norm1 takes its own statistics.  Not with a stash or taps (the
+        backward would need the trunk's).
+
         One walk for both modes.  The blocks of the `pair_levels` outermost resolution levels (none in the default mode) carry the
         residual stream as (hi, lo) pairs: the same graph, the same kernels for every contraction, pair-aware epilogues / norms
         (skg_*_hilo), the same GroupNorm statistics from the producers' epilogues and the same shared CFG front; eps then is a pair
@@ -917,6 +942,13 @@ class HipUNet:
             if not 0 <= int(diff_from) < rows:
                 raise ValueError(f"diff_from = {diff_from}: a row index below rows = {rows} expected")
             diff_from = int(diff_from)
+        if through_mid and not down_only:
+            raise ValueError("through_mid continues the down_only walk: pass down_only=True with it")
+        if hint is not None and not down_only:
+            raise ValueError("hint: the input of a ControlNet trunk's walk (down_only=True, through_mid=True)")
+        if control is not None and (down_only or stash is not None or want_taps):
+            raise ValueError("control: a plain eps evaluation (no down_only, no stash, want_taps=False) - the guidance gradient and "
+                             "the taps' consumers would need the ControlNet trunk's backward")
         sz = (H, H if W is None else W)
         cfg, W = self.cfg, self.W
         assert self.ctx is not None and self.ctx["rows"] == rows, "call prepare_context first"
@@ -961,7 +993,8 @@ class HipUNet:
             h, hp = tr("down_blocks.0.attentions.0", h1, rows, cur, cfg.num_heads[0], stash, out=cats.skip_slot(boc[0], cur),
                        xpart=hp1, want_part=0 < lpb - 1, shared=True, x_full=x_full)
         else:
-            h, hp = self._conv_gn(x32, W["conv_in.weight"], "conv_in.bias", rows, sz, ops.CONV_S1, cats.skip_slot(boc[0], sz))
+            h, hp = self._conv_gn(x32, W["conv_in.weight"], "conv_in.bias", rows, sz, ops.CONV_S1, cats.skip_slot(boc[0], sz),
+                                  residual=hint)
         cats.push(h, hp)
         taps_down = []
         for i in range(nb):
@@ -987,7 +1020,7 @@ class HipUNet:
                 cats.push(h, hp)
             if i < 3:
                 taps_down.append((_hi(h), _side(cur)))
-        if down_only:
+        if down_only and not through_mid:
             # modules/sketch_encoder.py:39-98: the forward stops after the down path and returns the per-block
             # tuples of residual samples ((tensor [rows*s*s, C], s), ...) - what SatMixin.set_res_samples consumes
             # (on a non-square map: (tensor [rows*sh*sw, C], (sh, sw)))
@@ -1003,8 +1036,18 @@ class HipUNet:
         tap_r0 = (_hi(h), _side(cur))
         h, hp = tr("mid_block.attentions.0", h, rows, cur, cfg.num_heads[-1], stash, xpart=hp, want_part=True)
         tap_at = (_hi(h), _side(cur))
-        h, _ = res("mid_block.resnets.1", h, rows, cur, tb, stash, out=cats.h_slot(0), xpart=hp)
+        h, _ = res("mid_block.resnets.1", h, rows, cur, tb, stash, out=None if down_only else cats.h_slot(0), xpart=hp)
+        if down_only:
+            return list(cats.skips), h
         tap_r1 = (_hi(h), _side(cur))
+        if control is not None:
+            feats, zero_convs, cscale = control
+            if len(feats) != len(cats.skips) + 1 or len(zero_convs) != len(feats):
+                raise ValueError(f"control: {len(cats.skips) + 1} residuals and zero convolutions expected, got {len(feats)} / {len(zero_convs)}")
+            for k, skip in enumerate(cats.skips):
+                self._add_control(skip, feats[k], zero_convs[k], cscale)
+                cats.parts[k] = None
+            self._add_control(h, feats[-1], zero_convs[-1], cscale)
         hp = None
         taps_up = []
         rev_heads = tuple(reversed(cfg.num_heads))
