@@ -18,6 +18,7 @@ SURVEY Q3) with one sample's 2*h*h rows as the batch, and updates running stats 
 """
 from __future__ import annotations
 
+import contextlib
 from typing import Dict, List, Optional, Sequence, Tuple
 
 import torch
@@ -121,6 +122,19 @@ class HipLGP:
             grads.append(ops.gemm(dP, self.W0T[off:off + C]))
             off += C
         return grads, loss
+
+    @contextlib.contextmanager
+    def preserving_running_stats(self):
+        """Puts the BatchNorm running statistics and batch counters back on exit as they were on entry: for a pass that is not
+        part of a trajectory (the sampler's warm-up pass and captures of a new hipGraph set)."""
+        stats = self.running_mean + self.running_var
+        saved, tracked = [r.clone() for r in stats], list(self.num_batches_tracked)
+        try:
+            yield
+        finally:
+            for r, s in zip(stats, saved):
+                r.copy_(s)
+            self.num_batches_tracked = tracked
 
     def state_dict(self) -> Dict[str, torch.Tensor]:
         """Running statistics in the reference's checkpoint key layout (the only mutable state)."""

@@ -551,7 +551,7 @@ class AntiGradientPipeline:
             cb = lambda i, t, x: callback(i, t, x) if i % callback_steps == 0 else None
         out = sampler.sample(lat, target, num_inference_steps, guidance_scale, 1.6, callback=cb, tables=tab, eta=eta,
                              generator=generator, classifier_free=do_classifier_free_guidance, init_latents=init, start_step=first,
-                             mask=mask, **({} if control is None else {"control": control}))
+                             mask=mask, control=control)
         self.last_aux = sampler.last_aux
         if lgp is not None:
             self.lgp_model._sync_running_stats()

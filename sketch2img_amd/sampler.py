@@ -9,13 +9,19 @@ indexing); everything that touches a latent runs in HIP kernels.
 
 A batch of S samples is S independent B = 1 trajectories of the reference (which crashes for B > 1:
 SURVEY Q1): alpha, the BatchNorm statistics and the loss are per sample.
+
+A scheduler (DDIMTables, DPMTables) owns its step: key() is what of it reaches kernel arguments, update() computes its coefficients
+and issues its ops.cfg_*_step call, on an explicit History where the method is multistep.  One StepPlan per sample() call holds the
+call's constants, and StepPlan.key(tab, shape) names the GraphSet that replays them.  HipSampler._run_step - step with the control
+inside its window, then the masked blend - is what the eager loop, a new set's warm-up pass and its captures all run.
 """
 from __future__ import annotations
 
+import contextlib
 import logging
 import math
 import os
-from dataclasses import dataclass
+from dataclasses import dataclass, fields
 from typing import Callable, List, Optional, Sequence
 
 import numpy as np
@@ -61,12 +67,45 @@ def draw_noise(shape: Sequence[int], generator, device) -> torch.Tensor:
 
 
 @dataclass
+class History:
+    """DPM-Solver++'s multistep state: the previous x0 prediction (the step kernel updates it in place) and the number of model
+    outputs it has seen, which decides the order of the next update."""
+    x0: torch.Tensor
+    seen: int = 0
+
+
+def _fingerprint(acp: torch.Tensor) -> tuple:
+    """An alphas_cumprod table in a key: two schedulers may share timesteps and differ in betas."""
+    return int(acp.numel()), float(acp.double().sum()), float(acp[0]), float(acp[-1])
+
+
+@dataclass
 class DDIMTables:
     alphas_cumprod: torch.Tensor      # (num_train,) fp32 CPU
     final_alpha_cumprod: float
     timesteps: np.ndarray             # (T,) int64 descending
     ratio: int
     v_prediction: bool = False        # scheduler config prediction_type == "v_prediction" (SD2.1-768): the UNet output is v
+    has_eta = True                    # (not a field) eta > 0 selects the stochastic step
+
+    def key(self) -> tuple:
+        """Everything of the schedule that ends up in kernel arguments (every field; tests/test_host_sampler_plan.py holds it to that)."""
+        return (type(self).__name__, tuple(int(t) for t in self.timesteps), bool(self.v_prediction), float(self.final_alpha_cumprod),
+                int(self.ratio)) + _fingerprint(self.alphas_cumprod)
+
+    def noisy(self, eta: float) -> bool:
+        return eta > 0.0
+
+    def new_history(self, x: torch.Tensor) -> None:
+        return None                   # a one-step method
+
+    def update(self, i: int, eu, ec, x, z, history, S: int, hw: int, g: float, want_eps: bool, lo_off: int, eta: float):
+        """The scheduler step of entry i on the UNet's eps halves (ops.eps_halves) -> what the ops.cfg_*_step call returns."""
+        t = int(self.timesteps[i])
+        if eta > 0.0:
+            return ops.cfg_ddim_eta_step(eu, ec, x, z, S, hw, g, self.coeffs_eta(t, eta), want_eps, lo_off=lo_off,
+                                         v_prediction=self.v_prediction)
+        return ops.cfg_ddim_step(eu, ec, x, S, hw, g, self.coeffs(t), want_eps, lo_off=lo_off, v_prediction=self.v_prediction)
 
     @staticmethod
     def make(num_inference_steps: int, num_train_timesteps: int = 1000, beta_start: float = 0.00085,
@@ -194,9 +233,36 @@ class DPMTables:
         return DPMTables(acp, al, sg, torch.log(al) - torch.log(sg), ts, lower_order_final, solver_order, v_prediction,
                          bool(use_karras_sigmas), algorithm_type, sigmas)
 
+    has_eta = False                           # (not a field) diffusers' prepare_extra_step_kwargs drops eta for this scheduler
+
     @property
     def stochastic(self) -> bool:
         return self.algorithm_type == "sde-dpmsolver++"
+
+    def key(self) -> tuple:
+        """Everything of the schedule that ends up in kernel arguments: the sigma spacing with its per-step sigmas and the
+        algorithm type (ODE or SDE step kernel) included; alpha_t, sigma_t and lambda_t are functions of alphas_cumprod."""
+        return (type(self).__name__, tuple(int(t) for t in self.timesteps), bool(self.v_prediction), int(self.solver_order),
+                bool(self.lower_order_final), bool(self.use_karras_sigmas), self.algorithm_type,
+                None if self.sigmas is None else tuple(float(s) for s in self.sigmas)) + _fingerprint(self.alphas_cumprod)
+
+    def noisy(self, eta: float) -> bool:
+        return self.stochastic
+
+    def new_history(self, x: torch.Tensor) -> History:
+        return History(torch.zeros_like(x))
+
+    def update(self, i: int, eu, ec, x, z, history: History, S: int, hw: int, g: float, want_eps: bool, lo_off: int, eta: float):
+        """The scheduler step of entry i (DDIMTables.update); `history` moves on by one model output."""
+        order = self.order(i, history.seen)
+        if self.stochastic:
+            res = ops.cfg_dpmpp2m_sde_step(eu, ec, x, z, history.x0, S, hw, g, self.coeffs_sde(i, order), want_eps, lo_off=lo_off,
+                                           v_prediction=self.v_prediction)
+        else:
+            res = ops.cfg_dpmpp2m_step(eu, ec, x, history.x0, S, hw, g, self.coeffs(i, order), want_eps, lo_off=lo_off,
+                                       v_prediction=self.v_prediction)
+        history.seen = min(history.seen + 1, self.solver_order)
+        return res
 
     def order(self, i: int, seen: int) -> int:
         """Update order of step i after `seen` model outputs (lower order at the start, and on the final step of
@@ -289,27 +355,109 @@ def guided_step(i: int, T: int) -> bool:
     return not (i > 0.5 * T)            # modules/pipeline.py:89-92,108
 
 
+@dataclass(frozen=True)
+class StepPlan:
+    """The constants of one sample() call.  Every field is baked into the kernel arguments of a captured step, so every field is in
+    the key: the guidance constants, the effective eta (the step kernel and its sigma / c_dir), whether the UNet runs the CFG-doubled
+    batch or the cond rows alone, the entry the executed steps start at, whether each of them ends with the masked blend, whether
+    the CFG halves share the UNet's front, whether there is no sketch target, and the ControlNet conditioning."""
+    guidance_scale: float
+    beta: float
+    eta: float
+    classifier_free: bool
+    start: int
+    masked: bool
+    share_cfg_prefix: bool
+    unguided: bool
+    control: Optional[object] = None          # a controlnet.Control; in the key as Control.key()
+
+    def key(self, tab, shape) -> tuple:
+        """The key of the graph set of this call: the plan, the schedule (tab.key()) and the latents' shape.  A call without a
+        control adds nothing for it, so uncontrolled keys do not depend on the ControlNet feature."""
+        key = tab.key() + (tuple(shape),)
+        for f in fields(self):
+            v = getattr(self, f.name)
+            key += (v,) if f.name != "control" else () if v is None else v.key()
+        return key
+
+
 def graph_key(tab, shape, unguided: bool, guidance_scale: float, beta: float, share_cfg_prefix: bool, eta: float = 0.0,
               classifier_free: bool = True, start_step: int = 0, masked: bool = False) -> tuple:
-    """Everything that is baked into the kernel arguments of a captured set of steps: the schedule (timesteps AND the table values
-    the per-step coefficients come from - two schedulers may share timesteps and differ in betas / final alpha), the prediction
-    type, shapes, the guidance constants (v_prediction was missing -> a stale graph would have been replayed), eta (the
-    step kernel and its sigma / c_dir), whether the UNet runs the CFG-doubled batch or the cond rows alone, and for DPM-Solver++
-    the sigma spacing with its per-step sigmas and the algorithm type (ODE or SDE step kernel); for img2img the entry the captured
-    steps start at and whether each of them ends with the masked blend."""
-    acp = tab.alphas_cumprod
-    sigmas = getattr(tab, "sigmas", None)
-    return (type(tab).__name__, tuple(int(t) for t in tab.timesteps), tuple(shape), bool(unguided),
-            float(guidance_scale), float(beta), bool(share_cfg_prefix), bool(tab.v_prediction),
-            float(getattr(tab, "final_alpha_cumprod", 0.0)), int(acp.numel()), float(acp.double().sum()), float(acp[0]), float(acp[-1]),
-            getattr(tab, "solver_order", 0), getattr(tab, "lower_order_final", None), float(eta), bool(classifier_free),
-            bool(getattr(tab, "use_karras_sigmas", False)), getattr(tab, "algorithm_type", None),
-            None if sigmas is None else tuple(float(s) for s in sigmas), int(start_step), bool(masked))
+    """StepPlan.key of an uncontrolled call with these constants."""
+    return StepPlan(float(guidance_scale), float(beta), float(eta), bool(classifier_free), int(start_step), bool(masked),
+                    bool(share_cfg_prefix), bool(unguided)).key(tab, shape)
 
 
 def draws_noise(tab, eta: float) -> bool:
     """Whether every step of a trajectory adds caller-drawn noise: DDIM with eta > 0, or the stochastic DPM-Solver++."""
-    return bool(getattr(tab, "stochastic", False)) or (isinstance(tab, DDIMTables) and eta > 0.0)
+    return tab.noisy(eta)
+
+
+@dataclass
+class GraphSet:
+    """One captured schedule: a hipGraph per executed step, the static buffers the captured launches read and write, and what else
+    they point at - the text context's K / V (prepare_context builds a NEW dict per prompt), the injector's per-image K / V
+    (set_state / set_res_samples build a new dict per sketch) and scale, the ControlNet engine and its context.  The set keeps
+    STRONG references to those objects and is valid only while the pipeline still holds the very same ones - ids alone could be
+    recycled after the old objects were freed."""
+    xs: torch.Tensor                          # latents: each graph reads them and writes the step's result back
+    ns: torch.Tensor                          # the noise draw eps (LGP argument, masked blend)
+    ts: Optional[torch.Tensor]                # sketch target
+    init: Optional[torch.Tensor]              # masked img2img: the original ...
+    mask: Optional[torch.Tensor]              # ... and the mask
+    zs: Optional[torch.Tensor]                # noised steps: [executed steps, S, 4, h, w], one slice per captured step
+    control: Optional[object]                 # the call's Control with the set's static hint buffer
+    history: History
+    owner: dict                               # ops.private_buffers: split-K workspace and scratch
+    ctx: object
+    inject: object
+    per_image: object
+    scale: object
+    cnet: object
+    cctx: object
+    graphs: list
+    auxs: list
+
+    def valid_for(self, sampler: "HipSampler", control) -> bool:
+        inj = sampler.unet.inject
+        return (self.ctx is sampler.unet.ctx and self.inject is inj and
+                (inj is None or (self.per_image is inj.per_image and self.scale == inj.scale)) and
+                (control is None or (self.cnet is control.net and self.cctx is control.net.ctx)))
+
+    def refill(self, x, noise, tgt, init, mask, control, zall) -> None:
+        """This call's tensors into the static buffers (another control image of the same size replays the same set)."""
+        self.xs.copy_(x); self.ns.copy_(noise)
+        if tgt is not None:
+            self.ts.copy_(tgt)
+        if mask is not None:
+            self.init.copy_(init); self.mask.copy_(mask)
+        self.history.x0.zero_()
+        if control is not None:
+            self.control.hint.copy_(control.hint)
+        if zall is not None:
+            self.zs.copy_(zall)
+
+    def run(self, sampler: "HipSampler", plan: StepPlan, tab, i: int, x: torch.Tensor):
+        """Schedule entry i from latents x on the set's buffers, with the step's slice of the pre-drawn noise."""
+        return sampler._run_step(plan, tab, i, x, self.ns, self.ts, self.init, self.mask,
+                                 None if self.zs is None else self.zs[i - plan.start], self.control, history=self.history)
+
+    def warm_up(self, sampler: "HipSampler", plan: StepPlan, tab) -> None:
+        """One eager pass on a copy of the latents: the per-timestep bias vectors and every lazily built per-image buffer must exist
+        before a capture.  It reads zs and so consumes no generator state."""
+        w = self.xs.clone()
+        for i in range(plan.start, len(tab.timesteps)):
+            w, _ = self.run(sampler, plan, tab, i, w)
+
+    def replay(self, sampler: "HipSampler") -> torch.Tensor:
+        lgp, S = sampler.lgp, self.xs.shape[0]
+        for g, aux in zip(self.graphs, self.auxs):
+            g.replay()
+            sampler.last_aux.append(None if aux is None else aux.clone())
+            if aux is not None and lgp is not None and lgp.training:
+                for l in range(4):
+                    lgp.num_batches_tracked[l] += S
+        return self.xs.clone()
 
 
 class HipSampler:
@@ -325,8 +473,7 @@ class HipSampler:
         self.unet, self.lgp, self.use_graphs = unet, lgp, use_graphs
         self.last_aux: List[Optional[torch.Tensor]] = []
         self.last_latents: Optional[torch.Tensor] = None
-        self._x0_before: Optional[torch.Tensor] = None      # DPM-Solver++ history (one x0 prediction)
-        self._seen = 0
+        self._history: Optional[History] = None             # of the steps that are not given one (tab.new_history, lazily)
         self.share_cfg_prefix = os.environ.get("SKG_SHARE_CFG", "1") != "0"      # A/B switch (bench.py on one box)
         # guided steps: LGP + backward-to-input on a second HIP stream from the moment the ninth tap exists, next to the last
         # up block + conv_out + CFG / DDIM on the launch stream (A/B switch; not under graph capture)
@@ -336,12 +483,17 @@ class HipSampler:
         self.max_graph_sets = 4
 
     def reset_history(self):
-        self._x0_before, self._seen = None, 0
+        self._history = None
+
+    @property
+    def _x0_before(self) -> Optional[torch.Tensor]:
+        """The x0 prediction in the sampler's own history (read-only: what the last step() that was given none left there)."""
+        return None if self._history is None else self._history.x0
 
     @torch.no_grad()
     def step(self, x: torch.Tensor, noise: torch.Tensor, target: Optional[torch.Tensor], tab,
              i: int, guidance_scale: float, beta: float, want_eps: bool = False, eta: float = 0.0, generator=None,
-             z: Optional[torch.Tensor] = None, classifier_free: bool = True, control=None):
+             z: Optional[torch.Tensor] = None, classifier_free: bool = True, control=None, history: Optional[History] = None):
         """One iteration of the loop for S samples.  x fp32 [S,4,h,w] on the device -> x_{t-1}.
         eta > 0 (DDIM only; DPM-Solver++ has no eta): the step adds sigma_t z, z = `z` if given (fp32, x's shape, on the device:
         the hipGraph path's static slice) else one draw_noise(x.shape, generator) after the UNet evaluation.  The stochastic
@@ -350,7 +502,8 @@ class HipSampler:
         rows) and the step kernels take that one tensor as both CFG operands with g = 1 - u + 1 (u - u) is u exactly.
         control (a controlnet.Control whose net has the context of the same rows): the ControlNet trunk runs on the UNet's input -
         all rows, with the control's hint - and its residuals join the UNet's skips and mid block (HipUNet.forward(control=)).
-        Not on a guided step.  Whether a step lies in the control's window is the caller's decision (sample)."""
+        Not on a guided step.  Whether a step lies in the control's window is the caller's decision (sample).
+        history: the multistep state to advance (a GraphSet's); None is the sampler's own, a zero one of x's shape made on demand."""
         S, _, h, w = x.shape
         hw = h * w
         T = len(tab.timesteps)
@@ -394,32 +547,18 @@ class HipSampler:
             ctl = (control.net.forward(x32, t, rows, h, w, control.hint), control.net.zero_convs, control.scale)
         eps, taps = self.unet.forward(x32, t, rows, h, stash, want_taps=guided,
                                       shared_input=self.share_cfg_prefix and classifier_free, on_taps=on_taps if fork else None, W=w,
-                                      **({} if ctl is None else {"control": ctl}))
+                                      control=ctl)
         fork = fork and "done" in branch          # (a forward that never reached the hook runs the branch in line)
         eu, ec, lo_off = ops.eps_halves(eps, S, hw)      # (accuracy mode: eps is a (hi, lo) pair, combined in fp32 by the step kernel)
         if not classifier_free:
             ec, guidance_scale = eu, 1.0
-        if isinstance(tab, DPMTables):
-            if self._x0_before is None or self._x0_before.shape != x.shape:
-                self._x0_before, self._seen = torch.zeros_like(x), 0
-            order = tab.order(i, self._seen)
-            if tab.stochastic:
-                if z is None:
-                    z = draw_noise(x.shape, generator, x.device)
-                res = ops.cfg_dpmpp2m_sde_step(eu, ec, x, z, self._x0_before, S, hw, guidance_scale, tab.coeffs_sde(i, order), want_eps,
-                                               lo_off=lo_off, v_prediction=tab.v_prediction)
-            else:
-                res = ops.cfg_dpmpp2m_step(eu, ec, x, self._x0_before, S, hw, guidance_scale, tab.coeffs(i, order), want_eps,
-                                           lo_off=lo_off, v_prediction=tab.v_prediction)
-            self._seen = min(self._seen + 1, tab.solver_order)
-        elif eta > 0.0:
-            if z is None:
-                z = draw_noise(x.shape, generator, x.device)
-            res = ops.cfg_ddim_eta_step(eu, ec, x, z, S, hw, guidance_scale, tab.coeffs_eta(t, eta), want_eps, lo_off=lo_off,
-                                        v_prediction=tab.v_prediction)
-        else:
-            res = ops.cfg_ddim_step(eu, ec, x, S, hw, guidance_scale, tab.coeffs(t), want_eps, lo_off=lo_off,
-                                    v_prediction=tab.v_prediction)
+        if history is None:
+            history = self._history
+            if history is None or history.x0.shape != x.shape:
+                history = self._history = tab.new_history(x)
+        if z is None and tab.noisy(eta):
+            z = draw_noise(x.shape, generator, x.device)
+        res = tab.update(i, eu, ec, x, z, history, S, hw, guidance_scale, want_eps, lo_off, eta)
         x_prev, eps_cfg = res if want_eps else (res, None)
         aux = None
         if guided:
@@ -470,7 +609,7 @@ class HipSampler:
                                  or tuple(mask.shape[1:]) != (1,) + tuple(latents0.shape[2:])):
             raise ValueError(f"mask shape {tuple(mask.shape)}: expected (1 or {latents0.shape[0]}, 1, {latents0.shape[2]}, "
                              f"{latents0.shape[3]})")
-        if eta > 0.0 and not isinstance(tab, DDIMTables):
+        if eta > 0.0 and not tab.has_eta:
             # DPM-Solver++ has no eta (diffusers' prepare_extra_step_kwargs drops the argument for it): no noise is drawn either
             if not HipSampler._eta_ignored_logged:
                 HipSampler._eta_ignored_logged = True
@@ -506,137 +645,80 @@ class HipSampler:
             control.net.prepare_timesteps(tab.timesteps.tolist())
         self.last_aux = []
         self.reset_history()
+        plan = StepPlan(float(guidance_scale), float(beta), eta, bool(classifier_free), start_step, m is not None,
+                        bool(self.share_cfg_prefix), tgt is None, control)
         if (self.use_graphs if graphs is None else graphs) and callback is None:
-            x = self._sample_graphed(x, tgt, tab, guidance_scale, beta, eta, generator, classifier_free,
-                                     noise=None if init is None else noise, init=init, mask=m, start=start_step,
-                                     **({} if control is None else {"control": control}))
+            x = self._sample_graphed(plan, tab, x, noise, tgt, init, m, generator)
         else:
             steps = tab.timesteps.tolist()
             for n, i in enumerate(range(start_step, T)):
-                ckw = {"control": control} if control is not None and control.active(n, T - start_step) else {}
-                x, _, aux = self.step(x, noise, tgt, tab, i, guidance_scale, beta, eta=eta, generator=generator,
-                                      classifier_free=classifier_free, **ckw)
-                if m is not None:
-                    ops.latent_renoise(init, noise, *tab.level(i + 1), x=x, mask=m)
+                # (z = None: step draws from `generator` after the UNet evaluation)
+                x, aux = self._run_step(plan, tab, i, x, noise, tgt, init, m, None, control, generator=generator)
                 self.last_aux.append(aux)
                 if callback is not None:
                     callback(n, steps[i], x)
         self.last_latents = x
         return x
 
-    # ------------------------------------------------------------------------------------------ hipGraph replay
-    def _sample_graphed(self, x: torch.Tensor, tgt: Optional[torch.Tensor], tab, guidance_scale: float, beta: float,
-                        eta: float = 0.0, generator=None, classifier_free: bool = True, noise: Optional[torch.Tensor] = None,
-                        init: Optional[torch.Tensor] = None, mask: Optional[torch.Tensor] = None, start: int = 0, control=None):
-        """Captures (first call for a given schedule / shape) and replays one hipGraph per step.  Every launch of a
-        step goes to torch's current stream, which is the capturing stream inside ``torch.cuda.graph``; nothing on the
-        step path allocates outside torch's (graph-private) pool or synchronises with the host.
-        Noised steps (draws_noise: eta > 0, or the stochastic DPM-Solver++): the set owns a static [T, S, 4, h, w] noise buffer,
-        each captured step reads its slice; all T draws of a trajectory are made here, once, in step order (draw_noise) -
-        before the warm-up pass of a new set, which reads the buffer too and so consumes no generator state - and copied in
-        before the first replay.
-        img2img (init given: x is the start a*init + s*eps already, `noise` the draw eps, `start` the first entry): only the
-        executed steps start .. T-1 are captured and only their noise is drawn; with a mask each captured step ends with the blend,
-        which reads the set's static `init` and `mask` buffers - refilled before each replay like `ts` - and `ns`, which holds eps.
-        control: the ControlNet launches of the steps inside the control's window are captured with the rest; they read the set's
-        static hint buffer (refilled before each replay: another control image of the same size replays the same set); the key
-        holds "controlled", the scale, the window and the hint's shape, and the set is valid only for the same engine and the
-        text context it was captured with."""
-        T = len(tab.timesteps)
-        inj = self.unet.inject
-        key = graph_key(tab, x.shape, tgt is None, guidance_scale, beta, self.share_cfg_prefix, eta, classifier_free, start,
-                        mask is not None)
-        if control is not None:      # (an uncontrolled call keeps the key - and the launches - it had)
-            key = key + control.key()
-        if noise is None:
-            noise = x                                             # a trajectory from pure noise: modules/pipeline.py:75
-        zall = torch.stack([draw_noise(x.shape, generator, x.device) for _ in range(start, T)]) if draws_noise(tab, eta) else None
-        def step_kw(zs, i, ctl=None):
-            kw = dict(eta=eta, z=None if zs is None else zs[i - start], classifier_free=classifier_free)
-            if ctl is not None and ctl.active(i - start, T - start):
-                kw["control"] = ctl
-            return kw
+    def _run_step(self, plan: StepPlan, tab, i: int, x, noise, tgt, init, mask, z, control, generator=None, history=None):
+        """Schedule entry i on these buffers -> (x, aux): step - with the control iff executed step i - start lies in its window -
+        then, with a mask, the blend with the original re-noised to entry i + 1 (in place).  `control` is the one whose hint
+        the launches are to read (a GraphSet's has the set's static buffer)."""
+        if control is not None and not control.active(i - plan.start, len(tab.timesteps) - plan.start):
+            control = None
+        x, _, aux = self.step(x, noise, tgt, tab, i, plan.guidance_scale, plan.beta, eta=plan.eta, generator=generator, z=z,
+                              classifier_free=plan.classifier_free, control=control, history=history)
+        if mask is not None:
+            ops.latent_renoise(init, noise, *tab.level(i + 1), x=x, mask=mask)
+        return x, aux
 
-        def blend(xn, ent_init, ent_mask, ns, i):
-            if ent_mask is not None:
-                ops.latent_renoise(ent_init, ns, *tab.level(i + 1), x=xn, mask=ent_mask)
-        # What a captured step points at besides the static latents: the text context's K / V (prepare_context builds a
-        # NEW dict per prompt) and the injector's per-image K / V (set_state / set_res_samples build a new dict per sketch)
-        # and scale.  The entry keeps STRONG references to those objects and is valid only while the pipeline still holds
-        # the very same ones - ids alone could be recycled after the old objects were freed (ADVICE r2).
-        ent = self._graphs.get(key)
-        if ent is not None and not (ent["ctx"] is self.unet.ctx and ent["inject"] is inj and
-                                    (inj is None or (ent["per_image"] is inj.per_image and ent["scale"] == inj.scale)) and
-                                    (control is None or (ent["cnet"] is control.net and ent["cctx"] is control.net.ctx))):
-            del self._graphs[key]          # stale: prompt, sketch or scale changed since the capture
-            ent = None
-        if ent is not None:
-            self._graphs[key] = self._graphs.pop(key)       # most recently used last
-        if ent is None:
-            while len(self._graphs) >= self.max_graph_sets:   # LRU bound: every set owns T graphs + a private pool
+    # ------------------------------------------------------------------------------------------ hipGraph replay
+    def _sample_graphed(self, plan: StepPlan, tab, x, noise, tgt, init, mask, generator) -> torch.Tensor:
+        """Replays the GraphSet of this plan, schedule and shape, captured on the first call (or when the one there is stale:
+        prompt, sketch, scale or ControlNet changed since the capture).  x is the start of the trajectory, `noise` the draw eps.
+        Noised steps (tab.noisy: eta > 0, or the stochastic DPM-Solver++): all draws of the executed steps are made here, once, in
+        step order (draw_noise) - before the warm-up pass of a new set - and copied into the set's buffer before the first replay."""
+        key = plan.key(tab, x.shape)
+        zall = None
+        if tab.noisy(plan.eta):
+            zall = torch.stack([draw_noise(x.shape, generator, x.device) for _ in range(plan.start, len(tab.timesteps))])
+        gs = self._graphs.pop(key, None)
+        if gs is None or not gs.valid_for(self, plan.control):
+            while len(self._graphs) >= self.max_graph_sets:   # LRU bound: every set owns its graphs + a private pool
                 self._graphs.pop(next(iter(self._graphs)))
-            owner: dict = {}
-            ops.private_buffers.prepare(owner, x.device)
-            xs, ns = torch.empty_like(x), torch.empty_like(x)
-            ts = None if tgt is None else torch.empty_like(tgt)
-            x0b = torch.zeros_like(x)
-            zs = None if zall is None else zall.clone()
-            ins = None if mask is None else torch.empty_like(init)
-            ms = None if mask is None else torch.empty_like(mask)
-            cs = None if control is None else control.with_hint(control.hint.clone())      # (the set's static hint buffer)
-            # one eager pass first: the per-timestep bias vectors and every lazily built per-image buffer must exist before
-            # a capture.  The split-K workspace of the captured launches is the set's own (allocated above, outside the
-            # capture); scratch buffers first touched inside the capture come from the set's private pool.
-            xs.copy_(x); ns.copy_(noise)
-            if ts is not None:
-                ts.copy_(tgt)
-            if ms is not None:
-                ins.copy_(init); ms.copy_(mask)
-            saved = None if self.lgp is None else [[r.clone() for r in self.lgp.running_mean], [r.clone() for r in self.lgp.running_var],
-                                                   tuple(self.lgp.num_batches_tracked)]
-            self._x0_before, self._seen = x0b, 0
-            w = xs.clone()
-            for i in range(start, T):
-                w, _, _ = self.step(w, ns, ts, tab, i, guidance_scale, beta, **step_kw(zs, i, cs))
-                blend(w, ins, ms, ns, i)
-            if saved is not None:       # the warm-up pass is not part of the trajectory: undo its BatchNorm side effects
-                for l in range(4):
-                    self.lgp.running_mean[l].copy_(saved[0][l]); self.lgp.running_var[l].copy_(saved[1][l])
-                self.lgp.num_batches_tracked = list(saved[2])
+            gs = self._capture(plan, tab, x, noise, tgt, init, mask, zall)
+        self._graphs[key] = gs                                # most recently used last
+        gs.refill(x, noise, tgt, init, mask, plan.control, zall)
+        return gs.replay(self)
+
+    def _capture(self, plan: StepPlan, tab, x, noise, tgt, init, mask, zall) -> GraphSet:
+        """One hipGraph per executed step.  Every launch of a step goes to torch's current stream, which is the capturing stream
+        inside ``torch.cuda.graph``; nothing on the step path allocates outside torch's (graph-private) pool or synchronises with
+        the host.  The split-K workspace of the captured launches is the set's own (allocated here, outside the capture); scratch
+        buffers first touched inside the capture come from the set's private pool.  Only the executed steps are captured; the
+        ControlNet launches of the steps inside the control's window are captured with the rest."""
+        owner: dict = {}
+        ops.private_buffers.prepare(owner, x.device)
+        new, inj, ctl = torch.empty_like, self.unet.inject, plan.control
+        gs = GraphSet(xs=new(x), ns=new(x), ts=None if tgt is None else new(tgt), init=None if mask is None else new(init),
+                      mask=None if mask is None else new(mask), zs=None if zall is None else new(zall),
+                      control=None if ctl is None else ctl.with_hint(new(ctl.hint)), history=History(new(x)), owner=owner,
+                      ctx=self.unet.ctx, inject=inj, per_image=None if inj is None else inj.per_image,
+                      scale=None if inj is None else inj.scale, cnet=None if ctl is None else ctl.net,
+                      cctx=None if ctl is None else ctl.net.ctx, graphs=[], auxs=[])
+        gs.refill(x, noise, tgt, init, mask, ctl, zall)
+        # neither pass is part of the trajectory: the warm-up's BatchNorm side effects are undone, and the captures - which do
+        # not execute - leave the Python-side batch counters where they were
+        with contextlib.nullcontext() if self.lgp is None else self.lgp.preserving_running_stats():
+            gs.warm_up(self, plan, tab)
             torch.cuda.synchronize()
             pool = torch.cuda.graph_pool_handle()
-            graphs, auxs = [], []
-            self._x0_before, self._seen = x0b, 0
-            for i in range(start, T):
+            gs.history.seen = 0
+            for i in range(plan.start, len(tab.timesteps)):
                 g = torch.cuda.CUDAGraph()
                 with torch.cuda.graph(g, pool=pool), ops.private_buffers(owner):
-                    xn, _, aux = self.step(xs, ns, ts, tab, i, guidance_scale, beta, **step_kw(zs, i, cs))
-                    blend(xn, ins, ms, ns, i)
-                    xs.copy_(xn)
-                graphs.append(g)
-                auxs.append(aux)
-            if saved is not None:       # captures do not execute, but keep the Python-side counters where they were
-                self.lgp.num_batches_tracked = list(saved[2])
-            ent = self._graphs[key] = dict(graphs=graphs, auxs=auxs, xs=xs, ns=ns, ts=ts, x0b=x0b, zs=zs, init=ins, mask=ms, owner=owner,
-                                           ctx=self.unet.ctx, inject=inj, per_image=None if inj is None else inj.per_image,
-                                           scale=None if inj is None else inj.scale, control=cs,
-                                           cnet=None if control is None else control.net, cctx=None if control is None else control.net.ctx)
-        ent["xs"].copy_(x); ent["ns"].copy_(noise)
-        if tgt is not None:
-            ent["ts"].copy_(tgt)
-        if mask is not None:
-            ent["init"].copy_(init); ent["mask"].copy_(mask)
-        ent["x0b"].zero_()
-        if control is not None:
-            ent["control"].hint.copy_(control.hint)
-        if zall is not None:
-            ent["zs"].copy_(zall)
-        S = x.shape[0]
-        for i, g in enumerate(ent["graphs"]):
-            g.replay()
-            aux = ent["auxs"][i]
-            self.last_aux.append(None if aux is None else aux.clone())
-            if aux is not None and self.lgp is not None and self.lgp.training:
-                for l in range(4):
-                    self.lgp.num_batches_tracked[l] += S
-        return ent["xs"].clone()
+                    xn, aux = gs.run(self, plan, tab, i, gs.xs)
+                    gs.xs.copy_(xn)
+                gs.graphs.append(g)
+                gs.auxs.append(aux)
+        return gs

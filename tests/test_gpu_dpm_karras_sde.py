@@ -285,7 +285,7 @@ def test_graph_replay_of_karras_schedules_is_bit_identical(tiny, algo):
         outs[seed] = a
     assert len(graphed._graphs) == 1 and not torch.equal(outs[1], outs[2])
     ent = next(iter(graphed._graphs.values()))
-    assert (ent["zs"] is not None and tuple(ent["zs"].shape) == (T_T, 1, 4, H_T, H_T)) if algo == SDE else ent["zs"] is None
+    assert (ent.zs is not None and tuple(ent.zs.shape) == (T_T, 1, 4, H_T, H_T)) if algo == SDE else ent.zs is None
     other = DPMTables.make(T_T, algorithm_type=algo)
     a, _ = run(eager, 1, other)
     b, _ = run(graphed, 1, other)

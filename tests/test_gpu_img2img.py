@@ -331,7 +331,7 @@ def test_graph_replay_of_masked_img2img_is_bit_identical(tiny, kind):
         outs[seed] = a
     assert len(graphed._graphs) == 1 and not torch.equal(outs[1], outs[2])
     ent = next(iter(graphed._graphs.values()))
-    assert len(ent["graphs"]) == T - k and ent["init"] is not None and ent["mask"] is not None
+    assert len(ent.graphs) == T - k and ent.init is not None and ent.mask is not None
     a, sa, na = run(eager, 1, img2img=False)
     b, sb, nb = run(graphed, 1, img2img=False)
     assert len(graphed._graphs) == 2 and torch.equal(a, b) and torch.equal(sa, sb) and na == nb == T

@@ -354,3 +354,49 @@ def test_graph_replay_with_eta_and_without_cfg_is_bit_identical(tiny, eta, class
         x0 = torch.randn(S, 4, h, h, generator=gen)
         det = graphed.sample(x0, None, T, tables=tab, classifier_free=classifier_free)      # another key: eta = 0
         assert len(graphed._graphs) == 2 and not torch.equal(det, outs[1])
+
+
+def test_every_option_at_once_replays_as_eager(tiny):
+    """Every option through the one step runner in one call: the stochastic Karras DPM-Solver++ with a list of two generators,
+    img2img from entry 1 with a per-sample mask, a ControlNet on the window (0.25, 0.75), no sketch target; non-square latents
+    [2, 4, 8, 16].  T = 4 is the shortest schedule with a second-order step and with executed steps outside the window at both
+    ends (of the 3 executed steps only the middle one is controlled); S = 2 separates the per-sample masks and generators.
+    Replay == eager bit for bit; another init, mask and hint of the same shapes replay the same set; the uncontrolled call is a
+    second set and equals the uncontrolled eager run."""
+    from oracle import unet as ounet
+    from sketch2img_amd.config import TINY
+    from sketch2img_amd.controlnet import Control, ControlNetModel
+    from sketch2img_amd.sampler import DPMTables, HipSampler
+    net, S, h, w, T = tiny["net"], 2, 8, 16, 4
+    ehs = rnd(2 * S, 77, ounet.TINY.cross_attention_dim, seed=41).half().float()
+    cnet = ControlNetModel.from_pretrained(None, unet_config=TINY).to(DEV).hip
+    net.prepare_context(ehs)
+    cnet.prepare_context(ehs)
+    tab = DPMTables.make(T, use_karras_sigmas=True, algorithm_type="sde-dpmsolver++")
+    eager, graphed = HipSampler(net), HipSampler(net, use_graphs=True)
+
+    def run(sampler, seed, controlled=True):
+        g = torch.Generator().manual_seed(seed)
+        eps, init = torch.randn(S, 4, h, w, generator=g), 0.8 * torch.randn(S, 4, h, w, generator=g)
+        mask = (torch.rand(S, 1, h, w, generator=g) > 0.5).float()
+        assert not torch.equal(mask[0], mask[1])
+        control = None
+        if controlled:
+            hint = cnet.hint_rows(cnet.embed(torch.rand(1, 3, 8 * h, 8 * w, generator=g).to(DEV)), 1, 2 * S)
+            control = Control(cnet, hint, 0.8, 0.25, 0.75)
+        gens = [torch.Generator().manual_seed(1000 * seed + b) for b in range(S)]
+        out = sampler.sample(eps, None, T, tables=tab, generator=gens, init_latents=init, start_step=1, mask=mask, control=control)
+        return out.clone(), [gen.get_state() for gen in gens], len(sampler.last_aux)
+
+    outs = []
+    for seed in (1, 2):                         # capture + replay, then a replay of the cached set with other buffers
+        a, sa, na = run(eager, seed)
+        b, sb, nb = run(graphed, seed)
+        assert torch.isfinite(a).all() and torch.equal(a, b), seed
+        assert all(torch.equal(p, q) for p, q in zip(sa, sb)) and na == nb == T - 1
+        assert len(graphed._graphs) == 1
+        outs.append(a)
+    assert not torch.equal(outs[0], outs[1])
+    a, _, _ = run(eager, 1, controlled=False)
+    b, _, _ = run(graphed, 1, controlled=False)
+    assert len(graphed._graphs) == 2 and torch.equal(a, b) and not torch.equal(a, outs[0])

@@ -79,7 +79,7 @@ probe_out = torch.empty(512 * 512, device=dev, dtype=torch.float32)
 
 
 def reset(ent, lat, tgt):
-    ent["xs"].copy_(lat); ent["ns"].copy_(lat); ent["ts"].copy_(tgt.expand_as(lat)); ent["x0b"].zero_()
+    ent.xs.copy_(lat); ent.ns.copy_(lat); ent.ts.copy_(tgt.expand_as(lat)); ent.history.x0.zero_()
 
 
 def two_streams(delay_iters):
@@ -90,27 +90,27 @@ def two_streams(delay_iters):
             check(lib.skg_box_probe_mfma(probe_out.data_ptr(), delay_iters, st_b.cuda_stream), "delay")
     for i in range(T):
         with torch.cuda.stream(st_a):
-            ea["graphs"][i].replay()
+            ea.graphs[i].replay()
         with torch.cuda.stream(st_b):
-            eb["graphs"][i].replay()
+            eb.graphs[i].replay()
 
 
 def one_stream():
     reset(ea, la, ta); reset(eb, lb, tb_)
     for i in range(T):
-        ea["graphs"][i].replay()
-        eb["graphs"][i].replay()
+        ea.graphs[i].replay()
+        eb.graphs[i].replay()
 
 
 res["E  2 x 4 graphs, one stream"] = timed(one_stream, args.reps)
 res["C  2 x 4 graphs, two streams, together"] = timed(lambda: two_streams(0), args.reps)
-xa, xb = ea["xs"].clone(), eb["xs"].clone()
+xa, xb = ea.xs.clone(), eb.xs.clone()
 # half a step of one group: ~ (E / 2) / T / 2 seconds; the delay kernel runs ~0.67 us per iteration at 2 PFLOP/s (512 workgroups: 1.34 us)
 half_step = res["E  2 x 4 graphs, one stream"][0] / 2 / T / 2
 iters = max(1, int(half_step / 1.34e-6))
 res[f"D  2 x 4 graphs, two streams, second delayed by {half_step * 1e3:.1f} ms"] = timed(lambda: two_streams(iters), args.reps)
-same = torch.equal(ea["xs"], xa) and torch.equal(eb["xs"], xb)
-fin = bool(torch.isfinite(ea["xs"]).all() and torch.isfinite(eb["xs"]).all())
+same = torch.equal(ea.xs, xa) and torch.equal(eb.xs, xb)
+fin = bool(torch.isfinite(ea.xs).all() and torch.isfinite(eb.xs).all())
 print(f"configs[1] sampling loop without the VAE decode, {T} DDIM steps, mode {args.mode}; best / mean of {args.reps} runs after one warm-up")
 for k, (best, mean) in res.items():
     print(f"  {k:62s} {best * 1e3:9.1f} ms  {mean * 1e3:9.1f} ms   {8 / best:6.3f} images/s")
