@@ -341,8 +341,8 @@ int skg_attn_fwd(const void* Q, int ldq, const void* K, int ldk, const void* Vt,
 /* Which kernel instantiation skg_attn_fwd runs for these arguments (it takes its decision from the same function): 1000 + QT for the
  * streaming kernel (attn_fwd_kernel with QT 16-query tiles per wave: 2, 1 at dh = 160, 3 at dh = 40 on launches of >= 1024
  * workgroups, 4 only behind SKG_ATTN_VAR), 2000 + QT for its SKG_ATTN_CAUSAL instantiation, 3000 + NT for the LDS-resident kernel
- * (attn_fwd_short_kernel with NT 16-key score tiles: 5 up to 80 key slots with SKG_ATTN_ROWV, 10 / 15 behind SKG_ATTN_RESIDENT_KV);
- * lab builds report 5000 + the waves per workgroup of the 8-wave formulation.  Negative: the SKG_E_* skg_attn_fwd returns for this
+ * (attn_fwd_short_kernel with NT 16-key score tiles: 5 up to 80 key slots with SKG_ATTN_ROWV, 10 / 15 behind SKG_ATTN_RESIDENT_KV).
+ * Negative: the SKG_E_* skg_attn_fwd returns for this
  * shape and these flags once its pointers and pitches pass.  *queries_per_workgroup (may be NULL; written only on success) = 64 QT,
  * or the resident kernel's query chunk.  Needs no GPU and no buffers; honours the SKG_ATTN_VAR / SKG_NO_ATTN_SHORT switches, which
  * the library reads once per process.  Lets a test name the instantiation it was written for (tests/attn_emulation.py FWD_CASES).

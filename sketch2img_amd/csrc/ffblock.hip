@@ -54,15 +54,14 @@ struct FFParams {
 
 constexpr int MAXCH = 40;
 
-// PROBE (timing experiments only, results are wrong; SKG_FFB_PROBE): 1 = no weight DMA inside the loop, 2 = no gate arithmetic,
-// 3 = no LDS fragment reads (a register stands in for every A operand), 4 = 1 + 3
-// SCHED (SKG_FFB_SCHED, A/B of issue orders): 0 = a gated PAIR after the MFMAs of every second k-step, 1 = the same with the
-// two waves of a SIMD in alternate k-steps, 2 = the pair's arithmetic in four stages spread over the MFMAs of two k-steps
+// PROBE, SCHED: always 0 (the timing probes and issue-order variants they selected are withdrawn); the parameters stay because the
+// instantiation name is part of what the benchmark reports
 // HILO (accuracy mode, skg_ff_block_f16 with X_lo): LayerNorm reads hi + lo, the residual sum is formed in fp32 on the pair and
 // stored as hi = fp16(v), lo = fp16(v - hi); everything between is the same kernel
 template <int KS, int PROBE = 0, int SCHED = 0, bool HILO = false, bool PROJ = false>
 __global__ __launch_bounds__(512, 1) void ff_block_kernel(const FFParams p) {
-  static_assert(!PROJ || (PROBE == 0 && KS == 10), "the proj_out phase exists for the C = 320 kernel");
+  static_assert(PROBE == 0 && SCHED == 0, "placeholders");
+  static_assert(!PROJ || KS == 10, "the proj_out phase exists for the C = 320 kernel");
   constexpr int C = 32 * KS, NU = C / 16, N1 = 4 * KS, NP = N1 + NU, PIECE = 512;
   constexpr int W1ST = N1 * PIECE, W2ST = NU * PIECE;      // halves per ring stage
   constexpr int W2OFF = 2 * W1ST, DUMP = W2OFF + 2 * W2ST, RING = DUMP + (64 - NP) * PIECE;
@@ -83,7 +82,6 @@ __global__ __launch_bounds__(512, 1) void ff_block_kernel(const FFParams p) {
   // q < 60 a W2 piece, else dead.  Unconditional (a branch per piece would cut the MFMA stream into basic blocks): a dead
   // piece - no such chunk, or q >= 60 - reads out of range = zero fill of a slot nobody reads.
   auto dma_slot = [&](int c, int j) {
-    if constexpr (PROBE == 1 || PROBE == 4) return;
     const int q = wave + 8 * j;
     const int cs = q < N1 ? c + 2 : c + 1;                                   // source chunk
     const bool live = q < NP && cs < (PROJ && q < N1 ? p.nch_w1 : p.nch);      // (PROJ: W1(nch) is the first proj_out chunk)
@@ -198,97 +196,31 @@ __global__ __launch_bounds__(512, 1) void ff_block_kernel(const FFParams p) {
     asm volatile("" : "+v"(hv), "+v"(hg));
     const half2_t pv = __builtin_convertvector(hv, half2_t), pg = __builtin_convertvector(hg, half2_t);
     float2_t o = {(float)pv[0] * gelu_fast_f((float)pg[0]), (float)pv[1] * gelu_fast_f((float)pg[1])};
-    if constexpr (PROBE == 2) o = hv + hg;
     half2_t ph = __builtin_convertvector(o, half2_t);
     asm volatile("" : "+v"(ph));
     gb[2 * pr] = ph[0];
     gb[2 * pr + 1] = ph[1];
   };
-  // SCHED 2: gelu_fast_f of a pair in four stages (same expressions), the live values pinned at every stage end
-  float2_t sa, sg, sz, st, se, sp;
-  auto stage = [&](const float4_t (&h)[4], int idx, half8_t& gb) {
-    const int pr = idx >> 2;
-    switch (idx & 3) {
-      case 0: {
-        const int t = pr >> 1, r = 2 * (pr & 1);
-        float2_t hv = {h[t][r], h[t][r + 1]}, hg = {h[2 + t][r], h[2 + t][r + 1]};
-        asm volatile("" : "+v"(hv), "+v"(hg));
-        const half2_t pv = __builtin_convertvector(hv, half2_t), pg = __builtin_convertvector(hg, half2_t);
-        sa = float2_t{(float)pv[0], (float)pv[1]};
-        sg = float2_t{(float)pg[0], (float)pg[1]};
-        sz = float2_t{fabsf(sg[0]) * 0.70710678118654752f, fabsf(sg[1]) * 0.70710678118654752f};
-        asm volatile("" : "+v"(sa), "+v"(sg), "+v"(sz));
-        break;
-      }
-      case 1: {
-        st = float2_t{__builtin_amdgcn_rcpf(fmaf(0.3275911f, sz[0], 1.f)), __builtin_amdgcn_rcpf(fmaf(0.3275911f, sz[1], 1.f))};
-        se = float2_t{__builtin_amdgcn_exp2f(-sz[0] * sz[0] * 1.4426950408889634f), __builtin_amdgcn_exp2f(-sz[1] * sz[1] * 1.4426950408889634f)};
-        asm volatile("" : "+v"(st), "+v"(se));
-        break;
-      }
-      case 2: {
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-          float q = fmaf(1.061405429f, st[j], -1.453152027f);
-          q = fmaf(q, st[j], 1.421413741f);
-          q = fmaf(q, st[j], -0.284496736f);
-          sp[j] = fmaf(q, st[j], 0.254829592f);
-        }
-        asm volatile("" : "+v"(sp));
-        break;
-      }
-      default: {
-        float2_t o;
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-          const float e = 1.f - sp[j] * st[j] * se[j];
-          o[j] = sa[j] * (0.5f * sg[j] + 0.5f * fabsf(sg[j]) * e);
-        }
-        if constexpr (PROBE == 2) o = sa + sg;
-        half2_t ph = __builtin_convertvector(o, half2_t);
-        asm volatile("" : "+v"(ph));
-        gb[2 * pr] = ph[0];
-        gb[2 * pr + 1] = ph[1];
-      }
-    }
-  };
-  const int gphase = (wave >> 2) & 1;
   auto ff1 = [&](float4_t (&h)[4], int cn, int c, const float4_t (&hin)[4], half8_t& gb, bool GATE) {
     const half_t* fr = smem + (cn & 1) * W1ST + lane * 8;
     half8_t fa[4], fb[4];
 #pragma unroll
     for (int t = 0; t < 4; ++t) h[t] = *reinterpret_cast<const float4_t*>(bs + cn * 64 + t * 16 + 4 * g);
 #pragma unroll
-    for (int t = 0; t < 4; ++t) fa[t] = (PROBE >= 3) ? xb[t] : ld_half8(fr + (t * KS) * PIECE);
+    for (int t = 0; t < 4; ++t) fa[t] = ld_half8(fr + (t * KS) * PIECE);
 #pragma unroll
     for (int ks = 0; ks < KS; ++ks) {
       half8_t (&cur)[4] = (ks & 1) ? fb : fa;
       half8_t (&nxt)[4] = (ks & 1) ? fa : fb;
       if (ks + 1 < KS) {
 #pragma unroll
-        for (int t = 0; t < 4; ++t) nxt[t] = (PROBE >= 3) ? xb[(t + ks) % KS] : ld_half8(fr + (t * KS + ks + 1) * PIECE);
+        for (int t = 0; t < 4; ++t) nxt[t] = ld_half8(fr + (t * KS + ks + 1) * PIECE);
       }
-      if constexpr (SCHED == 2) {
-        h[0] = __builtin_amdgcn_mfma_f32_16x16x32_f16(cur[0], xb[ks], h[0], 0, 0, 0);
-        __builtin_amdgcn_sched_barrier(0);
-        if (GATE && ks < 8) stage(hin, 2 * ks, gb);
-        __builtin_amdgcn_sched_barrier(0);
-        h[1] = __builtin_amdgcn_mfma_f32_16x16x32_f16(cur[1], xb[ks], h[1], 0, 0, 0);
-        h[2] = __builtin_amdgcn_mfma_f32_16x16x32_f16(cur[2], xb[ks], h[2], 0, 0, 0);
-        __builtin_amdgcn_sched_barrier(0);
-        if (GATE && ks < 8) stage(hin, 2 * ks + 1, gb);
-        __builtin_amdgcn_sched_barrier(0);
-        h[3] = __builtin_amdgcn_mfma_f32_16x16x32_f16(cur[3], xb[ks], h[3], 0, 0, 0);
-      } else {
 #pragma unroll
-        for (int t = 0; t < 4; ++t) h[t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(cur[t], xb[ks], h[t], 0, 0, 0);
-      }
+      for (int t = 0; t < 4; ++t) h[t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(cur[t], xb[ks], h[t], 0, 0, 0);
       __builtin_amdgcn_sched_barrier(0);
       if (ks < 8) {
-        // the two waves that share a SIMD (w and w + 4) gate in alternate k-steps: one is on the VALU while the other
-        // feeds the matrix pipe
-        if (SCHED == 0 && GATE && (ks & 1)) gate2(hin, ks >> 1, gb);
-        if (SCHED == 1 && GATE && (ks & 1) == gphase) gate2(hin, ks >> 1, gb);
+        if (GATE && (ks & 1)) gate2(hin, ks >> 1, gb);
         dma_slot(c, ks);
       }
       __builtin_amdgcn_sched_barrier(0);
@@ -302,7 +234,7 @@ __global__ __launch_bounds__(512, 1) void ff_block_kernel(const FFParams p) {
     const half_t* fr = smem + (w2base + (c & 1) * W2ST);
 #pragma unroll
     for (int u = 0; u < NU; ++u)
-      y[u] = __builtin_amdgcn_mfma_f32_16x16x32_f16((PROBE >= 3) ? xb[u % KS] : ld_half8(fr + u * PIECE), gb, y[u], 0, 0, 0);
+      y[u] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ld_half8(fr + u * PIECE), gb, y[u], 0, 0, 0);
   };
   // rows whose gate will be differentiated (the cond rows of a guided step) also store the pre-activation in the
   // interleaved FF1 pack order skg_geglu_bwd reads: the lane's units j .. j + 3 (j = 32 c + 16 t + 4 g) are the 8
@@ -558,22 +490,6 @@ extern "C" int skg_ff_block_f16(const void* X, const void* Xl, int ldx, void* Y,
   // against 6.706 / 6.706 images/s, one box, alternating): the 42 MB output no longer evicts what the next launches read
   p.nt_out = getenv("SKG_FFB_NT") ? atoi(getenv("SKG_FFB_NT")) : 1;      // A/B switch, read per launch
   const dim3 grid(skg_cdiv(M, 128));
-#ifdef SKG_LAB      // lab build only (make lab): probe instantiations compute WRONG results (timing experiments, EXPERIMENTS.md round 3)
-  static const int probe = getenv("SKG_FFB_PROBE") ? atoi(getenv("SKG_FFB_PROBE")) : 0;
-  static const int sched = getenv("SKG_FFB_SCHED") ? atoi(getenv("SKG_FFB_SCHED")) : 0;
-  if (!Xl && probe * 10 + sched) {
-    switch (probe * 10 + sched) {
-      case 10: hipLaunchKernelGGL((ff_block_kernel<10, 1>), grid, dim3(512), 0, (hipStream_t)stream, p); break;
-      case 20: hipLaunchKernelGGL((ff_block_kernel<10, 2>), grid, dim3(512), 0, (hipStream_t)stream, p); break;
-      case 30: hipLaunchKernelGGL((ff_block_kernel<10, 3>), grid, dim3(512), 0, (hipStream_t)stream, p); break;
-      case 40: hipLaunchKernelGGL((ff_block_kernel<10, 4>), grid, dim3(512), 0, (hipStream_t)stream, p); break;
-      case 1: hipLaunchKernelGGL((ff_block_kernel<10, 0, 1>), grid, dim3(512), 0, (hipStream_t)stream, p); break;
-      default: hipLaunchKernelGGL((ff_block_kernel<10, 0, 2>), grid, dim3(512), 0, (hipStream_t)stream, p); break;
-    }
-    SKG_CHECK_LAUNCH("skg_ff_block_f16 (probe)");
-    return SKG_OK;
-  }
-#endif
   if (bias_proj && Xl) hipLaunchKernelGGL((ff_block_kernel<10, 0, 0, true, true>), grid, dim3(512), 0, (hipStream_t)stream, p);
   else if (bias_proj) hipLaunchKernelGGL((ff_block_kernel<10, 0, 0, false, true>), grid, dim3(512), 0, (hipStream_t)stream, p);
   else if (Xl) hipLaunchKernelGGL((ff_block_kernel<10, 0, 0, true>), grid, dim3(512), 0, (hipStream_t)stream, p);

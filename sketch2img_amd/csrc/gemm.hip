@@ -190,12 +190,7 @@ int launch_plain(const GemmParams& p, hipStream_t st);
 template <int MODE>
 int launch(const GemmParams& p, hipStream_t st) {
   if (!p.gn_partial) return launch_plain<MODE>(p, st);
-#ifdef SKG_LAB
-  const bool v9 = !p.bias_pitch && skg_gemm9_eligible(p, MODE);      // (no statistics epilogue: the stand-alone pass follows)
-#else
-  constexpr bool v9 = false;
-#endif
-  const bool fused = v9 ? false : skg_gemm8_eligible(p, MODE) ? skg_gemm8_fuses_gn(p, MODE) : skg_gemm2_fuses_gn(p, MODE);      // (the k-pair kernel declines launches that ask for statistics)
+  const bool fused = skg_gemm8_eligible(p, MODE) ? skg_gemm8_fuses_gn(p, MODE) : skg_gemm2_fuses_gn(p, MODE);
   const int rc = launch_plain<MODE>(p, st);
   if (rc != SKG_OK || fused) return rc;
   skg_gn_partial_launch((const half_t*)p.C, p.ldc, p.M / p.gn_hw, p.gn_hw, p.N, p.gn_groups, p.gn_hw / 128, p.gn_partial, st);
@@ -205,28 +200,10 @@ int launch(const GemmParams& p, hipStream_t st) {
 
 template <int MODE>
 int launch_plain(const GemmParams& p, hipStream_t st) {
-#ifdef SKG_LAB      // withdrawn round-3 experiment (tools/lab/gemmws.hip, EXPERIMENTS.md): lab build only, SKG_GEMMWS=1
-  if (skg_gemmws_try_launch(p, MODE, st)) {
-    SKG_CHECK_LAUNCH("skg_gemm (ws)");
-    return SKG_OK;
-  }
-#endif
-#ifdef SKG_LAB      // round-5 experiment (tools/lab/gemm9.hip, EXPERIMENTS.md "the hand-placed K loop"): lab build only, SKG_GEMM9=<geometry><variant>
-  if (!p.bias_pitch && skg_gemm9_try_launch(p, MODE, st)) {      // (no per-sample bias row in the lab kernels)
-    SKG_CHECK_LAUNCH("skg_gemm (v9)");
-    return SKG_OK;
-  }
-#endif
   if (skg_gemm8_try_launch(p, MODE, st)) {
     SKG_CHECK_LAUNCH("skg_gemm (v8)");
     return SKG_OK;
   }
-#ifdef SKG_LAB      // withdrawn round-3 experiment (tools/lab/gemmk.hip, EXPERIMENTS.md): lab build only, SKG_GEMMK=1
-  if (!p.bias_pitch && skg_gemmk_try_launch(p, MODE, st)) {
-    SKG_CHECK_LAUNCH("skg_gemm (k-pair)");
-    return SKG_OK;
-  }
-#endif
   if (skg_gemm2_try_launch(p, MODE, st)) {
     SKG_CHECK_LAUNCH("skg_gemm (v2)");
     return SKG_OK;
@@ -270,15 +247,10 @@ void ws_attach(GemmParams& p, hipStream_t st) {
   std::lock_guard<std::mutex> lk(g_ws_mu);
   for (const WsEntry& e : g_ws_tab)
     if (e.dev == dev && e.st == st) {
-#ifdef SKG_LAB      // (the withdrawn self-finishing split-K launch keeps its tile tickets at the end of the slab)
-      p.ws = e.ws; p.ws_bytes = e.bytes - SKG_WS_TICKET_BYTES;
-      p.ws_cnt = reinterpret_cast<unsigned*>(reinterpret_cast<char*>(e.ws) + p.ws_bytes);
-#else
       p.ws = e.ws; p.ws_bytes = e.bytes;
-#endif
       return;
     }
-  p.ws = nullptr; p.ws_bytes = 0; p.ws_cnt = nullptr;
+  p.ws = nullptr; p.ws_bytes = 0;
 }
 }  // namespace
 
@@ -286,14 +258,6 @@ extern "C" int skg_set_workspace(void* ws, size_t bytes, void* stream) {
   SKG_REQUIRE(ws == nullptr || (skg_aligned(ws, 16) && bytes >= (1u << 20)));
   int dev = 0;
   (void)hipGetDevice(&dev);
-#ifdef SKG_LAB
-  if (ws) {      // the tile tickets of the self-finishing split-K launches start at zero (every launch leaves them there)
-    if (hipMemsetAsync(reinterpret_cast<char*>(ws) + bytes - SKG_WS_TICKET_BYTES, 0, SKG_WS_TICKET_BYTES, (hipStream_t)stream) != hipSuccess) {
-      (void)hipGetLastError();
-      return SKG_E_LAUNCH;
-    }
-  }
-#endif
   std::lock_guard<std::mutex> lk(g_ws_mu);
   for (size_t i = 0; i < g_ws_tab.size(); ++i)
     if (g_ws_tab[i].dev == dev && g_ws_tab[i].st == (hipStream_t)stream) {
@@ -312,19 +276,7 @@ extern "C" int skg_gemm_variant(int M, int N, int K, int Cin, int mode) {
   {   // v8 takes plain (fp16 out, no fused GEGLU) launches of eligible shapes
     GemmParams q{};
     q.M = M; q.N = N; q.K = K; q.Cin = Cin; q.lda = q.ldb = K; q.ldc = N; q.OH = q.OW = q.IH = q.IW = 1;
-#ifdef SKG_LAB
-    if (skg_gemmws_eligible(q, mode)) return 7320;      // (plain epilogue only: launches with statistics / GEGLU / fp32 out take v2)
-#endif
-#ifdef SKG_LAB
-    q.C = (void*)16;      // (alignment checks only)
-    if (skg_gemm9_eligible(q, mode)) return 9320;
-    q.C = nullptr;
-#endif
     if (const int bn8 = skg_gemm8_tile_n(q, mode)) return 8000 + bn8;
-#ifdef SKG_LAB
-    q.C = (void*)16;      // (alignment checks only)
-    if (skg_gemmk_eligible(q, mode)) return 9160;
-#endif
   }
   const int v2 = skg_gemm2_tile_n(M, N, K, Cin, mode, ws_query_bytes());
   return v2 ? 2000 + v2 : 1000 + (use_wide(M, N) ? 128 : 64);
@@ -354,9 +306,6 @@ extern "C" int skg_gemm_gn_fused(int M, int N, int K, int Cin, int mode, int HW,
   q.gn_partial = &dummy; q.gn_hw = HW; q.gn_groups = groups;
   const size_t wsb = ws_query_bytes();
   q.ws = wsb ? (float*)&dummy : nullptr; q.ws_bytes = wsb;
-#ifdef SKG_LAB
-  if (skg_gemm9_eligible(q, mode)) return 0;
-#endif
   return (skg_gemm8_eligible(q, mode) ? skg_gemm8_fuses_gn(q, mode) : skg_gemm2_fuses_gn(q, mode)) ? 1 : 0;
 }
 

@@ -124,30 +124,7 @@ __device__ unsigned long long g_phase[1 << 15][16];
 #define SKG_PH(i) do { } while (0)
 #endif
 
-// NS = pipeline stages.  2: two workgroups per CU cover each other's DMA waits.  3: for launches with at most ONE
-// workgroup per CU (<= 256 tiles) nothing else is resident, so the lone workgroup keeps two K tiles in flight instead
-// (110 KB of LDS) and waits with a counted vmcnt.
-// GNS: the instantiation whose epilogue also writes the GroupNorm partial sums of the output (launched only when asked
-// for - its 25 extra epilogue registers and code cost the plain launches 0.3 % of a batch when they shared one kernel)
-// HILO: the accuracy-mode instantiation (skg_*_hilo): the fp32-staged epilogue also adds p.res_lo and stores
-// lo = fp16(v - fp16(v)) to p.c_lo, whatever the launch (an own instantiation: the plain kernels stay as tuned)
-// agent-scope (sc1) 16-byte store / load of a slab element: two relaxed 8-byte atomics each (global_store / load_dwordx2 ... sc1)
-__device__ __forceinline__ void st_agent(float* p, float4_t v) {
-  typedef float float2v __attribute__((ext_vector_type(2)));
-  unsigned long long* q = reinterpret_cast<unsigned long long*>(p);
-  __hip_atomic_store(q, __builtin_bit_cast(unsigned long long, float2v{v[0], v[1]}), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  __hip_atomic_store(q + 1, __builtin_bit_cast(unsigned long long, float2v{v[2], v[3]}), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ float4_t ld_agent(const float* p) {
-  typedef float float2v __attribute__((ext_vector_type(2)));
-  unsigned long long* q = reinterpret_cast<unsigned long long*>(const_cast<float*>(p));
-  const float2v a = __builtin_bit_cast(float2v, __hip_atomic_load(q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
-  const float2v b = __builtin_bit_cast(float2v, __hip_atomic_load(q + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
-  return float4_t{a[0], a[1], b[0], b[1]};
-}
-
-// the epilogue of a split-K launch on 4 summed outputs (row m, columns n .. n + 3): splitk_reduce_kernel and the self-finishing
-// launch (gemm2_splitk_kernel) share it, bit for bit
+// the epilogue of a split-K launch on 4 summed outputs (row m, columns n .. n + 3)
 __device__ __forceinline__ void splitk_epilogue(const GemmParams& p, float4_t v, size_t m, int n) {
   if (p.bias) {
     const half4_t b = ld_half4(p.bias + (p.bias_pitch ? (m / (size_t)p.gn_hw) * (size_t)p.bias_pitch : 0) + n);      // (the sample's bias row)
@@ -177,19 +154,17 @@ __device__ __forceinline__ void splitk_epilogue(const GemmParams& p, float4_t v,
   }
 }
 
-// FIX (gemm2_splitk_kernel, lab build only - measured and withdrawn): the split-K launch finishes itself.  Every workgroup writes its fp32 slab as before, then takes a
-// ticket on its tile's counter (p.ws_cnt, kept zero between launches: the counter wraps at `splits`); the workgroup that draws
-// the LAST ticket of a tile adds the slabs in slab order (0, 1, ...: the order of splitk_reduce_kernel, so the result is the
-// same bit pattern whichever workgroup arrives last) and runs the reduce kernel's epilogue on its 128 x BN tile.  No workgroup
-// waits for another one.  Visibility across the XCDs' L2s (one per XCD, not coherent with each other for ordinary accesses): ONE
-// agent-scope release fence per workgroup behind the slab stores (buffer_wbl2 sc1), agent-scope (sc1) loads of the slabs behind
-// the ticket.  Bit-identical to the two-launch path (tools/lab/splitk_self_check.py) and 13-26 % SLOWER end to end in all three
-// forms tried (EXPERIMENTS.md): the reduction is 320 KB through one CU at memory-side latency where splitk_reduce_kernel has
-// the whole chip; the product keeps the reduce launch.
+// NS = pipeline stages.  2: two workgroups per CU cover each other's DMA waits.  3: for launches with at most ONE
+// workgroup per CU (<= 256 tiles) nothing else is resident, so the lone workgroup keeps two K tiles in flight instead
+// (110 KB of LDS) and waits with a counted vmcnt.
+// GNS: the instantiation whose epilogue also writes the GroupNorm partial sums of the output (launched only when asked
+// for - its 25 extra epilogue registers and code cost the plain launches 0.3 % of a batch when they shared one kernel)
+// HILO: the accuracy-mode instantiation (skg_*_hilo): the fp32-staged epilogue also adds p.res_lo and stores
+// lo = fp16(v - fp16(v)) to p.c_lo, whatever the launch (an own instantiation: the plain kernels stay as tuned)
 // BROWS: the instantiations for a bias row per sample (p.bias_pitch) on tiles that can span samples (launch_cfg: SKG_FLAG_BIAS_PER_ROW):
 // always the fp32-staged epilogue, whose second phase owns ONE output row per thread and adds that row's bias row there (the slice in
 // LDS stays zero), or the direct stores with a per-row lookup.  The plain instantiations only ever see tiles inside one sample.
-template <int BM, int BN, int WGM, int WGN, int MODE, int NS, bool GNS, bool HILO, bool FIX, bool BROWS = false>
+template <int BM, int BN, int WGM, int WGN, int MODE, int NS, bool GNS, bool HILO, bool BROWS = false>
 __device__ __forceinline__ void gemm2_body(const GemmParams& p, int tiles_n, int nwg, unsigned a_bytes, unsigned b_bytes,
                                            unsigned a_shift, int kt_per_split, float* __restrict__ ws) {
   constexpr int NW = WGM * WGN;       // waves
@@ -499,27 +474,6 @@ __device__ __forceinline__ void gemm2_body(const GemmParams& p, int tiles_n, int
 #pragma unroll
       for (int v = 0; v < plan_vmem<MT, NT>(gq, ND); ++v) dma_one(d, ibuf, di++);
     }
-#ifdef SKG_LAB
-    // VERDICT r3 #6 cost probe (lab build, SKG_GLUE_PROBE=1; results are wrong by construction): what GroupNorm + SiLU applied to
-    // the convolution's A operand inside the K loop would cost in its cheapest form - packed fp16 on the fragments as they leave
-    // LDS (y = x * s + t; y * rcp(1 + exp2(-1.4427 y))), per-lane constants instead of the per-(sample, channel) table
-    if (p.flags & 0x2000u) {
-      typedef _Float16 h2 __attribute__((ext_vector_type(2)));
-      const h2 sc = {(_Float16)1.0009765625f, (_Float16)1.0009765625f}, sh = {(_Float16)(lane * 1e-4f), (_Float16)0.f};
-#pragma unroll
-      for (int ks = 0; ks < 2; ++ks)
-#pragma unroll
-        for (int i = 0; i < MT; ++i)
-#pragma unroll
-          for (int e = 0; e < 8; e += 2) {
-            h2 y = h2{xf[ks][i][e], xf[ks][i][e + 1]} * sc + sh;
-            const h2 ex = {(_Float16)__builtin_amdgcn_exp2f((float)(y[0] * (_Float16)-1.4427f)), (_Float16)__builtin_amdgcn_exp2f((float)(y[1] * (_Float16)-1.4427f))};
-            const h2 den = ex + h2{(_Float16)1.f, (_Float16)1.f};
-            y = y * h2{(_Float16)__builtin_amdgcn_rcpf((float)den[0]), (_Float16)__builtin_amdgcn_rcpf((float)den[1])};
-            xf[ks][i][e] = y[0]; xf[ks][i][e + 1] = y[1];
-          }
-    }
-#endif
 #pragma unroll
     for (int ks = 0; ks < 2; ++ks)
 #pragma unroll
@@ -527,9 +481,6 @@ __device__ __forceinline__ void gemm2_body(const GemmParams& p, int tiles_n, int
 #pragma unroll
         for (int j = 0; j < NT; ++j)
           acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wf[ks][j], xf[ks][i], acc[i][j], 0, 0, 0);
-#ifdef SKG_LAB
-    if (!(p.flags & 0x2000u))
-#endif
     sched_plan<MT, NT, ND>();
   };
 
@@ -611,96 +562,8 @@ __device__ __forceinline__ void gemm2_body(const GemmParams& p, int tiles_n, int
         }
       }
     }
-    if constexpr (FIX) {
-      __shared__ unsigned s_ticket;
-      const int splits = nwg / ntiles;
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // this thread's slab stores sit in this XCD's L2
-      __syncthreads();
-      if (tid < 64) __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");      // ONE L2 write-back per workgroup (buffer_wbl2 sc1), no invalidate
-      if (tid == 0) s_ticket = atomicInc(p.ws_cnt + (tile_m * tiles_n + tile_n), (unsigned)(splits - 1));      // wraps to 0 at the last ticket
-      __syncthreads();
-      if (s_ticket == (unsigned)(splits - 1)) {          // workgroup-uniform
-        constexpr int N4 = BN / 4;
-        const size_t slab_sz = (size_t)p.M * p.N;
-        for (int i = tid; i < BM * N4; i += NTHR) {
-          const int r = i / N4;
-          const size_t m = (size_t)(m0 + r);
-          const int n = n0 + (i - r * N4) * 4;
-          if (m >= (size_t)p.M || n >= p.N) continue;
-          float4_t v = ld_agent(ws + m * p.N + n);
-          for (int sp = 1; sp < splits; ++sp) v += ld_agent(ws + sp * slab_sz + m * p.N + n);
-          splitk_epilogue(p, v, m, n);
-        }
-      }
-    }
     continue;
   }
-#ifdef SKG_LAB      // measured and withdrawn (EXPERIMENTS.md round 5: bit-equal outputs, 10-20 % SLOWER on every shape): lab build, SKG_DIRECT_EPI=1|2
-  // ---- register-direct epilogue (round 5; flag 0x10000 from the launcher: fp16 output, N % BN == 0, 16-byte aligned rows, no
-  // GEGLU / pair / statistics / row map).  v_permlane16_swap between the accumulator tiles (j, j + 1) of a 16-row fragment
-  // gives every lane 8 CONSECUTIVE columns of its row - lane group g holds columns 16 (g & 1) + 8 (g >> 1) .. + 7 of the
-  // 32-column pair - so the residual is one 16-byte load and the output one 16-byte store per lane, 64-byte runs per row and
-  // instruction (the rate of whole rows, EXPERIMENTS.md "store-instruction shape"), with NO LDS staging and NO barrier: a wave
-  // that has finished its K loop stores and leaves (or starts its next tile) without waiting for the other three, and the
-  // co-resident workgroup's K loop runs under it.  An odd last tile column pairs the fragments (i, i + 1) instead (32-byte runs).
-  if (!HILO && !GNS && (p.flags & 0x10000u)) {
-    const int cb = (g & 1) * 16 + (g >> 1) * 8;
-    auto emit = [&](float (&v)[8], int m, int n) {
-      if (m >= p.M) return;
-      half8_t bz = zero_half8();
-      if (p.bias) bz = ld_half8(p.bias + n);
-      float x[8];
-#pragma unroll
-      for (int e = 0; e < 8; ++e) x[e] = (v[e] + (float)bz[e]) * p.alpha;
-      if (p.res) {
-        const half8_t r = ld_half8(p.res + (size_t)m * p.ldr + n);
-#pragma unroll
-        for (int e = 0; e < 8; ++e) x[e] += (float)r[e];
-      }
-      if (relu) {
-#pragma unroll
-        for (int e = 0; e < 8; ++e) x[e] = fmaxf(x[e], 0.f);
-      }
-      half8_t o;
-#pragma unroll
-      for (int e = 0; e < 8; ++e) o[e] = (half_t)x[e];
-      half8_t* dst = reinterpret_cast<half8_t*>(reinterpret_cast<half_t*>(p.C) + (size_t)m * p.ldc + n);
-      if (stream_out) __builtin_nontemporal_store(o, dst);
-      else *dst = o;
-    };
-    auto swap8 = [&](const float4_t& a, const float4_t& b, float (&v)[8]) {
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const float fa = a[e], fb = b[e];      // (scalar copies: __builtin_bit_cast on a vector element reads element 0)
-        const auto sw = __builtin_amdgcn_permlane16_swap(__builtin_bit_cast(unsigned, fa), __builtin_bit_cast(unsigned, fb), false, false);
-        const unsigned s0 = sw[0], s1 = sw[1];
-        v[e] = __builtin_bit_cast(float, s0);
-        v[4 + e] = __builtin_bit_cast(float, s1);
-      }
-    };
-#pragma unroll
-    for (int i = 0; i < MT; ++i) {
-      const int m = m0 + wm * WM + i * 16 + l16;
-#pragma unroll
-      for (int j = 0; j + 1 < NT; j += 2) {
-        float v[8];
-        swap8(acc[i][j], acc[i][j + 1], v);
-        emit(v, m, n0 + wn * WN + j * 16 + cb);
-      }
-    }
-    if constexpr (NT & 1) {
-      static_assert(MT % 2 == 0, "odd tile column: fragments pair up over rows");
-#pragma unroll
-      for (int i = 0; i < MT; i += 2) {
-        float v[8];
-        swap8(acc[i][NT - 1], acc[i + 1][NT - 1], v);
-        emit(v, m0 + wm * WM + (i + (g & 1)) * 16 + l16, n0 + wn * WN + (NT - 1) * 16 + (g >> 1) * 8);
-      }
-    }
-    SKG_PH(3); SKG_PH(4);
-    continue;
-  }
-#endif
   const bool staged = HILO ||      // (launcher-checked alignment)
                       (!f32out && (p.ldc % 8 == 0) && ((reinterpret_cast<uintptr_t>(p.C) & 15) == 0) &&
                        (!p.res || ((p.ldr % 8 == 0) && (reinterpret_cast<uintptr_t>(p.res) & 15) == 0)));
@@ -1087,19 +950,8 @@ __global__ __launch_bounds__(WGM * WGN * 64, (NS * (BM + BN) * BK * 2 + 8 * BN <
                                                                   unsigned a_bytes, unsigned b_bytes,
                                                                   unsigned a_shift, int kt_per_split,
                                                                   float* __restrict__ ws) {
-  gemm2_body<BM, BN, WGM, WGN, MODE, NS, GNS, HILO, false, BROWS>(p, tiles_n, nwg, a_bytes, b_bytes, a_shift, kt_per_split, ws);
+  gemm2_body<BM, BN, WGM, WGN, MODE, NS, GNS, HILO, BROWS>(p, tiles_n, nwg, a_bytes, b_bytes, a_shift, kt_per_split, ws);
 }
-#ifdef SKG_LAB
-// the self-finishing split-K launch (see FIX above; WITHDRAWN, lab build only: EXPERIMENTS.md round 4): its own kernel, so that
-// the plain instantiations stay as they were tuned
-template <int BM, int BN, int WGM, int WGN, int MODE>
-__global__ __launch_bounds__(WGM * WGN * 64, (2 * (BM + BN) * BK * 2 + 8 * BN <= 80 * 1024) ? 2 : 1) void gemm2_splitk_kernel(const GemmParams p, int tiles_n, int nwg,
-                                                                  unsigned a_bytes, unsigned b_bytes,
-                                                                  unsigned a_shift, int kt_per_split,
-                                                                  float* __restrict__ ws) {
-  gemm2_body<BM, BN, WGM, WGN, MODE, 2, false, false, true>(p, tiles_n, nwg, a_bytes, b_bytes, a_shift, kt_per_split, ws);
-}
-#endif
 
 // out = epi(sum_s slab[s]) for a split-K launch; 4 outputs per thread
 __global__ __launch_bounds__(256) void splitk_reduce_kernel(const GemmParams p, const float* __restrict__ ws,
@@ -1117,9 +969,8 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(const GemmParams p, 
 }
 
 
-// Tuning values of the split-K policy (tools/smallm_bench.py --splits / --split-stages), ONE helper for launch_cfg, pick_splits and
-// skg_gemm2_tile_n: validated, read once per process in the product build; the lab build re-reads them per launch so
-// that the tool can walk its variants in one process (SKG_LIB=.../libskg_lab.so).
+// Tuning values of the split-K policy (SKG_SPLIT_TARGET, SKG_MAX_SPLITS, SKG_SPLIT_NS), ONE helper for launch_cfg, pick_splits and
+// skg_gemm2_tile_n: validated, read once per process.
 struct SplitTuning { int target, smax, ns; };
 inline SplitTuning read_split_tuning() {
   auto geti = [](const char* n, int dflt) { const char* e = getenv(n); return e ? atoi(e) : dflt; };
@@ -1130,12 +981,8 @@ inline SplitTuning read_split_tuning() {
   return t;
 }
 inline SplitTuning split_tuning() {
-#ifdef SKG_LAB
-  return read_split_tuning();
-#else
   static const SplitTuning t = read_split_tuning();
   return t;
-#endif
 }
 
 // number of K splits for a launch of `nwg` 128-row tiles over KT K-tiles (1 = no split)
@@ -1236,22 +1083,8 @@ void launch_cfg(const GemmParams& p_in, hipStream_t st) {
   const size_t out_bytes = (size_t)p.M * ((p.flags & SKG_EPI_GEGLU) ? p.N / 2 : p.N) * ((p.flags & SKG_EPI_OUT_F32) ? 4 : 2);
   static const bool tap_major = getenv("SKG_TAP_MAJOR") != nullptr;        // A/B switch for the K order (tools/gemm_bench.py)
   if (MODE != MODE_DIRECT && !tap_major) p.flags |= 0x1000u;
-#ifdef SKG_LAB
-  if (MODE != MODE_DIRECT && getenv("SKG_GLUE_PROBE")) p.flags |= 0x2000u;      // cost probe, wrong results (see the K loop)
-#endif
   static const char* smb = getenv("SKG_STREAM_MB");          // tuning only
   if (out_bytes >= (smb ? (size_t)atoi(smb) << 20 : STREAM_OUT_BYTES)) p.flags |= 0x800u;
-#ifdef SKG_LAB
-  // register-direct epilogue (no LDS staging, no barriers): A/B switch SKG_DIRECT_EPI (1 = every eligible launch, 2 = only
-  // K <= 640: the launches whose epilogue weighs as much as their K loop)
-  static const int direct_epi = getenv("SKG_DIRECT_EPI") ? atoi(getenv("SKG_DIRECT_EPI")) : 0;
-  const bool direct_ok = direct_epi && !(p.flags & (SKG_EPI_GEGLU | SKG_EPI_OUT_F32)) && !p.c_lo && !p.res_lo && !p.gn_partial && !p.up2 &&
-                         !p.seg_rows && !p.ntaps && !p.bias_pitch && p.N % BN == 0 && p.ldc % 8 == 0 && skg_aligned(p.C, 16) &&
-                         (!p.res || (p.ldr % 8 == 0 && skg_aligned(p.res, 16))) && (!p.bias || skg_aligned(p.bias, 16)) &&
-                         (direct_epi == 1 || p.K <= 640);
-#else
-  constexpr bool direct_ok = false;
-#endif
   const int tiles_n = skg_cdiv(p.N, BN);
   const int ntiles = skg_cdiv(p.M, BM) * tiles_n * (p.up2 == 5 ? 4 : 1);      // (5: the four polyphase launches in one grid)
   unsigned long long a, b, s;
@@ -1266,7 +1099,6 @@ void launch_cfg(const GemmParams& p_in, hipStream_t st) {
   // tiles that can span samples (or a launch that would take the direct stores: fp32 output, an unaligned output or residual) run the BROWS instantiations (launch_mode: BM = 128)
   if (p.bias_pitch && (p.gn_hw % BM != 0 || (p.flags & SKG_EPI_OUT_F32) || p.ldc % 8 != 0 || !skg_aligned(p.C, 16) || (p.res && (p.ldr % 8 != 0 || !skg_aligned(p.res, 16)))))
     p.flags |= SKG_FLAG_BIAS_PER_ROW;
-  if (direct_ok && splits == 1) p.flags |= 0x10000u;
   // XCDs per K slice: all 8 without split-K; 8 / ns when the slices line up with XCD boundaries
   const int ns_eff = splits > 1 ? skg_cdiv(KT, skg_cdiv(KT, splits)) : 1;
   const int G = (8 % ns_eff == 0) ? 8 / ns_eff : 0;
@@ -1291,18 +1123,8 @@ void launch_cfg(const GemmParams& p_in, hipStream_t st) {
   if (splits > 1) {
     const int per = skg_cdiv(KT, splits);
     const int ns = skg_cdiv(KT, per);            // every split non-empty
-#ifdef SKG_LAB
-    if constexpr (BM == 128) {
-      const bool self = getenv("SKG_SPLITK_SELF") != nullptr;      // (read per launch) the withdrawn self-finishing form instead of the reduce launch
-      if (p.ws_cnt && self && (size_t)ntiles * 4 <= SKG_WS_TICKET_BYTES && p.N % 4 == 0) {
-        hipLaunchKernelGGL((gemm2_splitk_kernel<BM, BN, WGM, WGN, MODE>), dim3(ntiles * ns), dim3(NTHR), 0, st, p, tiles_n, ntiles * ns,
-                           (unsigned)a, (unsigned)b, (unsigned)s, per, p.ws);
-        return;
-      }
-    }
-#endif
     // at most one workgroup per CU anyway: a deeper LDS ring (three / four stages, 110 / 147 KB) keeps two / three operand tiles of
-    // its K slice in flight where the two-stage kernel waits out one DMA latency per step (SKG_SPLIT_NS, read per launch: tuning)
+    // its K slice in flight where the two-stage kernel waits out one DMA latency per step (SKG_SPLIT_NS: tuning)
     bool deep = false;
     if constexpr (BM == 128 && BN == 160 && (MODE == MODE_DIRECT || MODE == MODE_S1)) {
       const int sns = split_tuning().ns;
@@ -1351,17 +1173,6 @@ void launch_cfg(const GemmParams& p_in, hipStream_t st) {
   // 128 x 64 tile always (74 KB: two workgroups per CU still fit)
   if constexpr (BM == 128 && (BN == 160 || BN == 64) && (MODE == MODE_DIRECT || MODE == MODE_S1)) {
     static const bool off = getenv("SKG_NO_NS3") != nullptr;        // A/B switch (tools/gemm_bench.py)
-#ifdef SKG_LAB      // round-5 probe (tools/smallm_bench.py --stages): deeper rings for the launches with one workgroup per CU anyway -
-    // SKG_NS (read per launch) = 4 (128 x 160: 148 KB of LDS; 128 x 64: 98 KB) or 6 (128 x 64 only: 148 KB)
-    if (!off && !gns && !hilo && ntiles <= 256) {
-      const char* e = getenv("SKG_NS");
-      const int ns = e ? atoi(e) : 0;
-      if (ns == 4 && KT >= 5) { G2_LAUNCH(4, false, false); return; }
-      if constexpr (BN == 64) {
-        if (ns == 6 && KT >= 7) { G2_LAUNCH(6, false, false); return; }
-      }
-    }
-#endif
     if (!off && KT >= 4 && (BN == 64 || ntiles <= 256)) {
       if constexpr (BN == 160) {
         if (gns) {

@@ -22,7 +22,8 @@
 // Two tiles: 256 x 160 (wave grid 4 x 2, three stages, prefetch distance two tiles) and 256 x 320 (wave grid 2 x 4, wave
 // tile 128 x 80, TWO stages of 73.7 KB: the whole next tile is requested in LOAD(2t) and waited for with vmcnt(0) at the
 // end of LOAD(2t + 1); 7 B of operands per kFLOP) - the latter only where one workgroup per CU still fills the chip,
-// i.e. the 64 x 64 level at 16 rows.
+// i.e. the 64 x 64 level at 16 rows.  Only the 256 x 320 tile is launched: the 256 x 160 form was withdrawn (EXPERIMENTS.md);
+// the kernel template still describes both geometries.
 // Scope: MODE_DIRECT and MODE_S1, K % 64 == 0 (conv: Cin % 64 == 0), N % 160 == 0, fp16 output, no fused GEGLU, no
 // split-K; everything else stays on gemm2.hip.  Epilogue: bias / alpha / residual / ReLU in fp32, one rounding.
 #include "gemm_params.h"
@@ -41,13 +42,14 @@ __device__ __forceinline__ void dma16(__amdgpu_buffer_rsrc_t rsrc, half_t* lds_w
 }
 __device__ __forceinline__ void bar() { asm volatile("s_barrier" ::: "memory"); }
 
-// EXP: probe builds (SKG_G8_EXP; compute on stale / missing data, timing only): 1 = no DMA in the loop, 2 = no
-// fragment reads in the loop, 4 = no priority raise, 8 = no stagger between the two groups
+// EXP: always 0 (the timing probes it selected are withdrawn); the parameter stays because the instantiation name is part of what
+// the benchmark reports
 // HILO: the accuracy-mode epilogue (skg_*_hilo): the residual is the pair p.res + p.res_lo, the output the pair
 // hi = fp16(v) -> p.C, lo = fp16(v - hi) -> p.c_lo (same leading dimensions); statistics (GNS) are those of hi
 template <int BN, int MODE, int EXP = 0, bool GNS = false, bool HILO = false>
 __global__ __launch_bounds__(NTHR, 2) void gemm8_kernel(const GemmParams p, int tiles_n, int nwg, unsigned a_bytes,
                                                         unsigned b_bytes, unsigned a_shift) {
+  static_assert(EXP == 0, "placeholder");
   constexpr int NS = BN == 160 ? 3 : 2;            // LDS stages
   constexpr int WGN = BN / 80, WGM = NW / WGN;     // wave grid: 4 x 2 (BN = 160) or 2 x 4 (BN = 320)
   constexpr int WM = BM / WGM, WN = 80, MT = WM / 16;
@@ -195,24 +197,20 @@ __global__ __launch_bounds__(NTHR, 2) void gemm8_kernel(const GemmParams p, int 
   // one sub-step of one wave: LOAD segment, barrier, COMPUTE segment, barrier
   auto substep = [&](int t, int stg, int ks) {        // stg, ks: compile-time constants at every call site
     const half_t* sb = &smem[stg * STAGE];
-    if (!(EXP & 2) || t == 0) {
 #pragma unroll
-      for (int j = 0; j < NT; ++j) wf[j] = ld_half8(sb + b_base[ks] + j * 16 * BK);
+    for (int j = 0; j < NT; ++j) wf[j] = ld_half8(sb + b_base[ks] + j * 16 * BK);
 #pragma unroll
-      for (int i = 0; i < MT; ++i) xf[i] = ld_half8(sb + a_base[ks] + i * 16 * BK);
-    }
-    if (!(EXP & 1)) {
-      if (NS == 3) {          // tile t + 2 into stage (stg + 2) % 3, whose last reader finished two barriers ago
-        const int nbuf = stg == 0 ? 2 : stg - 1;
-        if (ks == 0) dma_a(t + 2, nbuf);
-        else dma_b(t + 2, nbuf);
-      } else if (ks == 0) {   // tile t + 1 into the other stage: its last reader was group 1's LOAD(2t - 1), one barrier ago
-        dma_a(t + 1, stg ^ 1);
-        dma_b(t + 1, stg ^ 1);
-      }
+    for (int i = 0; i < MT; ++i) xf[i] = ld_half8(sb + a_base[ks] + i * 16 * BK);
+    if (NS == 3) {          // tile t + 2 into stage (stg + 2) % 3, whose last reader finished two barriers ago
+      const int nbuf = stg == 0 ? 2 : stg - 1;
+      if (ks == 0) dma_a(t + 2, nbuf);
+      else dma_b(t + 2, nbuf);
+    } else if (ks == 0) {   // tile t + 1 into the other stage: its last reader was group 1's LOAD(2t - 1), one barrier ago
+      dma_a(t + 1, stg ^ 1);
+      dma_b(t + 1, stg ^ 1);
     }
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    if (ks == 1 && !(EXP & 1)) {
+    if (ks == 1) {
       // the tile that LOAD(2t + 2) reads must have landed before the barrier below.  Three stages: the newest tile's
       // ND instructions may stay in flight.  Two stages: the tile requested in LOAD(2t) is the one - drain.
       if (NS == 3) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(ND) : "memory");
@@ -221,13 +219,13 @@ __global__ __launch_bounds__(NTHR, 2) void gemm8_kernel(const GemmParams p, int 
     __builtin_amdgcn_sched_barrier(0);
     bar();
     __builtin_amdgcn_sched_barrier(0);
-    if (!(EXP & 4)) __builtin_amdgcn_s_setprio(1);
+    __builtin_amdgcn_s_setprio(1);
 #pragma unroll
     for (int i = 0; i < MT; ++i)
 #pragma unroll
       for (int j = 0; j < NT; ++j)
         acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wf[j], xf[i], acc[i][j], 0, 0, 0);
-    if (!(EXP & 4)) __builtin_amdgcn_s_setprio(0);
+    __builtin_amdgcn_s_setprio(0);
     __builtin_amdgcn_sched_barrier(0);
     bar();
     __builtin_amdgcn_sched_barrier(0);
@@ -242,8 +240,7 @@ __global__ __launch_bounds__(NTHR, 2) void gemm8_kernel(const GemmParams p, int 
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   }
   bar();
-  if (EXP & 1) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  if (grp == 1 && !(EXP & 8)) bar();                   // group 1 runs one barrier behind group 0
+  if (grp == 1) bar();                   // group 1 runs one barrier behind group 0
   for (int t = 0; t < KT; t += NS) {
     substep(t, 0, 0);
     substep(t, 0, 1);
@@ -256,7 +253,7 @@ __global__ __launch_bounds__(NTHR, 2) void gemm8_kernel(const GemmParams p, int 
       substep(t + 2, 2, 1);
     }
   }
-  if (grp == 0 && !(EXP & 8)) bar();
+  if (grp == 0) bar();
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");     // the last tiles' zero-fill DMA
 
   // ---- epilogue: lane holds C[m = .. + l16][n = .. + 4g .. 4g + 3] --------------------------------------------------
@@ -393,17 +390,14 @@ inline bool operand_bytes(const GemmParams& p, int mode, unsigned long long& a, 
   return a < 0x7fffffffull && b < 0x7fffffffull;
 }
 
-// SKG_GEMM8 (read once): 0 = off; 1 = both tiles for every eligible shape (lab build only: `make lab`; the 256 x 160 form
-// and the probe instantiations are not part of libskg.so); 2 = the 256 x 320 tile for
-// long-K launches (K >= 1024) of both modes; unset = what ships: the 256 x 320 tile for 3x3 convolutions only - same
-// box, interleaved (tools/gemm8_bench.py, profiles/r02_gemm8_320.txt): conv 640->320 @ 64x64 213-221 -> 199 us, 960->320
+// SKG_GEMM8 (read once): 0 = off; 2 = the 256 x 320 tile for long-K launches (K >= 1024) of both modes; unset (or 1, which
+// once selected the withdrawn 256 x 160 form) = what ships: the 256 x 320 tile for 3x3 convolutions only - same
+// box, interleaved (profiles/r02_gemm8_320.txt): conv 640->320 @ 64x64 213-221 -> 199 us, 960->320
 // 306-327 -> 275-292 us (1.24-1.32 PFLOP/s), 320->320 124-127 -> 121 us; the FF2 GEMM (K = 1280) is 5 % SLOWER with the
 // direct-store epilogue and stays on gemm2.hip, like every shape the 256 x 160 tile would take.
 int gemm8_mode() {
   static const int v = getenv("SKG_GEMM8") ? atoi(getenv("SKG_GEMM8")) : 3;
-#ifndef SKG_LAB
   if (v == 1) return 3;
-#endif
   return v;
 }
 
@@ -423,76 +417,40 @@ int gemm8_tile(const GemmParams& p, int mode) {
   unsigned long long a, b, s;
   if (!operand_bytes(p, mode, a, b, s)) return 0;
   const long tm = skg_cdiv(p.M, BM);
-  // 256 x 320 where one workgroup per CU fills the chip in whole rounds; else 256 x 160 (mode 1 only)
+  // 256 x 320 where one workgroup per CU fills the chip in whole rounds
   if (md == 3 && mode != MODE_S1) return 0;
-  if (p.N % 320 == 0 && (md == 1 || p.K >= 1024)) {
+  if (p.N % 320 == 0 && p.K >= 1024) {
     const long t = tm * (p.N / 320);
     if (t >= 224 && (t <= 256 || t >= 480)) return 320;
   }
-  if (md == 1 && !hilo && p.N % 160 == 0 && tm * (p.N / 160) >= 224) return 160;
   return 0;
 }
 
 // the 256 x 320 instantiation writes the GroupNorm partials itself when every tile is whole, the 128-row halves stay
 // inside one sample and no group straddles a wave's 80 columns
 inline bool gn_fusable8(const GemmParams& p, int mode) {
-#ifdef SKG_LAB
-  // probe instantiations (SKG_G8_EXP) have no statistics epilogue: the caller must run the stand-alone pass
-  static const bool probe = getenv("SKG_G8_EXP") && atoi(getenv("SKG_G8_EXP")) != 0;
-  if (probe) return false;
-#endif
   if (!p.gn_partial || p.gn_groups <= 0 || p.gn_hw <= 0 || mode != MODE_S1 || gemm8_tile(p, mode) != 320) return false;
   if (p.M % 256 != 0 || p.gn_hw % 128 != 0 || p.M % p.gn_hw != 0 || p.N % p.gn_groups != 0) return false;
   const int cpg = p.N / p.gn_groups;
   return !(cpg & 1) && 80 % cpg == 0;
 }
 
-template <int BN>
 void launch8(const GemmParams& p_in, int mode, hipStream_t st) {
+  constexpr int BN = 320;
   GemmParams p = p_in;
-  if (BN == 320 && gn_fusable8(p, mode)) p.flags |= SKG_FLAG_GN_STATS;
+  if (gn_fusable8(p, mode)) p.flags |= SKG_FLAG_GN_STATS;
   unsigned long long a, b, s;
   operand_bytes(p, mode, a, b, s);
   const int tiles_n = p.N / BN;
   const int ntiles = skg_cdiv(p.M, BM) * tiles_n;
-#ifdef SKG_LAB
-  static const int exp = getenv("SKG_G8_EXP") ? atoi(getenv("SKG_G8_EXP")) : 0;
-#else
-  constexpr int exp = 0;
-#endif
-#define G8_LAUNCH(M_, E_) hipLaunchKernelGGL((gemm8_kernel<BN, M_, E_>), dim3(ntiles), dim3(NTHR), 0, st, p, tiles_n, ntiles, \
-                                             (unsigned)a, (unsigned)b, (unsigned)s)
-  if (mode == MODE_DIRECT) {
-    G8_LAUNCH(MODE_DIRECT, 0);
+#define G8_LAUNCH(M_, GNS_, HILO_) hipLaunchKernelGGL((gemm8_kernel<BN, M_, 0, GNS_, HILO_>), dim3(ntiles), dim3(NTHR), 0, st, p, tiles_n, ntiles, \
+                                                      (unsigned)a, (unsigned)b, (unsigned)s)
+  const bool gns = (p.flags & SKG_FLAG_GN_STATS) != 0;
+  if (mode == MODE_DIRECT) G8_LAUNCH(MODE_DIRECT, false, false);
+  else if (p.c_lo || p.res_lo) {      // accuracy mode
+    if (gns) G8_LAUNCH(MODE_S1, true, true); else G8_LAUNCH(MODE_S1, false, true);
   } else {
-    switch (exp) {
-#ifdef SKG_LAB
-      case 1: G8_LAUNCH(MODE_S1, 1); break;
-      case 2: G8_LAUNCH(MODE_S1, 2); break;
-      case 3: G8_LAUNCH(MODE_S1, 3); break;
-      case 4: G8_LAUNCH(MODE_S1, 4); break;
-      case 8: G8_LAUNCH(MODE_S1, 8); break;
-#endif
-      default:
-        if constexpr (BN == 320) {
-          if (p.c_lo || p.res_lo) {      // accuracy mode
-            if (p.flags & SKG_FLAG_GN_STATS)
-              hipLaunchKernelGGL((gemm8_kernel<BN, MODE_S1, 0, true, true>), dim3(ntiles), dim3(NTHR), 0, st, p, tiles_n, ntiles,
-                                 (unsigned)a, (unsigned)b, (unsigned)s);
-            else
-              hipLaunchKernelGGL((gemm8_kernel<BN, MODE_S1, 0, false, true>), dim3(ntiles), dim3(NTHR), 0, st, p, tiles_n, ntiles,
-                                 (unsigned)a, (unsigned)b, (unsigned)s);
-            break;
-          }
-          if (p.flags & SKG_FLAG_GN_STATS) {
-            hipLaunchKernelGGL((gemm8_kernel<BN, MODE_S1, 0, true>), dim3(ntiles), dim3(NTHR), 0, st, p, tiles_n, ntiles,
-                               (unsigned)a, (unsigned)b, (unsigned)s);
-            break;
-          }
-        }
-        G8_LAUNCH(MODE_S1, 0);
-        break;
-    }
+    if (gns) G8_LAUNCH(MODE_S1, true, false); else G8_LAUNCH(MODE_S1, false, false);
   }
 #undef G8_LAUNCH
 }
@@ -504,13 +462,7 @@ bool skg_gemm8_fuses_gn(const GemmParams& p, int mode) { return gn_fusable8(p, m
 int skg_gemm8_tile_n(const GemmParams& p, int mode) { return gemm8_tile(p, mode); }
 
 bool skg_gemm8_try_launch(const GemmParams& p, int mode, hipStream_t st) {
-  const int bn = gemm8_tile(p, mode);
-  if (!bn) return false;
-  if (bn == 320) launch8<320>(p, mode, st);
-#ifdef SKG_LAB
-  else launch8<160>(p, mode, st);
-#else
-  else return false;
-#endif
+  if (!gemm8_tile(p, mode)) return false;
+  launch8(p, mode, st);
   return true;
 }

@@ -1,4 +1,5 @@
-// Parameter block shared by the GEMM / implicit-GEMM conv kernels (gemm.hip: generic v1, gemm2.hip: v2).
+// Parameter block shared by the GEMM / implicit-GEMM conv kernels (gemm.hip: generic v1, gemm2.hip: v2, gemm8.hip: v8) and the
+// Winograd transforms (wino.hip), and the entry points these files offer each other.
 #pragma once
 #include "common.h"
 
@@ -42,9 +43,6 @@ struct GemmParams {
   // split-K workspace of the launch stream (host side: filled by the entry points from the per-stream registry of
   // skg_set_workspace; the kernels get the slab pointer as an argument)
   float* ws; size_t ws_bytes;
-  // tile tickets of the self-finishing split-K launch (gemm2_splitk_kernel): SKG_WS_TICKET_BYTES at the end of the registered
-  // workspace, zeroed at registration and left zero by every launch (nullptr: the launch is followed by splitk_reduce_kernel)
-  unsigned* ws_cnt;
   // a bias row per sample (SKG_EPI_BIAS_ROWS, the 3x3 convolutions): bias is [rows][bias_pitch] and output row m reads bias row
   // m / gn_hw (gn_hw = OH * OW, set by every conv launch; the Winograd output transform knows its sample anyway) (0 = one shared [N] row)
   int bias_pitch;
@@ -57,23 +55,11 @@ constexpr unsigned SKG_FLAG_BIAS_PER_ROW = 0x20000u;
 // v2 (gemm2.hip): returns true and launches if the shape is eligible, false otherwise (nothing launched).
 bool skg_gemm2_try_launch(const GemmParams& p, int mode, hipStream_t st);
 // column width of the tile v2 would use for an M x N output, or 0 if v2 does not take this shape
-constexpr size_t SKG_WS_TICKET_BYTES = 16 << 10;      // 4096 tiles (a split-K launch has at most 256)
 int skg_gemm2_tile_n(int M, int N, int K, int Cin, int mode, size_t ws_bytes);
-// lab build only (tools/lab/gemmws.hip): weight-stationary streaming kernel for N = K = 320 plain GEMMs with M >= 32768
-bool skg_gemmws_eligible(const GemmParams& p, int mode);
-bool skg_gemmws_try_launch(const GemmParams& p, int mode, hipStream_t st);
 // v8 (gemm8.hip): 256 x 320 tiles, one 8-wave workgroup per CU, ping-pong schedule (S1 convolutions of the 64 x 64 level).
 bool skg_gemm8_eligible(const GemmParams& p, int mode);
-int skg_gemm8_tile_n(const GemmParams& p, int mode);      // 160 / 320, or 0 when v8 does not take the launch
+int skg_gemm8_tile_n(const GemmParams& p, int mode);      // 320, or 0 when v8 does not take the launch
 bool skg_gemm8_try_launch(const GemmParams& p, int mode, hipStream_t st);
-// lab build only (tools/lab/gemm9.hip, round 5): hand-placed K loop - self-pipelined waves on 32x32x16 MFMAs, fragment register
-// double buffer, one barrier per K tile, LDS-DMA spread evenly over the MFMA slots (SKG_GEMM9 selects geometry and schedule variant)
-bool skg_gemm9_eligible(const GemmParams& p, int mode);
-bool skg_gemm9_try_launch(const GemmParams& p, int mode, hipStream_t st);
-// k-pair kernel (gemmk.hip): 128 x 160 tiles, one 8-wave workgroup per CU whose two wave groups take alternate K tiles -
-// the launches with at most one tile per CU (DIRECT / S1, plain epilogue, optional split-K across workgroups on top).
-bool skg_gemmk_eligible(const GemmParams& p, int mode);
-bool skg_gemmk_try_launch(const GemmParams& p, int mode, hipStream_t st);
 // out = epi(sum of `splits` fp32 slabs) (gemm2.hip)
 void skg_splitk_reduce_launch(const GemmParams& p, const float* ws, int splits, hipStream_t st);
 // true when the kernel that skg_gemm8 / skg_gemm2 would run for this launch writes p.gn_partial itself

@@ -169,7 +169,7 @@ def test_forced_tiles(force, env):
 def test_gemm8_pingpong_320_tile_convolutions(ops):
     """The 256 x 320 ping-pong tile (gemm8.hip) is what the 64 x 64-level 3x3 convolutions run by default: check that
     the dispatcher really takes it for those shapes and that it agrees with F.conv2d (bias, residual, ragged last tile).
-    (The withdrawn 256 x 160 form and the persistent gemm4 kernel live in tools/lab/, outside libskg.so.)"""
+    (The withdrawn 256 x 160 form and the persistent gemm4 kernel left the tree: EXPERIMENTS.md, "Where the withdrawn code is".)"""
     from sketch2img_amd._lib import lib
     g = torch.Generator().manual_seed(17)
     for rows, hw, cin, cout, res in [(16, 64, 128, 320, True), (15, 64, 128, 320, False), (16, 64, 320, 320, True)]:
@@ -956,7 +956,7 @@ def test_attention_forward(ops, dh, heads, Nq, Nkv):
     else:
         # every other shape: the same 4-wave flash kernel as the transposed-copy path (QT 2 also at d = 40, 4096 tokens: 352 workgroups
         # of 192 queries; QT 3 takes 1024 - tests/test_gpu_attention_fwd.py runs it), fed through ds_read_b64_tr_b16.  (The 8-wave
-        # formulation of round 4, attn_fwd8_kernel, left the product: lab build + SKG_ATTN8 only.)
+        # formulation of round 4 was measured and withdrawn: EXPERIMENTS.md.)
         assert ops.attn_fwd_variant(B, heads, Nq, Nkv, kvs, dh, v_rows=True) == ops.attn_fwd_variant(B, heads, Nq, Nkv, kvs, dh)
         assert torch.equal(o2, o) and torch.equal(lse2, lse)
 

@@ -16,7 +16,7 @@ Deviations from the issue's case list, both because the launcher's rules make th
  * the 256 x 320 ping-pong tile needs >= 224 tiles (gemm8_tile): rows = 16 at 64 x 64, the shape tests/test_host.py and
    test_gemm8_pingpong_320_tile_convolutions use (rows = 2 runs the 128 x 160 tile);
  * split-K needs >= 16 K tiles (pick_splits): Cin = 128 on the same maps (Cin = 64 has 9).  Only the reduce-kernel form is
-   reachable: the self-finishing launch is in the lab build alone.
+   reachable: the self-finishing launch was measured and withdrawn.
 Which instantiation of the LDS-DMA kernel ran (the per-row BROWS ones or the plain ones) is not visible through the C ABI - the
 export set is pinned, skg_gemm_variant does not know the flag.  What the probe shows instead: on spanning tiles and with an fp32
 output (direct stores) a plain instantiation would write the tile's first sample's row (or row 0) to every row of the tile."""
