@@ -573,6 +573,30 @@ int skg_cfg_dpmpp2m_step(const void* eps_u, const void* eps_c, int ld, int lo_of
 int skg_cfg_dpmpp2m_sde_step(const void* eps_u, const void* eps_c, int ld, int lo_off, const float* x, const float* z,
                              float* x0_io, float* x_prev, float* eps_out, int samples, int HW, float g, float alpha_s,
                              float sigma_s, float a, float b, float c, float d, int vpred, void* stream);
+/* ---- sigma-space samplers: Euler and Euler ancestral (diffusers EulerDiscreteScheduler / EulerAncestralDiscreteScheduler).  The
+ * trajectory is x = x0 + sigma*eps with sigma up to 14.6 and the UNet reads x / sqrt(sigma^2 + 1).  Additive entry points
+ * (SKG_ABI_VERSION unchanged).
+ *
+ * The UNet operand of one step - modules/pipeline.py:85-86, torch.cat([latents] * 2) and scheduler.scale_model_input, plus the
+ * layout change of skg_nchw_f32_to_nhwc_f16 - in one launch.  x: float NCHW [samples][C][HW].
+ *   y         fp16 NHWC [dup*samples*HW][Cpad], dup 1 or 2 (the second copy is the CFG twin): half(c_in * x), the fp32 product
+ *             rounded once; columns C..Cpad-1 zero, as skg_nchw_f32_to_nhwc_f16 writes them (c_in = 1 gives its output bit for bit);
+ *   x_scaled  NULL, or float NCHW [samples][C][HW] = c_in * x: latent_model_input, the `latents_prev` the guidance update
+ *             measures its length from (modules/pipeline.py:109, :160). */
+int skg_model_input(const float* x, void* y, float* x_scaled, int samples, int C, int HW, int Cpad, int dup, float c_in,
+                    void* stream);
+/* CFG combine + one Euler / Euler-ancestral update - modules/pipeline.py:99-104 with one of the two schedulers - on float NCHW
+ * latents, eps operands and lo_off as in skg_cfg_ddim_step (the pair's halves are summed in fp32):
+ *   m = eps_u + g*(eps_c - eps_u);  x0 = k_x*x + k_m*m;  d = (x - x0)/sigma;  x_prev = x + dt*d + sigma_up*z
+ * epsilon prediction: k_x = 1, k_m = -sigma; v prediction: k_x = 1/(sigma^2 + 1), k_m = -sigma/sqrt(sigma^2 + 1).
+ * Euler: dt = sigma_next - sigma, sigma_up = 0, z NULL.  Ancestral: sigma_up = sqrt(sigma_next^2 (sigma^2 - sigma_next^2)/sigma^2),
+ * dt = sqrt(sigma_next^2 - sigma_up^2) - sigma, z a caller-drawn N(0, 1) float NCHW like x; the last step (sigma_next = 0) has
+ * sigma_up = 0 and dt = -sigma: x_prev = x0.  The scalars are float64 host arithmetic cast once (sampler.py EulerTables.coeffs).
+ * eps_out (nullable) receives d.  z NULL with sigma_up != 0 is SKG_E_BADARG, nothing launched; every product is rounded before
+ * its sum, so sigma_up = 0 with a finite z gives the z = NULL result bit for bit. */
+int skg_cfg_euler_step(const void* eps_u, const void* eps_c, int ld, int lo_off, const float* x, const float* z, float* x_prev,
+                       float* eps_out, int samples, int HW, float g, float sigma, float k_x, float k_m, float dt, float sigma_up,
+                       void* stream);
 /* guidance update, modules/pipeline.py:159-161, per sample s:
  *   g = -grad[s] (fp16 NHWC [HW][ld], first 4 ch);  alpha = sqrt(2)*||x_in - x_prev|| / ||g|| * beta
  *   x_prev += alpha * g.   aux float [samples][4] receives (alpha, ||g||, ||x_in-x_prev||*sqrt2, 0). */

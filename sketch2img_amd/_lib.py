@@ -32,7 +32,8 @@ LIB_PATH = os.environ.get("SKG_LIB") or os.path.join(_HERE, "libskg.so")
 # skg_cfg_dpmpp2m_sde_step, the DPM-Solver++ 2M step with the noise term of algorithm_type "sde-dpmsolver++";
 # skg_latent_renoise, the img2img start a*init + s*noise and the masked-repaint blend; skg_adamw8_step, AdamW on block-wise
 # quantised 8-bit moments (flat_adamw.FlatAdamW state_bits = 8); skg_attn_fwd_variant, which instantiation skg_attn_fwd runs;
-# skg_conv3x3_small_f16, the 3- and 16-channel convolutions of the ControlNet hint encoder
+# skg_conv3x3_small_f16, the 3- and 16-channel convolutions of the ControlNet hint encoder; skg_model_input and
+# skg_cfg_euler_step, the scaled UNet operand and the step of the Euler / Euler-ancestral samplers
 ABI_VERSION = 6
 
 # spec letters: p = device/host pointer, i = int, f = float, u = unsigned, z = size_t (return only)
@@ -124,6 +125,10 @@ SIGNATURES = {
     "skg_adamw8_step": ("i", "ppppppppppipfffffifpp"),
     # ControlNet hint encoder (controlnet.py): the small-channel 3x3 convolutions, additive entry point, same ABI version
     "skg_conv3x3_small_f16": ("i", "pippiiiiiiipip"),
+    # Euler / Euler ancestral (sampler.py EulerTables): the scaled UNet operand and the sigma-space step, additive entry points,
+    # same ABI version
+    "skg_model_input": ("i", "pppiiiiifp"),
+    "skg_cfg_euler_step": ("i", "ppiippppiiffffffp"),
 }
 
 _CT = {"p": ctypes.c_void_p, "i": ctypes.c_int, "f": ctypes.c_float, "u": ctypes.c_uint,

@@ -504,7 +504,109 @@ __global__ __launch_bounds__(256) void latent_renoise_kernel(const float* init, 
   }
 }
 
+// Sigma-space samplers (Euler, Euler ancestral): the UNet operand of one step.  torch.cat([latents] * 2), scale_model_input and the
+// layout change in one pass over the NHWC output index: Y[d][m][c] = half(c_in * x) for both CFG copies d, zero padding columns as
+// nchw2nhwc_kernel writes them, and - if asked for - the fp32 product itself in x's NCHW layout (the guidance update's x_in).
+// c_in = 1 is nchw2nhwc_kernel's value bit for bit (1 * x is x).
+__global__ __launch_bounds__(256) void model_input_kernel(const float* __restrict__ X, half_t* __restrict__ Y,
+                                                          float* __restrict__ Xs, int rows, int C, int HW, int Cpad, int dup,
+                                                          float c_in) {
+  const size_t total = (size_t)rows * HW * Cpad;
+  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
+    const int c = (int)(i % Cpad);
+    const size_t m = i / Cpad;
+    const size_t b = m / HW;
+    const int p = (int)(m - b * HW);
+    half_t h = (half_t)0.f;
+    if (c < C) {
+      const size_t src = (b * C + c) * HW + p;
+      const float v = c_in * X[src];
+      h = (half_t)v;
+      if (Xs) Xs[src] = v;
+    }
+    Y[i] = h;
+    if (dup == 2) Y[total + i] = h;
+  }
+}
+
+// CFG combine + one Euler / Euler-ancestral update in sigma space (x = x0 + sigma eps) on float NCHW latents, 4 channels:
+//   m = u + g (c - u);  x0 = k_x x + k_m m;  d = (x - x0) / sigma;  x_prev = x + dt d [+ sigma_up z]
+// Every product is rounded before its sum in both instantiations (no fma): the NOISE = true kernel with sigma_up = 0 gives the
+// NOISE = false result bit for bit, whatever (finite) z holds - and each of the fewer than sixteen operations is one fp32 rounding
+// of intermediates bounded by |x| + sigma (|u| + g (|c| + |u|)) + sigma_up |z|.
+__device__ __forceinline__ float euler_x0(float xv, float m, float k_x, float k_m) {
+#pragma clang fp contract(off)
+  return k_x * xv + k_m * m;
+}
+
+__device__ __forceinline__ float euler_advance(float xv, float d, float dt) {
+#pragma clang fp contract(off)
+  return xv + dt * d;
+}
+
+__device__ __forceinline__ float euler_noise(float r, float zv, float sigma_up) {
+#pragma clang fp contract(off)
+  return r + sigma_up * zv;
+}
+
+template <bool NOISE>
+__global__ __launch_bounds__(256) void cfg_euler_kernel(const half_t* __restrict__ eu, const half_t* __restrict__ ec,
+                                                        int ld, int lo_off, const float* __restrict__ x,
+                                                        float* __restrict__ xp, float* __restrict__ eps_out,
+                                                        int samples, int HW, float g, float sigma, float k_x, float k_m,
+                                                        float dt, const float* __restrict__ z, float sigma_up) {
+  const size_t total = (size_t)samples * 4 * HW;
+  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
+    const int p = (int)(i % HW);
+    const size_t t = i / HW;
+    const int ch = (int)(t & 3);
+    const size_t s = t >> 2;
+    const size_t off = (s * HW + p) * ld + ch;
+    float u = (float)eu[off], v = (float)ec[off];
+    if (lo_off) { u += (float)eu[off + lo_off]; v += (float)ec[off + lo_off]; }
+    float m;
+    {
+#pragma clang fp contract(off)
+      m = u + g * (v - u);
+    }
+    const float xv = x[i];
+    const float x0 = euler_x0(xv, m, k_x, k_m);
+    const float d = (xv - x0) / sigma;
+    float r = euler_advance(xv, d, dt);
+    if (NOISE) r = euler_noise(r, z[i], sigma_up);
+    xp[i] = r;
+    if (eps_out) eps_out[i] = d;
+  }
+}
+
 }  // namespace
+
+extern "C" int skg_model_input(const float* x, void* y, float* x_scaled, int samples, int C, int HW, int Cpad, int dup,
+                               float c_in, void* stream) {
+  SKG_REQUIRE(x && y && samples > 0 && C > 0 && HW > 0 && Cpad >= C && (dup == 1 || dup == 2));
+  hipLaunchKernelGGL(model_input_kernel, dim3(ew_grid((size_t)samples * HW * Cpad)), dim3(256), 0, (hipStream_t)stream, x,
+                     (half_t*)y, x_scaled, samples, C, HW, Cpad, dup, c_in);
+  SKG_CHECK_LAUNCH("skg_model_input");
+  return SKG_OK;
+}
+
+extern "C" int skg_cfg_euler_step(const void* eps_u, const void* eps_c, int ld, int lo_off, const float* x, const float* z,
+                                  float* x_prev, float* eps_out, int samples, int HW, float g, float sigma, float k_x,
+                                  float k_m, float dt, float sigma_up, void* stream) {
+  SKG_REQUIRE(eps_u && eps_c && x && x_prev && samples > 0 && HW > 0 && ld >= 4 && sigma > 0.f && sigma_up >= 0.f);
+  SKG_REQUIRE(lo_off >= 0 && (lo_off == 0 || ld >= lo_off + 4));
+  SKG_REQUIRE(z || sigma_up == 0.f);
+  if (z)
+    hipLaunchKernelGGL(cfg_euler_kernel<true>, dim3(ew_grid((size_t)samples * 4 * HW)), dim3(256), 0, (hipStream_t)stream,
+                       (const half_t*)eps_u, (const half_t*)eps_c, ld, lo_off, x, x_prev, eps_out, samples, HW, g, sigma, k_x,
+                       k_m, dt, z, sigma_up);
+  else
+    hipLaunchKernelGGL(cfg_euler_kernel<false>, dim3(ew_grid((size_t)samples * 4 * HW)), dim3(256), 0, (hipStream_t)stream,
+                       (const half_t*)eps_u, (const half_t*)eps_c, ld, lo_off, x, x_prev, eps_out, samples, HW, g, sigma, k_x,
+                       k_m, dt, (const float*)nullptr, 0.f);
+  SKG_CHECK_LAUNCH("skg_cfg_euler_step");
+  return SKG_OK;
+}
 
 extern "C" int skg_latent_renoise(const float* init, const float* noise, const float* mask, int mask_samples, float* x,
                                   int samples, int HW, float a, float s, void* stream) {

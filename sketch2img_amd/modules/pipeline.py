@@ -15,7 +15,8 @@ Around the hot path:
                      (deterministic in the prompt text) and seeded synthetic UNet weights exist for boxes without
                      checkpoints, but only behind the explicit opt-in ``from_pretrained(None)`` / ``synthetic=True``:
                      a path that does not resolve to weights raises.
-Schedulers: DDIM (the BASELINE metric) and DPM-Solver++ 2M (what app.py configures); see `sketch2img_amd.schedulers`.
+Schedulers: DDIM (the BASELINE metric), DPM-Solver++ 2M (what app.py configures), Euler and Euler ancestral; see
+`sketch2img_amd.schedulers`.
 """
 from __future__ import annotations
 
@@ -30,7 +31,9 @@ import numpy as np
 import torch
 
 from ..config import SD15, SD21, UNetConfig, tap_channels
-from ..sampler import DPM_ALGORITHMS, DDIMTables, DPMTables, HipSampler, check_eta, check_generators, draw_noise, start_step
+from ..sampler import (DPM_ALGORITHMS, DDIMTables, DPMTables, EulerTables, HipSampler, check_eta, check_generators, draw_noise,
+                       start_step)
+from ..schedulers import euler_unsupported
 from .latent_predictor import LatentEdgePredictor, hook_unet
 
 logger = logging.getLogger(__name__)      # (the reference: diffusers.utils.logging.get_logger(__name__), modules/pipeline.py:11)
@@ -329,7 +332,8 @@ class AntiGradientPipeline:
             gdev = generator.device if isinstance(generator, torch.Generator) else "cpu"
             latents = torch.randn(shape, generator=generator if isinstance(generator, torch.Generator) else None,
                                   device=gdev, dtype=torch.float32)
-        return latents.to(device=device, dtype=torch.float32)       # init_noise_sigma = 1 for DDIM
+        # (init_noise_sigma = 1 for DDIM and DPM-Solver++; the Euler tables' factor is applied by HipSampler.sample)
+        return latents.to(device=device, dtype=torch.float32)
 
     # ------------------------------------------------------------------ img2img / masked repaint inputs (host side only)
     @staticmethod
@@ -591,6 +595,18 @@ class AntiGradientPipeline:
         if "DDIM" in name and get("clip_sample", False):
             raise NotImplementedError("DDIM clip_sample=True is not implemented (Stable Diffusion uses clip_sample=False; "
                                       "note that diffusers' DDIMScheduler() default is True)")
+        if "EulerDiscrete" in name or "EulerAncestralDiscrete" in name:
+            # "Euler" / "Euler a" (diffusers' classes or schedulers.py's, by class name): sigma-space tables.  The spacing has no
+            # default here - diffusers' constructor says "linspace", SD's model repos ship "leading", and the two start a trajectory at
+            # different sigmas - so a config that does not state it is refused, not guessed (both kinds of object always state it)
+            bad = euler_unsupported(get)
+            if get("timestep_spacing", None) is None:
+                bad.append("a config without timestep_spacing")
+            if bad:
+                raise NotImplementedError(f"{name}: {', '.join(bad)} is not implemented")
+            return EulerTables.make(num_inference_steps, get("num_train_timesteps", 1000), get("beta_start", 0.00085),
+                                    get("beta_end", 0.012), get("timestep_spacing", None), int(get("steps_offset", 0)),
+                                    bool(get("use_karras_sigmas", False)), "Ancestral" in name, vpred)
         if "DPMSolverMultistep" in name or get("algorithm_type", None) is not None:
             algorithm = get("algorithm_type", "dpmsolver++")
             if algorithm not in DPM_ALGORITHMS or get("solver_type", "midpoint") != "midpoint":
@@ -606,7 +622,8 @@ class AntiGradientPipeline:
                                   get("beta_end", 0.012), get("lower_order_final", True), get("solver_order", 2), vpred,
                                   karras, algorithm)
         if "DDIM" not in name and not isinstance(sch, (dict, SimpleNamespace)):
-            raise NotImplementedError(f"{name}: DDIMScheduler and DPMSolverMultistepScheduler are implemented")
+            raise NotImplementedError(f"{name}: DDIMScheduler, DPMSolverMultistepScheduler, EulerDiscreteScheduler and "
+                                      "EulerAncestralDiscreteScheduler are implemented")
         return DDIMTables.make(num_inference_steps, get("num_train_timesteps", 1000), get("beta_start", 0.00085),
                                get("beta_end", 0.012), get("steps_offset", 1), get("set_alpha_to_one", False), vpred)
 

@@ -1126,6 +1126,33 @@ def cfg_dpmpp2m_sde_step(eps_u, eps_c, x, z, x0_io, samples, HW, g, coeffs: Tupl
     return (x_prev, eps_out) if want_eps else x_prev
 
 
+def model_input(x: torch.Tensor, c_in: float, Cpad: int, dup: int = 1, want_scaled: bool = False):
+    """The UNet operand of a sigma-space step: float32 [S, C, H, W] -> fp16 [dup*S*H*W, Cpad] = half(c_in * x), dup = 2 stacking the
+    CFG twin, and - want_scaled - the fp32 product [S, C, H, W] itself.  Returns (operand, scaled or None)."""
+    assert x.is_cuda and x.dtype == torch.float32 and x.is_contiguous() and x.dim() == 4 and dup in (1, 2)
+    S, C, H, W = x.shape
+    out = torch.empty(dup * S * H * W, Cpad, device=x.device, dtype=torch.float16)
+    scaled = torch.empty_like(x) if want_scaled else None
+    check(lib.skg_model_input(_p(x), _p(out), _p(scaled), S, C, H * W, Cpad, dup, c_in, _stream()), "skg_model_input")
+    return out, scaled
+
+
+def cfg_euler_step(eps_u, eps_c, x, z, samples, HW, g, coeffs: Tuple[float, float, float, float, float], want_eps=False,
+                   lo_off: int = 0):
+    """CFG combine + one Euler (z None) or Euler-ancestral step: coeffs = EulerTables.coeffs(i) = (sigma, k_x, k_m, dt, sigma_up),
+    x0 = k_x x + k_m m, d = (x - x0)/sigma, x_prev = x + dt d + sigma_up z.  z: N(0, 1) drawn by the caller, fp32 and contiguous in
+    x's shape; the prediction type is in k_x and k_m.  The returned eps is d."""
+    _f16(eps_u, eps_c)
+    assert z is None or (z.is_cuda and z.dtype == torch.float32 and z.is_contiguous() and z.shape == x.shape), \
+        "z: contiguous fp32 CUDA tensor of the latents' shape"
+    x_prev = torch.empty_like(x)
+    eps_out = torch.empty_like(x) if want_eps else None
+    sigma, k_x, k_m, dt, sigma_up = coeffs
+    check(lib.skg_cfg_euler_step(_p(eps_u), _p(eps_c), _ld(eps_u), lo_off, _p(x), _p(z), _p(x_prev), _p(eps_out), samples, HW, g,
+                                 sigma, k_x, k_m, dt, sigma_up, _stream()), "skg_cfg_euler_step")
+    return (x_prev, eps_out) if want_eps else x_prev
+
+
 def guidance_update(grad, x_in, x_prev, samples, HW, beta):
     """In place: x_prev += alpha * (-grad).  Returns aux [samples,4] = (alpha, ||g||, sqrt2*||dx||, 0)."""
     _f16(grad)

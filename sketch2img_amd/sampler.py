@@ -1,4 +1,4 @@
-"""The sketch-guided sampling loop (DDIM or DPM-Solver++ 2M) on the libskg.so kernels.
+"""The sketch-guided sampling loop (DDIM, DPM-Solver++ 2M, Euler or Euler ancestral) on the libskg.so kernels.
 
 Mirrors the reference's hot loop, modules/pipeline.py:83-115 and apply_anti_gradient :141-161:
   per step  CFG-doubled UNet eval (:85-96) -> CFG combine (:99-101) -> scheduler.step (:104) ->
@@ -10,7 +10,7 @@ indexing); everything that touches a latent runs in HIP kernels.
 A batch of S samples is S independent B = 1 trajectories of the reference (which crashes for B > 1:
 SURVEY Q1): alpha, the BatchNorm statistics and the loss are per sample.
 
-A scheduler (DDIMTables, DPMTables) owns its step: key() is what of it reaches kernel arguments, update() computes its coefficients
+A scheduler (DDIMTables, DPMTables, EulerTables) owns its step: key() is what of it reaches kernel arguments, update() computes its coefficients
 and issues its ops.cfg_*_step call, on an explicit History where the method is multistep.  One StepPlan per sample() call holds the
 call's constants, and StepPlan.key(tab, shape) names the GraphSet that replays them.  HipSampler._run_step - step with the control
 inside its window, then the masked blend - is what the eager loop, a new set's warm-up pass and its captures all run.
@@ -87,6 +87,7 @@ class DDIMTables:
     ratio: int
     v_prediction: bool = False        # scheduler config prediction_type == "v_prediction" (SD2.1-768): the UNet output is v
     has_eta = True                    # (not a field) eta > 0 selects the stochastic step
+    scales_input = False              # (not a field) the UNet reads x as it is
 
     def key(self) -> tuple:
         """Everything of the schedule that ends up in kernel arguments (every field; tests/test_host_sampler_plan.py holds it to that)."""
@@ -175,15 +176,18 @@ def _f32(v: float) -> float:
     return float(np.float32(v))
 
 
-def karras_schedule(alphas_cumprod: torch.Tensor, num_inference_steps: int, rho: float = 7.0):
+def karras_schedule(alphas_cumprod: torch.Tensor, num_inference_steps: int, rho: float = 7.0, sigma_min: Optional[float] = None,
+                    sigma_max: Optional[float] = None):
     """diffusers' use_karras_sigmas=True, final_sigmas_type="zero", in float64 from the fp32 alphas_cumprod table ->
     (sigmas [N + 1] float64 with a final 0, timesteps [N] int64).  sigma(t) = sqrt((1 - abar_t)/abar_t); the N sigmas run from
     sigma(last t) to sigma(0) evenly in sigma^(1/rho) (Karras et al. 2022, eq. 5); the UNet is evaluated at round(tau(sigma_i)),
     tau the piecewise-linear interpolation of t in log sigma over the table, clipped to it (_sigma_to_t).  Two steps may round
-    to one timestep: the step coefficients come from the sigmas."""
+    to one timestep: the step coefficients come from the sigmas.  sigma_min / sigma_max: other ends than the table's (the Euler
+    scheduler spaces between the ends of its own interpolated schedule)."""
     acp = alphas_cumprod.double().numpy()
     table = np.sqrt((1.0 - acp) / acp)
-    lo, hi = table[0] ** (1.0 / rho), table[-1] ** (1.0 / rho)
+    lo = (table[0] if sigma_min is None else sigma_min) ** (1.0 / rho)
+    hi = (table[-1] if sigma_max is None else sigma_max) ** (1.0 / rho)
     sig = (hi + np.linspace(0.0, 1.0, num_inference_steps) * (lo - hi)) ** rho
     logs, ls = np.log(table), np.log(sig)
     low = np.clip(np.searchsorted(logs, ls, side="right") - 1, 0, len(table) - 2)      # the last table entry at or below sigma
@@ -234,6 +238,7 @@ class DPMTables:
                          bool(use_karras_sigmas), algorithm_type, sigmas)
 
     has_eta = False                           # (not a field) diffusers' prepare_extra_step_kwargs drops eta for this scheduler
+    scales_input = False                      # (not a field) the UNet reads x as it is
 
     @property
     def stochastic(self) -> bool:
@@ -349,6 +354,105 @@ class DPMTables:
 
     def sigma(self, t: int) -> float:
         return float((1 - self.alphas_cumprod[t]) ** 0.5)
+
+
+EULER_SPACINGS = ("leading", "trailing", "linspace")
+
+
+@dataclass
+class EulerTables:
+    """diffusers EulerDiscreteScheduler and, with `ancestral`, EulerAncestralDiscreteScheduler ("Euler" / "Euler a"): the trajectory
+    lives in sigma space, x = x0 + sigma eps with sigma = sqrt((1 - abar)/abar) up to 14.6.  The UNet reads x / sqrt(sigma^2 + 1)
+    (c_in: the operand is built by skg_model_input), a trajectory from noise starts at init_noise_sigma times the draw, and the
+    update runs in skg_cfg_euler_step.  Schedule arithmetic in float64 from the fp32 alphas_cumprod table; what reaches a kernel is
+    cast once (_f32).  The sigmas are taken at the schedule's own - under "linspace" spacing fractional - timesteps, the UNet runs at
+    the nearest integer timestep (`timesteps`), as on the Karras DPM path; "leading" and "trailing" timesteps are integers."""
+    alphas_cumprod: torch.Tensor      # (num_train,) fp32 CPU: sigma(t), the LGP's noise level
+    timesteps: np.ndarray             # (T,) int64: where the UNet is evaluated
+    sigmas: np.ndarray                # (T + 1,) float64 descending, a final 0
+    init_noise_sigma: float           # the start latent is this times the N(0, 1) draw
+    ancestral: bool = False           # Euler a: step to sigma_down, then sigma_up z, one N(0, 1) draw per step
+    v_prediction: bool = False
+    has_eta = False                   # (not a field) neither scheduler's step takes eta
+    scales_input = True               # (not a field) the UNet operand is c_in(i) x, not x
+
+    @staticmethod
+    def make(num_inference_steps: int, num_train_timesteps: int = 1000, beta_start: float = 0.00085, beta_end: float = 0.012,
+             timestep_spacing: str = "leading", steps_offset: int = 1, use_karras_sigmas: bool = False, ancestral: bool = False,
+             v_prediction: bool = False) -> "EulerTables":
+        """The defaults are what SD's model repos ship (scaled_linear betas, "leading" spacing, steps_offset 1); diffusers'
+        constructor default is "linspace" with steps_offset 0 (schedulers.EulerDiscreteScheduler).  use_karras_sigmas: rho = 7
+        sigmas between the two ends of the interpolated schedule, each timestep from the rounded log-sigma interpolation
+        (karras_schedule); with `ancestral` this is k-diffusion's "Euler a Karras"."""
+        if timestep_spacing not in EULER_SPACINGS:
+            raise NotImplementedError(f"timestep_spacing={timestep_spacing!r}: {', '.join(map(repr, EULER_SPACINGS))} are implemented")
+        N, M = int(num_inference_steps), int(num_train_timesteps)
+        betas = torch.linspace(beta_start ** 0.5, beta_end ** 0.5, M, dtype=torch.float32) ** 2
+        acp = torch.cumprod(1.0 - betas, dim=0)
+        if timestep_spacing == "leading":
+            ts = (np.arange(0, N) * (M // N))[::-1].astype(np.float64) + steps_offset
+        elif timestep_spacing == "trailing":
+            ts = np.round(np.arange(M, 0, -M / N))[:N] - 1
+        else:
+            ts = np.linspace(0, M - 1, N, dtype=np.float64)[::-1].copy()
+        a64 = acp.double().numpy()
+        sig = np.interp(ts, np.arange(M, dtype=np.float64), np.sqrt((1.0 - a64) / a64))
+        if use_karras_sigmas:
+            sigmas, its = karras_schedule(acp, N, sigma_min=sig[-1], sigma_max=sig[0])
+        else:
+            sigmas, its = np.concatenate([sig, [0.0]]), np.round(ts).astype(np.int64)
+        top = float(sigmas.max())
+        return EulerTables(acp, its, sigmas, math.sqrt(top * top + 1.0) if timestep_spacing == "leading" else top,
+                           bool(ancestral), bool(v_prediction))
+
+    def key(self) -> tuple:
+        """Everything of the schedule that ends up in kernel arguments (every field)."""
+        return (type(self).__name__, tuple(int(t) for t in self.timesteps), bool(self.v_prediction), bool(self.ancestral),
+                float(self.init_noise_sigma), tuple(float(s) for s in self.sigmas)) + _fingerprint(self.alphas_cumprod)
+
+    def noisy(self, eta: float) -> bool:
+        return self.ancestral
+
+    def new_history(self, x: torch.Tensor) -> None:
+        return None                   # a one-step method
+
+    def c_in(self, i: int) -> float:
+        """scale_model_input of entry i: 1 / sqrt(sigma_i^2 + 1)."""
+        s = float(self.sigmas[i])
+        return _f32(1.0 / math.sqrt(s * s + 1.0))
+
+    def sigma_up_down(self, i: int):
+        """(sigma_up, sigma_down) of the ancestral step i -> i + 1 in float64: sigma_up^2 + sigma_down^2 = sigma_next^2; both 0 on
+        the last step."""
+        s, sn = float(self.sigmas[i]), float(self.sigmas[i + 1])
+        up = math.sqrt(sn * sn * (s * s - sn * sn) / (s * s))
+        return up, math.sqrt(max(sn * sn - up * up, 0.0))
+
+    def coeffs(self, i: int):
+        """(sigma, k_x, k_m, dt, sigma_up) of skg_cfg_euler_step for entry i: x0 = k_x x + k_m m (epsilon: 1, -sigma; v:
+        1/(sigma^2 + 1), -sigma/sqrt(sigma^2 + 1)), d = (x - x0)/sigma, x_prev = x + dt d + sigma_up z with dt = sigma_to - sigma,
+        sigma_to = sigma_next (Euler) or sigma_down (ancestral)."""
+        s = float(self.sigmas[i])
+        up, to = self.sigma_up_down(i) if self.ancestral else (0.0, float(self.sigmas[i + 1]))
+        if self.v_prediction:
+            k_x, k_m = 1.0 / (s * s + 1.0), -s / math.sqrt(s * s + 1.0)
+        else:
+            k_x, k_m = 1.0, -s
+        return _f32(s), _f32(k_x), _f32(k_m), _f32(to - s), _f32(up)
+
+    def update(self, i: int, eu, ec, x, z, history, S: int, hw: int, g: float, want_eps: bool, lo_off: int, eta: float):
+        """The scheduler step of entry i (DDIMTables.update); x is the unscaled state."""
+        return ops.cfg_euler_step(eu, ec, x, z if self.ancestral else None, S, hw, g, self.coeffs(i), want_eps, lo_off=lo_off)
+
+    def sigma(self, t: int) -> float:
+        """get_noise_level's factor sqrt(1 - alphas_cumprod[t]) at the integer timestep (modules/pipeline.py:133) - not the Euler
+        sigma, whatever the name."""
+        return float((1 - self.alphas_cumprod[t]) ** 0.5)
+
+    def level(self, j: int):
+        """(a, s) of schedule entry j in 0..T as fp32 floats: a latent at entry j is init + sigma_j eps (the Euler schedulers'
+        add_noise).  Entry T is the clean target (1, 0)."""
+        return 1.0, _f32(float(self.sigmas[j]))
 
 
 def guided_step(i: int, T: int) -> bool:
@@ -513,7 +617,12 @@ class HipSampler:
             raise ValueError("LGP guidance differentiates the cond half of a CFG-doubled batch: classifier_free=False has none")
         if guided and control is not None:
             raise ValueError("a ControlNet on a guided step: the guidance gradient would need the trunk's backward")
-        x32 = ops.nchw_to_nhwc((torch.cat([x, x]) if classifier_free else x).contiguous(), CIN_PAD)
+        if tab.scales_input:
+            # sigma-space schedulers: the UNet (and a ControlNet trunk) reads c_in x; x_in is latent_model_input, which the guidance
+            # update measures its length from (modules/pipeline.py:86, :109, :160) - x itself stays the unscaled state
+            x32, x_in = ops.model_input(x, tab.c_in(i), CIN_PAD, dup=2 if classifier_free else 1, want_scaled=guided)
+        else:
+            x32, x_in = ops.nchw_to_nhwc((torch.cat([x, x]) if classifier_free else x).contiguous(), CIN_PAD), x
         stash = Stash() if guided else None
         # (the two CFG halves of x32 are the same latents: the text-independent front of the UNet runs once)
         fork = guided and self.fork_guidance and not torch.cuda.is_current_stream_capturing()
@@ -567,7 +676,7 @@ class HipSampler:
                 grad, loss = branch["grad"], branch["loss"]
             else:
                 grad, loss = guidance_branch(taps)
-            aux = ops.guidance_update(grad, x, x_prev, S, hw, beta)
+            aux = ops.guidance_update(grad, x_in, x_prev, S, hw, beta)
             aux[:, 3] = loss
         return x_prev, eps_cfg, aux
 
@@ -583,6 +692,9 @@ class HipSampler:
         launches.  Not together with a sketch target, nor with an injector on the UNet.
         eta, generator: DDIM's stochastic step (DDIMTables.coeffs_eta, draw_noise); a generator list holds one per sample.
         DPM-Solver++ ignores eta; its "sde-dpmsolver++" tables draw from `generator` in the same way, once per step.
+        EulerTables (sigma space): latents0 is still the N(0, 1) draw - the trajectory starts at init_noise_sigma times it, and that
+        scaled start is the LGP's noise argument (modules/pipeline.py:75 clones after prepare_latents); with init_latents the start is
+        init + sigma eps and the argument stays the draw eps.  eta is ignored; the ancestral tables draw like the SDE solver.
         classifier_free=False: no CFG - the context prepared on the UNet holds the S cond rows - and no LGP guidance.
         init_latents (fp32 [S,4,h,w]), start_step: img2img.  latents0 is then the noise draw eps, the trajectory starts at
         a*init + s*eps with (a, s) = tab.level(start_step) and runs the entries start_step .. T-1 of the full-length schedule
@@ -626,6 +738,9 @@ class HipSampler:
         if draws_noise(tab, eta):
             check_generators(generator, latents0.shape[0])
         x = latents0.to(dev, torch.float32).contiguous()
+        if tab.scales_input and init_latents is None:
+            # prepare_latents' latents * init_noise_sigma (a*x + 0*x is a*x exactly); the clone below is then the scaled start
+            x = ops.latent_renoise(x, x, _f32(tab.init_noise_sigma), 0.0)
         noise = x.clone()                                     # modules/pipeline.py:75
         if target is not None and tuple(target.shape[-2:]) != tuple(x.shape[-2:]):
             raise ValueError(f"target spatial shape {tuple(target.shape[-2:])} differs from the latents' {tuple(x.shape[-2:])}")
